@@ -4,6 +4,15 @@
     python bench.py --gpus N --steps K --warmup W          # N > 1: starts the N ranks itself (one per GPU, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W              # the driver's form; WORLD_SIZE must equal --gpus
+    python bench.py --gpus 1 --steps K --warmup W --full   # + every side measurement listed below
+    python bench.py ... --dump-outputs DIR                  # + the last timed step's output as DIR/samples.npy
+
+A plain run sets up, runs W untimed and K timed steps, and prints the line with the headline (`value`, `ms_per_step`) and
+nothing else measured: the roofline / kernel table, the update micro-benchmarks, `launch_modes`, `throughput_by_batch`,
+`other_configs`, `latency` and `cpu_baseline` are null unless `--full` is given (their `--no-*` switches still apply there).
+`--dump-outputs DIR` writes what the timed path returned in its last step (the sampled images, float32) as DIR/samples.npy
+(DIR/samples_rank<r>.npy per rank when N > 1); the inputs are seeded, so two builds run with the same arguments can be compared
+output for output.
 
 `--gpus` is checked, never trusted: WORLD_SIZE != --gpus, fewer visible GPUs than ranks, or a communicator that counts a
 different number of ranks all exit non-zero (diff_sampler_amd/launch.py); `n_gpus` in the line comes from an all-reduce.
@@ -13,7 +22,7 @@ at the NFE the metric is quoted on) over a batch of synthetic N(0,1) latents alr
 random-init (signal-carrying) CIFAR-10 SongUNet.  Ranks shard images, nothing is exchanged during sampling
 (SURVEY.md section 8e), so scaling is weak: every rank runs ``--batch`` images per step.
 
-Prints ONE JSON line on rank 0 with the driver's contract fields plus
+Prints ONE JSON line on rank 0 with the driver's contract fields plus (with --full)
   roofline         the dominant kernel (largest share of GPU time; the fp32-MFMA LDS-halo 3x3 convolution):
                    achieved = algorithmic FLOPs of its launches in one sampler step / their summed duration, measured
                    with HIP events on the launch stream in an instrumented replay of the timed workload;
@@ -111,8 +120,15 @@ def parse(argv=None):
     ap.add_argument('--sweep-batches', type=lambda t: [int(v) for v in t.split(',') if v], default=[64, 1024, 4096],
                     help='batches of throughput_by_batch next to --batch (comma separated)')
     ap.add_argument('--no-other-configs', action='store_true', help='skip the other_configs / latency measurements of the default run')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the side measurements (roofline and kernel table, update micro-benchmarks, launch modes, batch sweep, '
+                         'other configurations, latencies, CPU baseline); a plain run times the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's output as DIR/samples.npy (float32, at most 64 MB: a seeded sample of images beyond that)")
     ap.add_argument('--stub', action='store_true', help=argparse.SUPPRESS)   # launcher self-test: gloo ranks on CPU, no kernels
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.solver is None:
         args.solver = 'ipndm' if args.config == 'imagenet64' else 'dpmpp'
     if args.batch is None:
@@ -603,6 +619,26 @@ def measure_config(config, dtype, batch, nfe, dev, calls=5, warmup=2, latency_ba
     return res, lat_ms
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, name, t, budget=DUMP_BYTES):
+    """Write tensor `t` as <dirname>/<name>.npy in float32 (float64 stays float64).  A tensor larger than `budget` bytes keeps a fixed,
+    seeded sample of its images (leading dimension, in ascending order): the same images in every run of the same arguments."""
+    import numpy as np
+    a = t.detach()
+    a = (a if a.dtype == torch.float64 else a.float()).cpu()
+    row = max(1, a[0].numel() * a.element_size()) if a.dim() else 1
+    if a.dim() and a.numel() * a.element_size() > budget:
+        keep = max(1, budget // row)
+        idx = torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        a = a[idx]
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, name + '.npy')
+    np.save(path, a.numpy())
+    return path
+
+
 def main(argv=None):
     from diff_sampler_amd import launch
     args = parse(argv)
@@ -646,7 +682,7 @@ def main(argv=None):
             args.solver = 'dpmpp'
         latents = torch.randn(B, spec.in_channels, spec.img_resolution, spec.img_resolution, generator=g).to(dev)
 
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline_ldm(args, args.nfe) if ldm is not None else cpu_baseline(args, args.nfe)
 
         run_step = lambda: sampler_call(solvers, args.solver, net, latents, args.nfe, ldm)
@@ -693,6 +729,8 @@ def main(argv=None):
                      fid_moment_allreduce=fid_allreduce_timing(dist, dev, world))
     if not stub:
         assert torch.isfinite(out).all()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, 'samples' if world == 1 else f'samples_rank{rank}', out, DUMP_BYTES // world)
 
     roof = roof_u = kernels = roof_norm = None
     if rank == 0 and stub:
@@ -701,7 +739,7 @@ def main(argv=None):
         kernels, roof, dom_id, _ = kernel_report({('conv', 2565): [1.0, 1, 1.0e9]})
         attach_traffic(roof, dom_id, (args.config, args.dtype))
         roof['stub'] = True
-    if rank == 0 and not stub:
+    if rank == 0 and not stub and args.full:
         rec = instrumented_pass(net, solvers, args.solver, latents, args.nfe, ldm)
         kernels, roof, dom_id, total_ms = kernel_report(rec)
         if args.dtype == 'fp16':
@@ -741,7 +779,7 @@ def main(argv=None):
                           note='latency-bound at this batch (3 MB per operand); see roofline_update_large_batch')
 
     roof_ul = roof_ul_other = modes = by_batch = None
-    if rank == 0 and ldm is None and not stub:
+    if rank == 0 and ldm is None and not stub and args.full:
         roof_ul = update_roofline_large_batch(dev, kind=('dpmpp' if args.solver == 'dpmpp' else 'ipndm'))
         roof_ul_other = update_roofline_large_batch(dev, kind=('ipndm' if args.solver == 'dpmpp' else 'dpmpp'))
         if not args.no_launch_modes and world == 1:
@@ -777,7 +815,7 @@ def main(argv=None):
                 torch.cuda.empty_cache()
             by_batch = dict(sorted(by_batch.items(), key=lambda kv: int(kv[0])))
     others = latency = None
-    if (rank == 0 and world == 1 and not stub and not args.no_other_configs and not args.graph
+    if (rank == 0 and world == 1 and not stub and args.full and not args.no_other_configs and not args.graph
             and (args.config, args.dtype, B, args.solver, args.nfe) == ('cifar10', 'fp32', 256, 'dpmpp', 10)):
         # the default run: the other benchmarked configurations / modes and the small-batch latencies, under the same clock
         latency = {}
@@ -816,7 +854,7 @@ def main(argv=None):
             'roofline': roof, 'roofline_norm_act': roof_norm, 'roofline_update': roof_u, 'roofline_update_large_batch': roof_ul, 'roofline_update_large_batch_other_solver': roof_ul_other, 'kernels': kernels,
             'launch_modes': modes, 'throughput_by_batch': by_batch, 'cpu_baseline': cpu, 'multi_gpu': multi,
             'application': (application_fraction(args.config, args.dtype, total_images / dt / world, args.nfe) if not stub and args.config in GFLOP_PER_EVAL else None),
-            'other_configs': others, 'latency': latency,
+            'other_configs': others, 'latency': latency, 'full': args.full,
         }
         if stub:
             line['stub'] = True

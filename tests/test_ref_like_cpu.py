@@ -1,7 +1,7 @@
-"""`tests/_ref_like.py` (the duck-typed EDMPrecond the GPU tests of the real-checkpoint route are built on) against the REAL reference class:
-same state_dict keys in the same order with the same shapes (incl. the `resample_filter` buffers), same attributes, same module-tree
-names -- so that what `spec_from_module` / `from_reference_module` / the persistence hook read from the duck on the GPU box is what they
-would read from an unpickled `edm-*.pkl`.  Needs /root/reference (build container only); skipped on the GPU box."""
+"""`tests/_ref_like.py` (the duck-typed EDMPrecond the GPU tests of the real-checkpoint route are built on) against the REAL reference class,
+as recorded in `tests/golden/ref_structure.json.gz` (`oracle/gen_ref_structure.py`): same state_dict keys in the same order with the same
+shapes and dtypes (incl. the `resample_filter` buffers), same attributes, same module-tree names -- so that what `spec_from_module` /
+`from_reference_module` / the persistence hook read from the duck on the GPU box is what they would read from an unpickled `edm-*.pkl`."""
 import os
 import sys
 
@@ -11,34 +11,23 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
-REF = '/root/reference/diff-solvers-main'
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason='/root/reference is not present on this machine')
-
-
-@pytest.fixture(scope='module')
-def RefPrecond():
-    sys.path.insert(0, REF)
-    try:
-        from models.networks_edm import EDMPrecond as cls
-    finally:
-        sys.path.remove(REF)
-    return cls
 
 
 @pytest.mark.parametrize('name', ['cifar10', 'ffhq', 'imagenet64', 'tiny_song', 'tiny_song_cond', 'tiny_adm', 'tiny_song_amed'])
 @pytest.mark.parametrize('use_fp16', [False, True])
-def test_duck_equals_the_reference_module_where_the_adapters_look(name, use_fp16, RefPrecond):
+def test_duck_equals_the_reference_module_where_the_adapters_look(name, use_fp16):
     import _ref_like
+    import _ref_structure
     import diff_sampler_amd.arch as arch
     from diff_sampler_amd.engine import spec_from_module
     kw = dict(arch.NAMED_CONFIGS[name], use_fp16=use_fp16)
     with torch.device('meta'):
-        real = RefPrecond(**kw)
         duck = _ref_like.EDMPrecond(**kw)
-    rs, ds = real.state_dict(), duck.state_dict()
+    real = _ref_structure.recorded(name, use_fp16)
+    rs = {k: (shape, dtype) for k, shape, dtype in _ref_structure.state_dict_entries(name, use_fp16)}
+    ds = duck.state_dict()
     assert list(ds) == list(rs)                                                  # keys AND order (buffers included)
-    assert all(tuple(ds[k].shape) == tuple(rs[k].shape) and ds[k].dtype == rs[k].dtype for k in rs)
+    assert all(tuple(ds[k].shape) == rs[k][0] and ds[k].dtype == rs[k][1] for k in rs)
     assert any('resample_filter' in k for k in rs) == any('resample_filter' in k for k in ds)
     for attr in ('img_resolution', 'img_channels', 'label_dim', 'use_fp16', 'sigma_min', 'sigma_max', 'sigma_data'):
         assert getattr(duck, attr) == getattr(real, attr), attr

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of engine.fuse_norm16 (GroupNorm apply + SiLU inside conv3x3_f16dma's LDS halo vs the ds_norm_act pass) on the two fp16 sampler lines,
 # alternating in one gpurun session; then the per-kernel-class table of both plans (bench.py's instrumented pass).
-Q="--steps 3 --warmup 1 --no-cpu-baseline --no-launch-modes --no-batch-sweep --no-other-configs"
+Q="--steps 3 --warmup 1 --full --no-cpu-baseline --no-launch-modes --no-batch-sweep --no-other-configs"
 for rep in 1 2; do
   for f in 0 1; do
     for cfg in imagenet64 sd15; do

@@ -6,7 +6,7 @@
 #     suite                     the whole GPU test suite                          -> pytest_all.txt
 #     tests:<pytest args>       e.g. "tests:tests/test_hip_fp16.py -k edm"        -> pytest_<n>.txt
 #     smoke                     __graft_entry__.smoke()                           -> smoke.txt
-#     bench[:<bench.py args>]   one bench line (args may name --config/--dtype)   -> bench_<n>.json
+#     bench[:<bench.py args>]   one full bench line (--full; args may name --config/--dtype) -> bench_<n>.json
 #     prof[:<bench.py args>]    rocprofv3 --kernel-trace --stats of bench.py      -> kernel_stats_<n>.txt + the line under rocprof
 #     pmc[:<bench.py args>]     separate FETCH_SIZE / WRITE_SIZE passes           -> pmc_hbm_<n>.json
 #     sq[:<bench.py args>]      SQ counter passes (MFMA busy, VALU / LDS instr.)  -> sq_counters_<n>.json
@@ -15,7 +15,7 @@ set -x
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 TAG=$1; shift
 O=gpurun_out/$TAG; mkdir -p $O
-QUICK="--no-cpu-baseline --no-launch-modes --no-batch-sweep --no-other-configs"
+QUICK="--full --no-cpu-baseline --no-launch-modes --no-batch-sweep --no-other-configs"      # --full: the instrumented pass and update rooflines stay in
 n=0
 for step in "$@"; do
   n=$((n+1)); kind=${step%%:*}; arg=""; [ "$kind" != "$step" ] && arg=${step#*:}
@@ -23,7 +23,7 @@ for step in "$@"; do
     suite) timeout 900 python -m pytest tests -x -q -m gpu > $O/pytest_all.txt 2>&1; tail -4 $O/pytest_all.txt ;;
     tests) eval "timeout 900 python -m pytest $arg -q -m gpu" > $O/pytest_$n.txt 2>&1; tail -15 $O/pytest_$n.txt ;;   # eval: -k 'a or b' stays one argument
     smoke) timeout 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -2 $O/smoke.txt ;;
-    bench) timeout 600 python bench.py $arg > $O/bench_$n.json 2> $O/bench_$n.err; tail -1 $O/bench_$n.json | cut -c1-300; tail -2 $O/bench_$n.err ;;
+    bench) timeout 600 python bench.py --full $arg > $O/bench_$n.json 2> $O/bench_$n.err; tail -1 $O/bench_$n.json | cut -c1-300; tail -2 $O/bench_$n.err ;;
     prof)  timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof_$n -o bench -- python bench.py $QUICK $arg > $O/bench_under_rocprof_$n.json 2> $O/prof_$n.err
            python tools/rocprof_summary.py stats $(find $O/prof_$n -name "*.db" | head -1) $O/kernel_stats_$n.txt > /dev/null 2>> $O/prof_$n.err
            head -12 $O/kernel_stats_$n.txt; tail -1 $O/bench_under_rocprof_$n.json | cut -c1-200 ;;
