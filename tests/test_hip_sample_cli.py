@@ -33,7 +33,8 @@ def test_sample_run_writes_reference_output_tree(tmp_path):
     assert sorted(imgs) == list(range(12)) + [1003]
     assert os.path.exists(a / '000000' / '000007.png') and os.path.exists(a / '001000' / '001003.png')
     assert all(v.shape == (16, 16, 3) and v.dtype == np.uint8 for v in imgs.values())
-    # a different batch size regroups the seeds but every seed owns its generator: identical images
+    # a different batch size regroups the seeds but every seed owns its generator: identical images (batches of 2 - 5 images route every
+    # launch identically: tests/test_batch_routing_cpu.py::test_cli_batch_sizes_of_the_byte_identity_test_route_every_row_identically)
     b = tmp_path / 'b'
     sample.run('tiny_song', max_batch_size=3, seeds='0-11,1003', outdir=str(b), solver='ipndm', num_steps=5, max_order=3, random_init=True)
     imgs_b = _read(str(b))
