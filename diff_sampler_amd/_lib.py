@@ -81,6 +81,11 @@ class ConvArgs(C.Structure):
                 ('update', vp)]          # const ds_update_args*: the solver update fused into the network head (ABI 3)
 
 
+class ConvRouteInfo(C.Structure):
+    # ds_conv_route (ABI 5): kernel id, split-K factor and the fp16-activation 3x3 kernel's column-tile widths (64-channel units)
+    _fields_ = [('kernel_id', C.c_int), ('splits', C.c_int), ('f16_groups', C.c_int), ('f16_widths', C.c_int * 4)]
+
+
 class GemmArgs(C.Structure):
     _fields_ = [('a', vp), ('lda', C.c_int), ('a_bstride', C.c_longlong), ('a_hstride', C.c_longlong),
                 ('b', vp), ('ldb', C.c_int), ('b_bstride', C.c_longlong), ('b_hstride', C.c_longlong),
@@ -163,6 +168,7 @@ _SIGNATURES = {
     'ds_error_string': (C.c_char_p, [C.c_int]),
     'ds_conv2d_nhwc': (C.c_int, [C.POINTER(ConvArgs), vp]),
     'ds_conv_kernel_id': (C.c_int, [C.POINTER(ConvArgs)]),
+    'ds_conv_route': (C.c_int, [C.POINTER(ConvArgs), C.POINTER(ConvRouteInfo)]),
     'ds_conv3x3_halo_supported': (C.c_int, [C.c_int, C.c_int]),
     'ds_conv_f16_supported': (C.c_int, [C.c_int] * 7),
     'ds_conv_f16dma_supported': (C.c_int, [C.c_int] * 6),
@@ -176,6 +182,7 @@ _SIGNATURES = {
     'ds_gn_finalize': (C.c_int, [C.POINTER(GnFinalizeArgs), vp]),
     'ds_softmax_rows': (C.c_int, [vp, vp, C.c_longlong, C.c_int, C.c_int, vp]),
     'ds_attention': (C.c_int, [C.POINTER(AttnArgs), vp]),
+    'ds_attention_variant': (C.c_int, [C.POINTER(AttnArgs)]),
     'ds_attention_supported': (C.c_int, [C.c_int]),
     'ds_attention_f16': (C.c_int, [C.POINTER(AttnArgs), vp]),
     'ds_attention_f16_supported': (C.c_int, [C.c_int]),
@@ -237,8 +244,8 @@ def load():
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype, fn.argtypes = res, args
-    if lib.ds_version() != 4:
-        raise DsError(f'{LIB_PATH} reports ABI version {lib.ds_version()}, this binding is written for 4: rebuild it (python diff_sampler_amd/build.py)')
+    if lib.ds_version() != 5:
+        raise DsError(f'{LIB_PATH} reports ABI version {lib.ds_version()}, this binding is written for 5: rebuild it (python diff_sampler_amd/build.py)')
     _lib = lib
     return lib
 

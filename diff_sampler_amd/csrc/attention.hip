@@ -231,16 +231,28 @@ __global__ void __launch_bounds__(256) flash_attn_kernel(const ds_attn_args a) {
     }
 }
 
+}  // namespace
+
+// Head sizes that are multiples of 128: the channel-split block (32 queries, four waves x d / 4 channels) while the query-split grid has fewer
+// than 1 024 waves (one per SIMD); ds_attn_args.variant: 1 = query split, 2 = channel split (tests, A/B runs).  Other head sizes: query split.
+extern "C" int ds_attention_variant(const ds_attn_args* a) {
+    if (!a) return DS_E_ARG;
+    if (a->d % 128 == 0) {
+        const long long waves = (long long)((a->sq + 127) / 128) * a->heads * a->batch * 4;
+        if (a->variant == 2 || (a->variant != 1 && waves < 1024)) return 2;
+    }
+    return 1;
+}
+
+namespace {
+
 template <int D>
 int launch(const ds_attn_args* a, hipStream_t stream) {
     constexpr int DB = (D > 32 && (D % 32) == 8) ? D / 32 : (D + 31) / 32;
     constexpr int KT = (D <= 64 && !(D > 32 && (D % 32) == 8)) ? 64 : 32;
     constexpr int bytes = (KT * (D + 4) + KT * (DB * 32 + 8) + 32 + 4 * 32 * 33) * (int)sizeof(float);
     if constexpr (D % 128 == 0) {
-        // the channel-split block (32 queries, four waves x D / 4 channels) while the query-split grid has fewer than 1 024 waves (one per SIMD);
-        // ds_attn_args.variant: 1 = query split, 2 = channel split (tests, A/B runs)
-        const long long waves = (long long)((a->sq + 127) / 128) * a->heads * a->batch * 4;
-        if (a->variant == 2 || (a->variant != 1 && waves < 1024)) {
+        if (ds_attention_variant(a) == 2) {
             constexpr int bytes_d = bytes + 4 * 16 * 64 * (int)sizeof(float);
             DS_ENSURE_DYN_LDS((&flash_attn_kernel<D, true>), bytes_d);
             dim3 grid((a->sq + 31) / 32, a->heads, a->batch);

@@ -544,7 +544,7 @@ static int tiling(const KParams& p, int nb0, int (*out)[3], int* cost, bool half
     return n;
 }
 
-int conv3x3_f16dma_plan(const KParams& p, int (*out)[3], bool half = false) {
+static int conv3x3_f16dma_plan(const KParams& p, int (*out)[3], bool half) {
 #ifdef DS_BUILD_EXPERIMENTS
     const int cap = half ? conv3x3_f16dmah_max_nb(p.W) : max_nb(p);
 #else
@@ -587,7 +587,7 @@ static int conv3x3_f16dma_splits(const KParams& p, int (*plan)[3], int* n) {
 
 // Which layers take the four-wave half-slab variant (two workgroups per CU, conv3x3_f16dmah.hip).  ds_conv_args.tune.f16dma_nw forces it
 // (4) or the eight-wave kernel (8); otherwise by layer class, from the A/B of profiles/r4_conv_f16dmah_ab.txt.
-bool conv3x3_f16dma_use_half(const KParams& p) {
+static bool conv3x3_f16dma_use_half(const KParams& p) {
 #ifdef DS_BUILD_EXPERIMENTS                                    // a recorded negative result: built with DS_BUILD_EXPERIMENTS=1 only, never a default
     return p.t_nw == 4 && conv3x3_f16dmah_applicable(p);
 #else
@@ -596,27 +596,29 @@ bool conv3x3_f16dma_use_half(const KParams& p) {
 #endif
 }
 
-int launch_conv3x3_f16dma(KParams& p, hipStream_t stream) {
-    int plan[4][3];
-#ifdef DS_BUILD_EXPERIMENTS
-    if (conv3x3_f16dma_use_half(p)) {
-        const int n = conv3x3_f16dma_plan(p, plan, true);
-        for (int i = 0; i < n; ++i) {
-            const int rc = launch_conv3x3_f16dmah_tiles(p, plan[i][2], plan[i][0], plan[i][1], stream);
-            if (rc) return rc;
-        }
-        return DS_OK;
-    }
-#endif
-    int n = conv3x3_f16dma_plan(p, plan);
-    p.splits = conv3x3_f16dma_splits(p, plan, &n);
-    for (int i = 0; i < n; ++i) {
+void conv3x3_f16dma_route(const KParams& p, ConvRoute& r) {
+    const bool half = conv3x3_f16dma_use_half(p);
+    r.kernel_id = half ? 2569 : (p.norm ? 2572 : 2566);
+    r.ngroups = conv3x3_f16dma_plan(p, r.groups, half);
+    r.splits = half ? 1 : conv3x3_f16dma_splits(p, r.groups, &r.ngroups);
+}
+
+int launch_conv3x3_f16dma(KParams& p, const ConvRoute& r, hipStream_t stream) {
+    for (int i = 0; i < r.ngroups; ++i) {
+        const int col = r.groups[i][0], tiles = r.groups[i][1], nb = r.groups[i][2];
         int rc;
+#ifdef DS_BUILD_EXPERIMENTS
+        if (r.kernel_id == 2569) {
+            rc = launch_conv3x3_f16dmah_tiles(p, nb, col, tiles, stream);
+            if (rc) return rc;
+            continue;
+        }
+#endif
         switch (p.W) {
-            case 8: rc = launch_w<8>(p, plan[i][2], plan[i][0], plan[i][1], stream); break;
-            case 16: rc = launch_w<16>(p, plan[i][2], plan[i][0], plan[i][1], stream); break;
-            case 32: rc = launch_w<32>(p, plan[i][2], plan[i][0], plan[i][1], stream); break;
-            default: rc = launch_w<64>(p, plan[i][2], plan[i][0], plan[i][1], stream); break;
+            case 8: rc = launch_w<8>(p, nb, col, tiles, stream); break;
+            case 16: rc = launch_w<16>(p, nb, col, tiles, stream); break;
+            case 32: rc = launch_w<32>(p, nb, col, tiles, stream); break;
+            default: rc = launch_w<64>(p, nb, col, tiles, stream); break;
         }
         if (rc) return rc;
     }

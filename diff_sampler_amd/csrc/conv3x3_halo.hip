@@ -590,25 +590,21 @@ bool half_wave_tiles(const KParams& p, int n_begin, int wide) {
     return geometry(p, 128, 4).ok;
 }
 
-// One layer = the full 128-column tiles (WN = 2) plus, when the channel count leaves 1..64 columns over, one launch of
-// 64-column tiles for them (WN = 1); the split-K partial planes are shared and reduced once.
+// One layer = the column ranges of its route (conv3x3_halo_route): 192- or 256-column tiles of the 8-wave kernel, the full 128-column tiles
+// (WN = 2) plus, when the channel count leaves 1..64 columns over, one launch of 64-column tiles for them (WN = 1); the split-K partial planes
+// are shared and reduced once.
 template <int WM, bool GLDS>
-int launch_wm(KParams& p, hipStream_t stream) {
-    // columns [0, n256): 256-column tiles of the 8-wave kernel where they apply (channel counts such as 384 = 256 + 128,
-    // 576 = 2 x 256 + 64, 320 = 256 + 64 get them for their first 256-multiples); the rest as before from column n256 on
-    int n256 = 0;
+int launch_wm(KParams& p, const ConvRoute& r, hipStream_t stream) {
+    const int n256 = r.n256, wide = r.n128;
     if constexpr (WM == 4 && GLDS) {
         const Geo g4 = geometry(p, 256, 2);
-        // round 3: channel counts that are multiples of 192 but not of 256 (ADM: 192 / 384 / 576) take 192-column tiles (64 x 96 per wave)
-        // for ALL their columns instead of 256 / 128-column tiles plus a 64-column tail; variant bit 13 switches it off (A/B runs)
-        if (wide192_tiles(p, g4)) {
+        if (r.cols192) {
             KParams q = p;
             const int rc = launch_one<4, true, 2, VAR_TILE_OPTS, 3>(q, g4, 0, p.N / 192, stream);
             if (rc) return rc;
             return DS_OK;
         }
-        if (wide_n_tiles(p, g4)) {
-            n256 = (p.N / 256) * 256;
+        if (n256) {
             KParams q = p;
             int rc;
 #ifdef DS_CONV_ABLATIONS
@@ -630,17 +626,13 @@ int launch_wm(KParams& p, hipStream_t stream) {
             }
         }
     }
-    const int nrest = p.N - n256;
-    const int full = nrest / BN, rem = nrest - full * BN;
-    const bool tail64 = rem > 0 && rem <= 64 && geometry(p, 64 * WM, 1).ok && use_tail64(p);
-    const int wide = tail64 ? full : (nrest + BN - 1) / BN;
     if (wide > 0) {
         const Geo g = geometry(p, 64 * WM, 2);
         int rc;
-        if (WM == 4 && GLDS && (p.t_variant & 31) == 3 && p.splits == 1 && n256 == 0 && conv3x3_halo2_applicable(p, wide, 0)) {
+        if (r.halo2) {
             KParams q = p;
             rc = launch_conv3x3_halo2(q, wide, 0, stream);
-        } else if (WM == 2 && GLDS && half_wave_tiles(p, n256, wide)) {
+        } else if (r.half_wave) {
             if constexpr (WM == 2 && GLDS) rc = launch_one<2, true, 4, 0, 1>(p, geometry(p, 128, 4), n256, wide, stream);
             else rc = DS_E_ARG;
         } else if constexpr (GLDS) {
@@ -672,8 +664,8 @@ int launch_wm(KParams& p, hipStream_t stream) {
         }
         if (rc) return rc;
     }
-    if (tail64) {
-        int rc = launch_one<WM, GLDS, 1>(p, geometry(p, 64 * WM, 1), n256 + full * BN, 1, stream);
+    if (r.tail64) {
+        int rc = launch_one<WM, GLDS, 1>(p, geometry(p, 64 * WM, 1), n256 + wide * BN, 1, stream);
         if (rc) return rc;
     }
     if (p.splits > 1) return launch_splitk_reduce(p, stream);
@@ -684,60 +676,47 @@ int launch_wm(KParams& p, hipStream_t stream) {
 
 bool conv3x3_halo_supported(const KParams& p) { return geometry(p, 128).ok; }
 
-
-// Tile shape and split-K factor of a layer: the cheaper of the two tile shapes under the cost model (igemm_common.h); the
-// 256-pixel tile gets a 3 % bonus where both fill the chip (weights shared by twice the pixels).
-struct HaloPlan { int tile, splits; };
-
-HaloPlan plan_halo(const KParams& p) {
+// Tile shape and split-K factor of a layer: the cheaper of the two tile shapes under the cost model (igemm_common.h); the 256-pixel tile
+// gets a 3 % bonus where both fill the chip (weights shared by twice the pixels).  Then the column ranges launch_wm runs on that tile:
+// 192-column tiles for every column of the ADM channel counts (multiples of 192 but not of 256: 192 / 384 / 576; round 3; variant bit 13:
+// off), else 256-column tiles for the first 256-multiples where they apply (384 = 256 + 128, 576 = 2 x 256 + 64, 320 = 256 + 64), the rest on
+// 128-column tiles and a 64-column tail.  Kernel ids: 0 = unsupported, 128 / 256 = M tile of the 128-column kernels, 2565 = the 256 x 256
+// tiles, 2568 = the 256 x 192 tiles, 1284 = 128-pixel tiles on 8 half-size waves, 2560 = the second-generation kernel (tune.variant 3).
+void conv3x3_halo_route(const KParams& layer, ConvRoute& r) {
+    KParams p = layer;
     const Geo g128 = geometry(p, 128), g256 = geometry(p, 256);
-    HaloPlan hp{0, 1};
-    if (!g128.ok) return hp;
+    r.kernel_id = 0; r.tile = 0; r.splits = 1;
+    if (!g128.ok) return;
     const int nt = (p.N + BN - 1) / BN;
     const int units = (p.c0 + p.c1 + p.ec0 + p.ec1) / BK;
     const long long mn = (long long)p.M * p.N, cap = p.part ? p.part_cap : 0;
     double c128 = 0.0, c256 = 0.0;
-    const int s128 = choose_splits((long long)((p.M + 127) / 128) * nt, false, units, 9, cap, mn, &c128, p.t_splits);
-    hp.tile = 128; hp.splits = s128;
+    r.tile = 128;
+    r.splits = choose_splits((long long)((p.M + 127) / 128) * nt, false, units, 9, cap, mn, &c128, p.t_splits);
     const long long blocks256 = (long long)((p.M + 255) / 256) * nt;
     // the 8-wave shape only where its tiles alone cover the 256 CUs twice (below that the model is optimistic about it)
     if (g256.ok && tile_override(p) != 128 && (blocks256 >= 512 || tile_override(p) == 256)) {
         const int s256 = choose_splits(blocks256, true, units, 9, cap, mn, &c256, p.t_splits);
-        if (tile_override(p) == 256 || 0.97 * c256 < c128) { hp.tile = 256; hp.splits = s256; }
+        if (tile_override(p) == 256 || 0.97 * c256 < c128) { r.tile = 256; r.splits = s256; }
     }
-    if (((p.t_variant & 31) == 6 || (p.t_variant & 16384)) && hp.tile == 256) hp.splits = 1;      // forced wide tiles (tests at small sizes): no split-K
-    return hp;
+    if (((p.t_variant & 31) == 6 || (p.t_variant & 16384)) && r.tile == 256) r.splits = 1;      // forced wide tiles (tests at small sizes): no split-K
+    p.splits = r.splits;
+    const int WM = r.tile / 64;
+    if (r.tile == 256 && use_glds(p)) {
+        if (wide192_tiles(p, g256)) { r.cols192 = true; r.kernel_id = 2568; return; }
+        if (wide_n_tiles(p, g256)) r.n256 = (p.N / 256) * 256;
+    }
+    const int nrest = p.N - r.n256, full = nrest / BN, rem = nrest - full * BN;
+    r.tail64 = rem > 0 && rem <= 64 && geometry(p, 64 * WM, 1).ok && use_tail64(p);
+    r.n128 = r.tail64 ? full : (nrest + BN - 1) / BN;
+    r.halo2 = WM == 4 && use_glds(p) && (p.t_variant & 31) == 3 && p.splits == 1 && r.n256 == 0 && conv3x3_halo2_applicable(p, r.n128, 0);
+    r.half_wave = WM == 2 && use_glds(p) && half_wave_tiles(p, r.n256, r.n128);
+    r.kernel_id = r.halo2 ? 2560 : r.n256 ? 2565 : r.half_wave ? 1284 : r.tile;
 }
 
-// 0 = unsupported, 128 / 256 = M tile of the 128-column kernels, 2565 = the 256 x 256-tile kernel, 1284 = 128-pixel tiles on 8 half-size waves
-int conv3x3_halo_choice(const KParams& p) {
-    const HaloPlan hp = plan_halo(p);
-    if (hp.tile == 128 && use_glds(p)) {
-        KParams q = p;
-        q.splits = hp.splits;
-        const int full = p.N / BN, rem = p.N - full * BN;
-        const bool tail64 = rem > 0 && rem <= 64 && geometry(p, 128, 1).ok && use_tail64(p);
-        if (half_wave_tiles(q, 0, tail64 ? full : (p.N + BN - 1) / BN)) return 1284;
-    }
-    if (hp.tile == 256 && use_glds(p)) {
-        KParams q = p;
-        q.splits = hp.splits;
-        if ((p.t_variant & 31) == 3 && hp.splits == 1) {          // tune.variant 3: the second-generation 256 x 128 kernel where it applies
-            const int full = p.N / BN, rem = p.N - full * BN;
-            const bool tail64 = rem > 0 && rem <= 64 && geometry(p, 256, 1).ok && use_tail64(p);
-            if (conv3x3_halo2_applicable(q, tail64 ? full : (p.N + BN - 1) / BN, 0)) return 2560;
-        }
-        if (wide192_tiles(q, geometry(p, 256, 2))) return 2568;        // 192-column tiles for every column (ADM channel counts)
-        if (wide_n_tiles(q, geometry(p, 256, 2))) return 2565;         // (its first N / 256 column tiles; a remainder stays on 128 / 64 columns)
-    }
-    return hp.tile;
-}
-
-int launch_conv3x3_halo(KParams& p, hipStream_t stream) {
-    const HaloPlan hp = plan_halo(p);
-    p.splits = hp.splits;
-    if (hp.tile == 256) return use_glds(p) ? launch_wm<4, true>(p, stream) : launch_wm<4, false>(p, stream);
-    return use_glds(p) ? launch_wm<2, true>(p, stream) : launch_wm<2, false>(p, stream);
+int launch_conv3x3_halo(KParams& p, const ConvRoute& r, hipStream_t stream) {
+    if (r.tile == 256) return use_glds(p) ? launch_wm<4, true>(p, r, stream) : launch_wm<4, false>(p, r, stream);
+    return use_glds(p) ? launch_wm<2, true>(p, r, stream) : launch_wm<2, false>(p, r, stream);
 }
 
 }  // namespace igemm

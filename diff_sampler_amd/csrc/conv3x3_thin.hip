@@ -158,6 +158,15 @@ bool conv3x3_thin_applicable(const KParams& p) {
 // the fused update is on when the call carries a struct with at least one output (ds_conv_args.update)
 static bool thin_update_on(const KParams& p) { return p.upd && (p.upd->x_out || p.upd->m_out); }
 
+int conv3x3_thin_check_update(const KParams& p) {
+    if (!thin_update_on(p)) return DS_OK;
+    const ds_update_args& u = *p.upd;                            // read at call time (include/ds_engine.h)
+    if (!p.out_planar || !u.xe || !u.xb || !u.raw || u.afs || u.f_ld != 0) return DS_E_ARG;
+    if (u.c != p.N || (long long)u.n * u.h * u.w != (long long)p.M || u.h * u.w != p.HW) return DS_E_ARG;
+    if (u.coefs && u.coef_rows != 1 && u.coef_rows != u.n) return DS_E_ARG;
+    return DS_OK;
+}
+
 int launch_conv3x3_thin(KParams& p, hipStream_t stream) {
     const int smem = 9 * p.c0 * 16;
     // pixels per workgroup: 256 (four waves x eight rounds of eight), fewer rounds while the launch would leave CUs without a workgroup -- at 8
@@ -168,12 +177,7 @@ int launch_conv3x3_thin(KParams& p, hipStream_t stream) {
     const unsigned blocks = (unsigned)((p.M + 32 * rounds - 1) / (32 * rounds));
     const bool upd = thin_update_on(p);
     ds_update_args u{};
-    if (upd) {
-        u = *p.upd;                                                // read at call time (include/ds_engine.h)
-        if (!p.out_planar || !u.xe || !u.xb || !u.raw || u.afs || u.f_ld != 0) return DS_E_ARG;
-        if (u.c != p.N || (long long)u.n * u.h * u.w != (long long)p.M || u.h * u.w != p.HW) return DS_E_ARG;
-        if (u.coefs && u.coef_rows != 1 && u.coef_rows != u.n) return DS_E_ARG;
-    }
+    if (upd) u = *p.upd;                                           // checked by route_conv (conv3x3_thin_check_update)
 #define DST_LAUNCH(NORM_, UPD_)                                                                                    \
     do {                                                                                                           \
         DS_ENSURE_DYN_LDS((&conv3x3_thin_kernel<NORM_, UPD_>), 160 * 1024);                                        \

@@ -200,19 +200,13 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const KParams p) {
     }
 }
 
+// MODE 0: split K by p.splits (route_conv's choice); MODE 1: batched GEMM, no split-K
 template <int MODE>
 int launch(KParams& p, int batch, hipStream_t stream) {
     DS_ENSURE_DYN_LDS((&igemm_f32_kernel<MODE>), SMEM_BYTES);
     p.mtiles = (p.M + BM - 1) / BM;
     p.ntiles = (p.N + BN - 1) / BN;
-    dim3 grid;
-    if (MODE == 0) {
-        p.splits = choose_splits((long long)p.mtiles * p.ntiles, false, p.K / BK, 1, p.part ? p.part_cap : 0, (long long)p.M * p.N, nullptr, p.t_splits);
-        grid = dim3(grid_1d(p.mtiles, p.ntiles), p.splits, 1);
-    } else {
-        p.splits = 1;
-        grid = dim3(p.mtiles, p.ntiles, batch);
-    }
+    const dim3 grid = MODE == 0 ? dim3(grid_1d(p.mtiles, p.ntiles), p.splits, 1) : dim3(p.mtiles, p.ntiles, batch);
     hipLaunchKernelGGL(igemm_f32_kernel<MODE>, grid, dim3(256), SMEM_BYTES, stream, p);
     DS_CHECK_LAUNCH();
     if (p.splits > 1) return launch_splitk_reduce(p, stream);
@@ -441,8 +435,13 @@ int launch_gemv_rows(const KParams& p, hipStream_t stream) {
 }
 }  // namespace igemm
 
-extern "C" int ds_conv2d_nhwc(const ds_conv_args* a, void* stream) {
-    (void)hipGetLastError();   // drop stale errors of unrelated runtime calls
+// The whole routing decision of a ds_conv2d_nhwc call, made once: validates the arguments (0 or the DS_E_* code the call returns), fills the
+// kernel argument `p` and decides the kernel, its split-K factor and its tiling (`r`).  Host logic only, no HIP runtime call: ds_conv_kernel_id
+// and ds_conv_route answer from it without a GPU.
+static int route_conv(const ds_conv_args* a, KParams& p, ConvRoute& r) {
+    p = KParams{};
+    r = ConvRoute{};
+    r.splits = 1;
     if (!a || !a->x0 || !a->wgt || !a->out) return DS_E_ARG;
     if (a->taps != 1 && a->taps != 9) return DS_E_ARG;
     if (a->c0 <= 0 || a->c0 % 32 || a->c1 < 0 || a->c1 % 32) return DS_E_SHAPE;
@@ -465,7 +464,6 @@ extern "C" int ds_conv2d_nhwc(const ds_conv_args* a, void* stream) {
     if (a->n <= 0 || a->h <= 0 || a->w <= 0 || a->cout <= 0) return DS_E_ARG;
     const long long M = (long long)a->n * a->h * a->w;
     if (M > 0x7fffffffLL - BM) return DS_E_SHAPE;
-    KParams p{};
     set_tune(p, a);
     p.a0 = a->x0; p.a1 = a->x1; p.c0 = a->c0; p.c1 = a->c1; p.lda0 = a->ld0; p.lda1 = a->ld1;
     p.H = a->h; p.W = a->w; p.HW = a->h * a->w; p.taps = a->taps;
@@ -514,87 +512,114 @@ extern "C" int ds_conv2d_nhwc(const ds_conv_args* a, void* stream) {
             // 1x1 / Linear with fp16 operands: weights [cout_pad][K] halfs in plain K order
             if (a->wgt_shift) return DS_E_ARG;
             p.ldb = p.K / 2;
-            p.part = nullptr; p.part_cap = 0; p.splits = 1;
+            p.part = nullptr; p.part_cap = 0;
 #ifdef DS_TIMELINE
             if ((p.t_ablate & 0x8000) && a->workspace) p.part = a->workspace;         // diagnostics build only: phase stamps (ds_common.h)
 #endif
             if (a->in_f16) {            // fp16 activations: both operands by LDS-DMA
                 p.out_f16 = a->out_f16 ? 1 : 0; p.res_f16 = a->res_f16 ? 1 : 0;
                 if (!gemm_f16dma_applicable(p)) return DS_E_SHAPE;
-                return launch_gemm_f16dma(p, (hipStream_t)stream);
+                r.kernel_id = 2567;
+                return DS_OK;
             }
             if (!gemm_f16_applicable(p)) return DS_E_SHAPE;
-            return launch_gemm_f16(p, (hipStream_t)stream);
+            r.kernel_id = 2564;
+            return DS_OK;
         }
         if (a->wgt_f16 == 1 && a->in_f16 && a->taps == 9 && stride == 2) {
             // the latent-diffusion Downsample on fp16 rows: the fp16-activation GEMM with a gathered A tile (weights packed like the stride-1 kernel's)
             if (a->wgt_shift) return DS_E_ARG;
             p.ldb = p.K / 2;
             p.out_f16 = a->out_f16 ? 1 : 0; p.res_f16 = 0;
-            p.part = nullptr; p.part_cap = 0; p.splits = 1;
+            p.part = nullptr; p.part_cap = 0;
             if (!gemm_f16dma_gather_applicable(p)) return DS_E_SHAPE;
-            return launch_gemm_f16dma(p, (hipStream_t)stream, true);
+            r.kernel_id = 2571;
+            return DS_OK;
         }
         if (a->taps != 9 || stride != 1 || (a->wgt_f16 != 1 && a->wgt_f16 != 2)) return DS_E_ARG;
         if (a->wgt_shift < 0 || a->wgt_shift > 24 || (a->wgt_f16 == 1 && a->wgt_shift)) return DS_E_ARG;
         if (a->in_f16) {
             p.ldb = p.K / 2;
             p.out_f16 = a->out_f16 ? 1 : 0; p.res_f16 = a->res_f16 ? 1 : 0;
-            p.splits = 1;                                   // p.part stays: under-filled layers split K (conv3x3_f16dma_splits)
             if (!conv3x3_f16dma_applicable(p)) return DS_E_SHAPE;
-            return launch_conv3x3_f16dma(p, (hipStream_t)stream);
+            conv3x3_f16dma_route(p, r);                     // p.part stays: under-filled layers split K (conv3x3_f16dma_splits)
+            p.splits = r.splits;
+            return DS_OK;
         }
-        const int wide = (p.N + BN - 1) / BN;
+        r.n128 = (p.N + BN - 1) / BN;
         // row pitch of the fp16 weight matrix in float units: fp16 = K halfs per row, split = 2 K halfs (hi and lo)
         p.ldb = a->wgt_f16 == 1 ? p.K / 2 : p.K;
         p.acc_scale = 1.0f / (float)(1 << a->wgt_shift);
-        p.part = nullptr; p.part_cap = 0; p.splits = 1;
-        if (!conv3x3_halo2_applicable(p, wide, a->wgt_f16)) return DS_E_SHAPE;
-        return launch_conv3x3_halo2(p, wide, a->wgt_f16, (hipStream_t)stream);
+        p.part = nullptr; p.part_cap = 0;
+        if (!conv3x3_halo2_applicable(p, r.n128, a->wgt_f16)) return DS_E_SHAPE;
+        r.kernel_id = a->wgt_f16 == 2 ? 2563 : 2562;
+        return DS_OK;
     }
     const bool generic = p.t_mode == 1;                    // tune.mode 1: the generic gather kernel (A/B runs, cross-checks)
     // network heads (cout <= 4): VALU kernel instead of a 64- / 128-column matrix tile (tune.mode != 0 keeps the matrix kernels: 8 = just that)
     p.upd = a->update;
     const bool want_update = a->update && (a->update->x_out || a->update->m_out);
-    if (p.t_mode == 0 && p.t_variant == 0 && conv3x3_thin_applicable(p)) return launch_conv3x3_thin(p, (hipStream_t)stream);
+    if (p.t_mode == 0 && p.t_variant == 0 && conv3x3_thin_applicable(p)) {
+        r.kernel_id = 2570;
+        return conv3x3_thin_check_update(p);
+    }
     if (want_update) return DS_E_ARG;                      // the fused solver update exists in the head kernel only: fail loudly, never skip it
-    if (!generic && stride == 1 && conv3x3_halo_supported(p)) return launch_conv3x3_halo(p, (hipStream_t)stream);
+    if (!generic && stride == 1 && conv3x3_halo_supported(p)) {
+        conv3x3_halo_route(p, r);
+        p.splits = r.splits;
+        return DS_OK;
+    }
     if (p.norm) return DS_E_SHAPE;           // fused input normalisation exists only in the halo kernel
-    if (!generic && p.t_mode != 6 && gemm_dma8_applicable(p)) return launch_gemm_dma8(p, (hipStream_t)stream);     // mode 6: no 8-wave DMA kernel
-    if (p.t_mode == 0 && p.t_variant == 0 && gemv_rows_applicable(p)) return launch_gemv_rows(p, (hipStream_t)stream);
-    return launch<0>(p, 1, (hipStream_t)stream);
+    if (!generic && p.t_mode != 6 && gemm_dma8_applicable(p)) r.kernel_id = 2561;      // mode 6: no 8-wave DMA kernel
+    else if (p.t_mode == 0 && p.t_variant == 0 && gemv_rows_applicable(p)) r.kernel_id = 2573;
+    else {
+        r.kernel_id = 0;
+        r.splits = p.splits = choose_splits((long long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN), false, p.K / BK, 1, p.part ? p.part_cap : 0,
+                                            (long long)p.M * p.N, nullptr, p.t_splits);
+    }
+    return DS_OK;
+}
+
+extern "C" int ds_conv2d_nhwc(const ds_conv_args* a, void* stream) {
+    (void)hipGetLastError();   // drop stale errors of unrelated runtime calls
+    KParams p;
+    ConvRoute r;
+    const int rc = route_conv(a, p, r);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    switch (r.kernel_id) {
+        case 0: return launch<0>(p, 1, s);
+        case 2561: return launch_gemm_dma8(p, s);
+        case 2562: case 2563: return launch_conv3x3_halo2(p, r.n128, a->wgt_f16, s);
+        case 2564: return launch_gemm_f16(p, s);
+        case 2566: case 2569: case 2572: return launch_conv3x3_f16dma(p, r, s);
+        case 2567: return launch_gemm_f16dma(p, s);
+        case 2570: return launch_conv3x3_thin(p, s);
+        case 2571: return launch_gemm_f16dma(p, s, true);
+        case 2573: return launch_gemv_rows(p, s);
+        default: return launch_conv3x3_halo(p, r, s);      // 128 / 256 / 1284 / 2560 / 2565 / 2568
+    }
 }
 
 extern "C" int ds_conv_kernel_id(const ds_conv_args* a) {
-    if (!a) return DS_E_ARG;
-    KParams p{};
-    set_tune(p, a);
-    p.taps = a->taps; p.H = a->h; p.W = a->w; p.HW = a->h * a->w; p.M = a->n * a->h * a->w; p.N = a->cout;
-    p.c0 = a->c0; p.c1 = a->c1; p.ec0 = a->ec0; p.ec1 = a->ec1;
-    if (a->workspace && a->workspace_floats > 0 && ds_aligned16(a->workspace) && a->act != DS_ACT_GEGLU) {
-        p.part = a->workspace; p.part_cap = a->workspace_floats; p.vec_part = (p.N & 3) ? 0 : 1;
-    }
-    // the epilogue-related fields the tile choice looks at, as ds_conv2d_nhwc sets them
-    p.out = a->out; p.ldo = a->out_ld; p.colbias = a->bias; p.cbias = a->cbias; p.cbias_ld = a->cbias_ld; p.res = a->res; p.res_ld = a->res_ld;
-    p.act = a->act; p.out_planar = a->out_nchw ? 1 : 0;
-    p.vec_ok = (vec_epilogue_ok(p) && !a->out_nchw) ? 1 : 0;
-    p.stride = a->stride ? a->stride : 1; p.K = a->taps * (a->c0 + a->c1) + a->ec0 + a->ec1; p.norm = a->norm_coefs;
-    p.nrows_b = ((a->cout + BN - 1) / BN) * BN;                                     // weights are row-padded, as in ds_conv2d_nhwc
-    if (a->wgt_f16 == 1 && a->in_f16 && a->taps == 9 && p.stride == 2) return 2571;
-    if (a->wgt_f16 == 1 && a->in_f16) return a->taps == 1 ? 2567 : (conv3x3_f16dma_use_half(p) ? 2569 : (a->norm_coefs ? 2572 : 2566));
-    if (a->wgt_f16) return a->wgt_f16 == 2 ? 2563 : (a->taps == 1 ? 2564 : 2562);
-    if (p.t_mode == 1) return 0;
-    if (p.t_mode == 0 && p.t_variant == 0 && !a->res && !a->cbias && !a->stats_out) {
-        KParams q = p; q.HW = p.HW; q.res = nullptr; q.cbias = nullptr; q.stats = nullptr; q.splits = 1; q.norm_act = a->norm_act;
-        if (conv3x3_thin_applicable(q)) return 2570;
-    }
-    if (a->taps != 9 || a->stride > 1) {
-        if (p.t_mode != 6 && gemm_dma8_applicable(p)) return 2561;
-        KParams q = p; q.a0 = a->x0; q.lda0 = a->ld0; q.b = a->wgt; q.ldb = p.K; q.scale = a->out_scale; q.out_f16 = 0; q.splits = 1;
-        q.rowbias = nullptr; q.stats = a->stats_out;
-        return (p.t_mode == 0 && p.t_variant == 0 && gemv_rows_applicable(q)) ? 2573 : 0;
-    }
-    return conv3x3_halo_choice(p);
+    KParams p;
+    ConvRoute r;
+    const int rc = route_conv(a, p, r);
+    return rc ? rc : r.kernel_id;
+}
+
+extern "C" int ds_conv_route(const ds_conv_args* a, ds_conv_route_info* info) {
+    if (!info) return DS_E_ARG;
+    KParams p;
+    ConvRoute r;
+    const int rc = route_conv(a, p, r);
+    if (rc) return rc;
+    *info = ds_conv_route_info{};
+    info->kernel_id = r.kernel_id;
+    info->splits = r.splits;
+    info->f16_groups = r.ngroups;
+    for (int i = 0; i < r.ngroups; ++i) info->f16_widths[i] = r.groups[i][2];
+    return DS_OK;
 }
 
 static int reduced_supported(int mode, int n, int h, int w, int c0, int c1, int ec0, int ec1) {

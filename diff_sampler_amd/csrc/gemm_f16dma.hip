@@ -225,7 +225,7 @@ int launch_nb(KParams p, int n_begin, int ntiles, hipStream_t stream) {
 bool gemm_f16dma_applicable(const KParams& p) {
     if (p.taps != 1 || p.stride > 1 || p.norm != nullptr || p.ec0 || p.ec1 || p.c1) return false;
     if (p.K < 64 || p.K % 64 || p.N % 64 || !p.vec_ok || p.nrows_b < p.N || p.M < 1) return false;
-    return true;
+    return p.act != DS_ACT_GEGLU || p.N % 128 == 0;
 }
 
 // The strided 3x3 convolution on fp16 rows (GATHER): H, W = OUTPUT size, IH = 2 H, IW = 2 W; bias / per-image bias / column sums / fp16 or fp32
@@ -244,7 +244,6 @@ bool gemm_f16dma_gather_applicable(const KParams& p) {
 // profiles/r3_gemm_f16dma_epilogue.txt); ds_conv_args.tune.f16dma_nw (benchmarks) forces 4 or 8.
 int launch_gemm_f16dma(KParams& p, hipStream_t stream, bool gather) {
     const bool geglu = p.act == DS_ACT_GEGLU;
-    if (geglu && (p.N % 128)) return DS_E_SHAPE;
     int nw = (p.K <= 2560 && p.N <= 1280) ? 4 : 8;
     if (p.t_nw == 4 || p.t_nw == 8) nw = p.t_nw;
     if (gather) nw = 8;                                        // the gather is instantiated for the eight-wave tile only

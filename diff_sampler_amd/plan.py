@@ -31,8 +31,8 @@ SPLITK_WORKSPACE_FLOATS = 64 << 20      # 256 MiB per plan
 # GroupNorm column sums of the store-from-accumulators epilogue are taken per 64-row block whatever the width; the STAGED epilogue's
 # column sums follow its pass geometry (32- vs 64-column blocks), so layers that leave column sums through it keep the cost-model tile.
 # Results are therefore bit-identical with or without the measurement (tests/test_hip_fp16.py).  The split-K factor, which does
-# change the order of the fp32 sums, stays rule-based (conv3x3_f16dma_splits: a function of the layer alone).  DS_AUTOTUNE=0 in the
-# environment, or Builder(autotune=False), switches it off; launches whose tune words a test / benchmark has set are left alone; nothing
+# change the order of the fp32 sums, stays rule-based (conv3x3_f16dma_splits: a function of the layer alone; ds_conv_route reports it).
+# DS_AUTOTUNE=0 in the environment, or Builder(autotune=False), switches it off; launches whose tune words a test / benchmark has set are left alone; nothing
 # is measured during a stream capture.  Measured gain on whole sampler calls (session r7a, alternating in one process): SD-1.5 fp16
 # +1.5 %, ImageNet-64 fp16 +0.6 %.
 AUTOTUNE = os.environ.get('DS_AUTOTUNE', '1') != '0'

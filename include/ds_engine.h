@@ -47,7 +47,8 @@ extern "C" {
 #define DS_RESAMPLE_DOWN 1  /* 2x2 box filter, stride 2  (networks_edm.py:77 with resample_filter [1,1]) */
 #define DS_RESAMPLE_UP 2    /* nearest neighbour x2      (networks_edm.py:75 with resample_filter [1,1]) */
 
-DS_API int ds_version(void);      /* ABI version; a host must check it before passing argument structs.  4 (round 6): ds_norm_args.stats0 / stats1 / tune_variant and ds_attn_args.variant
+DS_API int ds_version(void);      /* ABI version; a host must check it before passing argument structs.  5: ds_conv_route / ds_attention_variant added (the
+                               * library's routing decisions as queries; ds_conv_kernel_id answers negative codes for rejected arguments).  4 (round 6): ds_norm_args.stats0 / stats1 / tune_variant and ds_attn_args.variant
                                * appended (the pass that computes its own GroupNorm statistics; struct size changed).  3 (round 5): ds_conv_args.update appended (the head-fused
                                * solver update; struct size changed), ds_build_experiments() added, ds_conv_args.norm_coefs also accepted with in_f16.
                                * 2 (round 4): ds_conv_args.tune / ds_update_args.variant appended (struct sizes changed), ds_fid_moments added, the
@@ -199,9 +200,25 @@ DS_API int ds_conv2d_nhwc(const ds_conv_args* a, void* stream);
  * LDS-halo kernel with 128-pixel tiles on eight waves of 64 x 32 (layers with at most one tile per CU), 2570 = the thin-output 3x3 kernel
  * of the network heads (conv3x3_thin_kernel: cout <= 4, one fp32 source, no residual / per-image bias / statistics), 2571 = the stride-2
  * 3x3 convolution on fp16 rows (gemm_f16dma_kernel<.., GATHER>), 2573 (round 6) = the 1x1 / Linear on at most four rows (gemv_rows_kernel: the
- * embedding path's one-row projections; one fp32 source, bias / scale / SiLU only, cout >= 64; tune.mode != 0 keeps the matrix kernels).  Used by
- * bench.py to attribute time per kernel. */
+ * embedding path's one-row projections; one fp32 source, bias / scale / SiLU only, cout >= 64; tune.mode != 0 keeps the matrix kernels), 2566 / 2572 =
+ * the fp16-activation 3x3 kernel without / with the fused input normalisation (conv3x3_f16dma_kernel), 2567 = the fp16-activation 1x1 / Linear
+ * (gemm_f16dma_kernel), 2568 = LDS-halo kernel <4> with 256-pixel x 192-channel tiles, 2569 = the four-wave half-slab fp16-activation 3x3 kernel
+ * (tune.f16dma_nw 4, DS_BUILD_EXPERIMENTS builds).  ABI 5: the answer comes from the same routing function as the launch, so for arguments
+ * ds_conv2d_nhwc rejects it returns the same negative DS_E_* code (until ABI 4 it answered with a kernel id regardless).  Used by bench.py
+ * to attribute time per kernel. */
 DS_API int ds_conv_kernel_id(const ds_conv_args* a);
+
+/* ABI 5: the whole routing decision of a ds_conv2d_nhwc call, without a GPU (host logic only): DS_OK and `info` filled, or the negative DS_E_*
+ * code the call would return (info untouched).  f16_groups / f16_widths: the column tiling of the fp16-activation 3x3 kernels (kernel ids
+ * 2566 / 2569 / 2572) -- groups of equal tiles, widest first, each width in 64-channel units (320 channels = 3 + 2); 0 groups on every other
+ * kernel. */
+typedef struct ds_conv_route_info {
+    int kernel_id;       /* = ds_conv_kernel_id */
+    int splits;          /* split-K factor: partial planes in ds_conv_args.workspace, reduced by a second launch (1 = none) */
+    int f16_groups;
+    int f16_widths[4];
+} ds_conv_route_info;
+DS_API int ds_conv_route(const ds_conv_args* a, ds_conv_route_info* info);
 
 /* 1 if a 3x3 convolution on h x w images runs on the LDS-halo kernel (needed for norm_coefs), else 0. */
 DS_API int ds_conv3x3_halo_supported(int h, int w);
@@ -356,6 +373,9 @@ typedef struct ds_attn_args {
 
 DS_API int ds_attention(const ds_attn_args* a, void* stream);
 DS_API int ds_attention_supported(int d);
+/* ABI 5: which work split ds_attention runs for `a` (host logic only): 1 = query split (128 queries per block), 2 = channel split (32 queries,
+ * four waves x d / 4 channels; head sizes that are multiples of 128 -- see ds_attn_args.variant); DS_E_ARG for a NULL pointer. */
+DS_API int ds_attention_variant(const ds_attn_args* a);
 
 /* The same operation with fp16 operands on the fp16 matrix pipe -- the attention of the reference's fp16 / autocast mode
  * (networks_edm.py:98-110 with use_fp16; ldm/modules/attention.py:168-194 under autocast, sample.py:296): q / k / v / out stay fp32

@@ -85,108 +85,3 @@ def ldm_stored_prefixes(plan):
             else:
                 raise KeyError(op.name)
     return out
-
-
-# ---- host mirrors of the tile / split-K rules of csrc/conv3x3_f16dma.hip (tiling, conv3x3_f16dma_plan, conv3x3_f16dma_splits): what a
-# ---- stride-1 fp16-activation 3x3 launch `a` (ds_conv_args) will run as, so that a parity test can assert WHICH tilings it exercised ----
-def _f16dma_tiling(M, N, nb0):
-    mtiles = -(-M // 256)                 # whole and partial 256-pixel tiles (8x8 images: one to three in the last, conv3x3_f16dma.hip tiling)
-    out, col, cost = [], 0, 0
-    for w in range(nb0, 0, -1):
-        if col >= N:
-            break
-        t = (N - col) // (64 * w)
-        if t > 0:
-            out.append((col, t, w))
-            col += t * 64 * w
-            cost += -(-mtiles * t // 256) * (1 + w)
-    return out, cost
-
-
-def f16dma_splits(a):
-    """Split-K factor of the launch (1 = none): conv3x3_f16dma_splits."""
-    M, N = a.n * a.h * a.w, a.cout
-    if not a.workspace or a.tune.splits == 1:
-        return 1
-    wide, _ = _f16dma_tiling(M, N, 4 if (a.w in (16, 32) and not a.norm_coefs) else 3)
-    tiles = sum(-(-M // 256) * t for _, t, _ in wide)
-    s = a.tune.splits if a.tune.splits > 1 else (256 // tiles if tiles <= 128 else 1)
-    kt_all = ((a.c0 + a.c1) // 64) * 9 + (a.ec0 + a.ec1) // 64
-    s = min(s, 16, kt_all // 18, a.workspace_floats // (M * N))
-    return s if s >= 2 else 1
-
-
-def f16dma_tile_widths(a):
-    """Column-tile widths (in 64-channel units) the launch uses when no width is forced or measured (tune.f16dma_nb == 0): the widest tiling
-    for a split layer, else the cost model's (conv3x3_f16dma_plan)."""
-    M, N = a.n * a.h * a.w, a.cout
-    cap = 4 if (a.w in (16, 32) and not a.norm_coefs) else 3          # max_nb: no 256-column tile with the fused input normalisation
-    if a.tune.f16dma_nb > 0:
-        return [w for _, _, w in _f16dma_tiling(M, N, min(a.tune.f16dma_nb, cap))[0]]
-    if f16dma_splits(a) > 1:
-        return [w for _, _, w in _f16dma_tiling(M, N, cap)[0]]
-    best = None
-    for nb in range(cap, 0, -1):
-        til, cost = _f16dma_tiling(M, N, nb)
-        if best is None or cost < best[0] or (cost == best[0] and len(til) < best[1]):
-            best = (cost, len(til), til)
-    return [w for _, _, w in best[2]]
-
-
-# ---- host mirror of the fp32 attention launcher's variant rule (csrc/attention.hip, launch<D>, :242-243): for head sizes that are a multiple
-# ---- of 128 the channel-split block runs while the query-split grid has fewer than 1 024 waves (one per SIMD); ds_attn_args.variant 1 / 2 forces
-def attention_variant(a):
-    """'channel_split' or 'query_split': which flash_attn_kernel<D> instantiation an fp32 ds_attention launch `a` (ds_attn_args) runs."""
-    if a.d % 128 == 0:
-        waves = ((a.sq + 127) // 128) * a.heads * a.batch * 4
-        if a.variant == 2 or (a.variant != 1 and waves < 1024):
-            return 'channel_split'
-    return 'query_split'
-
-
-# ---- host mirror of the fp32 split-K rule (csrc/igemm_common.h cu_time_us / layer_cost_us / choose_splits, applied as csrc/conv3x3_halo.hip
-# ---- plan_halo :700-706 and csrc/gemm_conv.hip launch<0> :210 apply it): the split factor of an fp32-activation convolution launch ----
-def _cu_time_us(n, big_tile):
-    return 3.3 * n if big_tile else 3.4 * (n // 2) + 2.1 * (n & 1)
-
-
-def _layer_cost_us(blocks, big_tile, ktiles, s, mn):
-    n = (blocks * s + 255) // 256
-    t = ((ktiles + s - 1) // s) * _cu_time_us(n, big_tile)
-    if s > 1:
-        t += 8.0 + s * mn * 8.0 / 2.0e6
-    return t
-
-
-def _choose_splits(blocks, big_tile, units, tiles_per_unit, cap, mn, forced=0):
-    ktiles = units * tiles_per_unit
-    best_c, best = _layer_cost_us(blocks, big_tile, ktiles, 1, mn), 1
-    smax = min(units, 16)
-    if mn > 0 and smax * mn > cap:
-        smax = cap // mn
-    if units >= 4 and mn > 0:
-        if forced > 0:
-            best = max(min(forced, smax), 1)
-        else:
-            for s in range(2, smax + 1):
-                c = _layer_cost_us(blocks, big_tile, ((units + s - 1) // s) * tiles_per_unit * s, s, mn)
-                if c < 0.97 * best_c:
-                    best_c, best = c, s
-    return best
-
-
-def fp32_splits(a, kernel_id):
-    """Split-K factor of an fp32-activation ds_conv2d_nhwc launch `a` whose ds_conv_kernel_id is `kernel_id`: the LDS-halo kernel's (128-pixel
-    tiles: ids 128 / 1284; 256-pixel tiles: 256 / 2565 / 2568) and the generic kernel's (id 0); 1 on every other kernel (gemm_dma8, gemv_rows,
-    the thin head kernel, the fp16-operand / fp16x3 kernels never split K).  Plans leave tune.variant at 0 (no forced wide tiles)."""
-    M, N = a.n * a.h * a.w, a.cout
-    cap = a.workspace_floats if (a.workspace and a.workspace_floats > 0 and a.act != _lib.DS_ACT_GEGLU) else 0
-    forced = a.tune.splits if a.tune.splits > 0 else 0
-    if kernel_id in (128, 1284, 256, 2565, 2568):
-        tile = 128 if kernel_id in (128, 1284) else 256
-        units = (a.c0 + a.c1 + a.ec0 + a.ec1) // 32
-        return _choose_splits(-(-M // tile) * -(-N // 128), tile == 256, units, 9, cap, M * N, forced)
-    if kernel_id == 0:
-        K = a.taps * (a.c0 + a.c1) + a.ec0 + a.ec1
-        return _choose_splits(-(-M // 128) * -(-N // 128), False, K // 32, 1, cap, M * N, forced)
-    return 1

@@ -4,10 +4,9 @@ Plans are host logic and the launchers' routing rules use compile-time constants
 every launch of an evaluation at batch B takes.  `signature(plan)` reduces a plan to what the batch can switch:
 
   * the C entry point of every launch;
-  * ds_conv2d_nhwc: ds_conv_kernel_id (tile shape / kernel family; 2573 = the <= 4-row projection kernel) and the split-K factor -- host
-    mirrors in tests/_f16_names.py: fp32_splits (choose_splits as the fp32 halo kernel's plan_halo and the generic kernel apply it) and, on the
-    stride-1 fp16-activation 3x3 launches, f16dma_splits together with the column-tile widths;
-  * ds_attention (fp32): channel-split or query-split block (tests/_f16_names.attention_variant);
+  * ds_conv2d_nhwc: the library's own routing decision (ds_conv_route): kernel id (tile shape / kernel family; 2573 = the <= 4-row projection
+    kernel) and split-K factor, reported as f16_splits together with the column-tile widths on the stride-1 fp16-activation 3x3 launches;
+  * ds_attention (fp32): channel-split or query-split block (ds_attention_variant);
   * ds_gn_stats: whether the launch carries the small-batch `partial` / `counters` scratch (several workgroups per image).
 
 A *boundary* of a configuration is a batch b whose signature differs from that of b - 1.  SWEEP holds, per configuration, the batches
@@ -16,7 +15,6 @@ and every batch size a real sampling run hands the engine (sample.shard_seeds)."
 import ctypes as C
 
 from diff_sampler_amd import _lib
-from _f16_names import attention_variant, f16dma_splits, f16dma_tile_widths, fp32_splits
 
 # configuration -> (network, engine kind, mode keywords, batch range scanned on the CPU, golden-pinned bench batch).  Batches count sampler
 # images (SD-1.5: latents; the U-Net sees twice as many under classifier-free guidance).
@@ -101,6 +99,14 @@ def plan_of(engine, config, B, emb_rows):
     return engine.plan(B, emb_rows)
 
 
+def conv_route(a):
+    """ds_conv_route of a launch's ds_conv_args (kernel_id, splits, f16_groups, f16_widths)."""
+    r = _lib.ConvRouteInfo()
+    rc = _lib.load().ds_conv_route(C.byref(a), C.byref(r))
+    assert rc == 0, rc
+    return r
+
+
 def signature(plan):
     """[(launch name, entry point, routing fields...)] of every launch of the plan (and of its per-context sub-plan, if any)."""
     lib = _lib.load()
@@ -111,14 +117,14 @@ def signature(plan):
         sig = (op.name, fn.__name__)
         if fn is lib.ds_conv2d_nhwc:
             a = op.keep[0]
-            kid = lib.ds_conv_kernel_id(C.byref(a))
-            sig += (('kernel', kid),)
+            r = conv_route(a)
+            sig += (('kernel', r.kernel_id),)
             if a.in_f16 and a.taps == 9 and (a.stride or 1) == 1:
-                sig += (('f16_splits', f16dma_splits(a)), ('f16_widths', tuple(f16dma_tile_widths(a))))
+                sig += (('f16_splits', r.splits), ('f16_widths', tuple(r.f16_widths[:r.f16_groups])))
             else:
-                sig += (('splits', fp32_splits(a, kid)),)
+                sig += (('splits', r.splits),)
         elif fn is lib.ds_attention:
-            sig += (('attention', attention_variant(op.keep[0])),)
+            sig += (('attention', 'channel_split' if lib.ds_attention_variant(C.byref(op.keep[0])) == 2 else 'query_split'),)
         elif fn is lib.ds_gn_stats:
             sig += (('gn_partial', bool(op.keep[0].partial)),)
         out.append(sig)

@@ -271,11 +271,11 @@ def test_config5_sd15_at_the_benchmark_batch_b16(mode, dev):
         assert errs[i] < min(max(1.5 * noise[i], 2e-3), 2e-2), (i, errs[i], noise[i])
         assert errs16[i] < max(2.0 * noise[i], 2e-3), (i, errs16[i], noise[i])      # two independent fp16 noises (expected ~1.4 x)
     assert e_eps < 2.5e-3, e_eps
-    # what only this batch exercises (host mirrors of the launcher's rules, tests/_f16_names.py): split-K on the 8x8 stage, 256-column tiles
-    from _f16_names import f16dma_splits, f16dma_tile_widths
-    s1 = [a for a in c33 if a.in_f16 and (a.stride or 1) == 1]
-    assert sum(1 for a in s1 if a.h == 8 and f16dma_splits(a) > 1) >= 10, [(a.h, a.c0, a.cout, f16dma_splits(a)) for a in s1]
-    assert sum(1 for a in s1 if 4 in f16dma_tile_widths(a)) >= 10
+    # what only this batch exercises (the launcher's own routing, ds_conv_route): split-K on the 8x8 stage, 256-column tiles
+    from _routing import conv_route
+    s1 = [(a, conv_route(a)) for a in c33 if a.in_f16 and (a.stride or 1) == 1]
+    assert sum(1 for a, r in s1 if a.h == 8 and r.splits > 1) >= 10, [(a.h, a.c0, a.cout, r.splits) for a, r in s1]
+    assert sum(1 for a, r in s1 if 4 in r.f16_widths[:r.f16_groups]) >= 10
 
 
 # ---- the OTHER benchmarked configurations at THEIR bench batches (bench.py --config imagenet64 --batch 64 / --config ffhq --batch 128),
