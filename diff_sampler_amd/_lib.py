@@ -23,7 +23,7 @@ DS_GN_MAX_CHUNKS = 32
 class ConvTune(C.Structure):
     """ds_conv_tune: per-call kernel selection overrides (include/ds_engine.h); all zero = the library's own choice."""
     _fields_ = [('mode', C.c_int), ('variant', C.c_int), ('splits', C.c_int), ('f16dma_nb', C.c_int), ('f16dma_nw', C.c_int),
-                ('ablate', C.c_int)]
+                ('ablate', C.c_int), ('invariant', C.c_int)]        # invariant: ABI 6 (bit 0: batch-invariant route, bit 1: embedding projection)
 
 
 _tune_state = threading.local()
@@ -244,8 +244,8 @@ def load():
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype, fn.argtypes = res, args
-    if lib.ds_version() != 5:
-        raise DsError(f'{LIB_PATH} reports ABI version {lib.ds_version()}, this binding is written for 5: rebuild it (python diff_sampler_amd/build.py)')
+    if lib.ds_version() != 6:
+        raise DsError(f'{LIB_PATH} reports ABI version {lib.ds_version()}, this binding is written for 6: rebuild it (python diff_sampler_amd/build.py)')
     _lib = lib
     return lib
 

@@ -383,20 +383,26 @@ static void set_tune(KParams& p, const ds_conv_args* a) {
 // weights (tools/time_plan_ops.py, sessions r10a / r10j).  Here a wave owns an output column: 64 lanes x 16 bytes of its weight row per step,
 // the <= 4 input rows from cache, a cross-lane sum at the end -- the weights are read once at streaming rate.  fp32 products and sums (another
 // order than the matrix kernel's: fp32 rounding apart).  Kernel id 2573; ds_conv_tune.mode != 0 keeps the matrix kernels.
+// ABI 6: blockIdx.y = group of four rows, so the batch-invariant route (ds_conv_tune.invariant bit 1) runs the embedding projections here at
+// any row count.  Each output is still one lane-strided fmaf chain per lane and the same cross-lane sum, whatever the row count or the row's
+// place in its group: every row of every batch gets the bits the one-row launch gives it.
 namespace igemm {
 namespace {
 __global__ void __launch_bounds__(256) gemv_rows_kernel(const KParams p) {
     const int lane = threadIdx.x & 63;
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= p.N) return;
+    const int m0 = blockIdx.y * 4;
+    const int rows = min(p.M - m0, 4);                       // rows of this group (the grid never has an empty one)
+    const float* a = p.a0 + (size_t)m0 * p.lda0;
     const float* w = p.b + (size_t)n * p.ldb;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int k = lane * 4; k < p.K; k += 256) {
         const f32x4 wv = *reinterpret_cast<const f32x4*>(w + k);
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            if (m < p.M) {
-                const f32x4 xv = *reinterpret_cast<const f32x4*>(p.a0 + (size_t)m * p.lda0 + k);
+            if (m < rows) {
+                const f32x4 xv = *reinterpret_cast<const f32x4*>(a + (size_t)m * p.lda0 + k);
                 acc[m] = __builtin_fmaf(xv[0], wv[0], __builtin_fmaf(xv[1], wv[1], __builtin_fmaf(xv[2], wv[2], __builtin_fmaf(xv[3], wv[3], acc[m]))));
             }
         }
@@ -410,18 +416,20 @@ __global__ void __launch_bounds__(256) gemv_rows_kernel(const KParams p) {
         const float bias = p.colbias ? p.colbias[n] : 0.f;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            if (m < p.M) {
+            if (m < rows) {
                 float v = (acc[m] + bias) * p.scale;
                 if (p.act == DS_ACT_SILU) v = ds_silu(v);
-                p.out[(size_t)m * p.ldo + n] = v;
+                p.out[(size_t)(m0 + m) * p.ldo + n] = v;
             }
         }
     }
 }
 }  // namespace
 
-bool gemv_rows_applicable(const KParams& p) {
-    if (p.taps != 1 || p.stride != 1 || p.M < 1 || p.M > 4 || p.c1 || p.ec0 || p.ec1 || p.norm) return false;
+// any_rows: the batch-invariant route of an embedding projection (every row count; the default route keeps the <= 4-row rule)
+bool gemv_rows_applicable(const KParams& p, bool any_rows) {
+    if (p.taps != 1 || p.stride != 1 || p.M < 1 || (!any_rows && p.M > 4) || p.c1 || p.ec0 || p.ec1 || p.norm) return false;
+    if ((long long)(p.M + 3) / 4 > 65535) return false;       // grid y: groups of four rows
     if (p.res || p.cbias || p.rowbias || p.stats || p.out_planar || p.out_f16 || p.splits > 1) return false;
     if (p.act != DS_ACT_NONE && p.act != DS_ACT_SILU) return false;
     if ((p.K & 3) || (p.lda0 & 3) || (p.ldb & 3) || !ds_aligned16(p.a0) || !ds_aligned16(p.b) || p.nrows_b < p.N) return false;
@@ -429,7 +437,7 @@ bool gemv_rows_applicable(const KParams& p) {
 }
 
 int launch_gemv_rows(const KParams& p, hipStream_t stream) {
-    hipLaunchKernelGGL(gemv_rows_kernel, dim3((unsigned)((p.N + 3) / 4)), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(gemv_rows_kernel, dim3((unsigned)((p.N + 3) / 4), (unsigned)((p.M + 3) / 4)), dim3(256), 0, stream, p);
     DS_CHECK_LAUNCH();
     return DS_OK;
 }
@@ -497,6 +505,14 @@ static int route_conv(const ds_conv_args* a, KParams& p, ConvRoute& r) {
         p.out_planar = 1; p.vec_ok = 0;
     }
     p.splits = 1; p.part = nullptr; p.part_cap = 0; p.vec_part = 0;
+    // ABI 6, the batch-invariant route (ds_conv_tune.invariant): no split-K in any family (tune.splits 1: the fp32 cost model and the
+    // fp16-activation kernel's own under-fill split both honour it), and the widest column tiles for fp16-activation layers whose staged
+    // epilogue leaves column sums (their sums follow the pass geometry, which the default cost model picks from the pixel-tile count)
+    const bool inv = (a->tune.invariant & 1) != 0;
+    if (inv) {
+        p.t_splits = 1;
+        if (a->in_f16 && p.stats && p.t_nb <= 0) p.t_nb = 4;
+    }
     if (a->act == DS_ACT_GEGLU) {
         // gate fused into the epilogue: needs the staged float4 path on whole 64-column wave tiles, and no split-K
         if (a->taps != 1 || (a->cout & 63) || !p.vec_ok || a->res || a->cbias || a->out_nchw || a->stats_out) return DS_E_ARG;
@@ -565,13 +581,18 @@ static int route_conv(const ds_conv_args* a, KParams& p, ConvRoute& r) {
     }
     if (want_update) return DS_E_ARG;                      // the fused solver update exists in the head kernel only: fail loudly, never skip it
     if (!generic && stride == 1 && conv3x3_halo_supported(p)) {
+        // invariant: never the half-size waves (1284, bit 11) nor the 256 x 192 tiles (2568, bit 13): their outputs are the canonical chain
+        // but their GroupNorm column sums are added in another order (tests/test_hip_batch_invariant.py)
+        if (inv) p.t_variant |= 2048 | 8192;
         conv3x3_halo_route(p, r);
         p.splits = r.splits;
         return DS_OK;
     }
     if (p.norm) return DS_E_SHAPE;           // fused input normalisation exists only in the halo kernel
-    if (!generic && p.t_mode != 6 && gemm_dma8_applicable(p)) r.kernel_id = 2561;      // mode 6: no 8-wave DMA kernel
-    else if (p.t_mode == 0 && p.t_variant == 0 && gemv_rows_applicable(p)) r.kernel_id = 2573;
+    const bool emb_rows = inv && (a->tune.invariant & 2) && p.t_mode == 0 && p.t_variant == 0;
+    if (emb_rows && gemv_rows_applicable(p, true)) r.kernel_id = 2573;                 // invariant embedding projection: the row kernel at any row count
+    else if (!generic && p.t_mode != 6 && gemm_dma8_applicable(p)) r.kernel_id = 2561;      // mode 6: no 8-wave DMA kernel
+    else if (p.t_mode == 0 && p.t_variant == 0 && !inv && gemv_rows_applicable(p, false)) r.kernel_id = 2573;
     else {
         r.kernel_id = 0;
         r.splits = p.splits = choose_splits((long long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN), false, p.K / BK, 1, p.part ? p.part_cap : 0,

@@ -50,8 +50,11 @@ def fuse_norm16_here(mode, side, cout):
 
 
 class UNetEngine:
-    def __init__(self, spec: arch.UNetSpec, params: Dict[str, torch.Tensor], device='cuda', use_fp16=False, split_fp16=False):
-        """split_fp16: fp32 EMULATED on the fp16 matrix pipe in the 3x3 convolutions -- every operand as fp16 hi + lo, three MFMA
+    def __init__(self, spec: arch.UNetSpec, params: Dict[str, torch.Tensor], device='cuda', use_fp16=False, split_fp16=False,
+                 batch_invariant=False):
+        """batch_invariant: every plan takes the batch-invariant route: an image's output bits depend on its own
+        inputs, the weights and the mode only -- not on the batch size, the other images or the sigma form.
+        split_fp16: fp32 EMULATED on the fp16 matrix pipe in the 3x3 convolutions -- every operand as fp16 hi + lo, three MFMA
         products per multiplication, fp32 accumulation (ds_conv_args.wgt_f16 == 2); 2**-22 relative per product, i.e. inside every
         fp32 tolerance of this engine, at 16/3 of the fp32 matrix rate.  Not a reduced-precision mode: it is tested against the same
         fp32 goldens and tolerances as the exact fp32 path.
@@ -64,6 +67,7 @@ class UNetEngine:
         self.device = torch.device(device)
         self.use_fp16 = bool(use_fp16)
         self.split_fp16 = bool(split_fp16) and not self.use_fp16
+        self.batch_invariant = bool(batch_invariant)
         # fp16 mode: GroupNorm apply + SiLU inside the fp16-activation convolution's LDS halo instead of a ds_norm_act pass (plan(): fz0 / fz1;
         # bit-identical results).  An attribute, not an argument, so that A/B runs flip it per engine: DS_FUSE_NORM16 sets the default.
         self.fuse_norm16 = fuse_norm16_value(os.environ.get('DS_FUSE_NORM16', FUSE_NORM16_DEFAULT))
@@ -154,7 +158,8 @@ class UNetEngine:
         if key in self._plans:
             return self._plans[key]
         spec, dev, w, lib = self.spec, self.device, self.w, self.lib
-        bd = Builder(dev, conv_mode=self.conv_mode, w16_cache=self._w16_cache)      # owns the plan, its workspaces and the emitters
+        bd = Builder(dev, conv_mode=self.conv_mode, w16_cache=self._w16_cache,       # owns the plan, its workspaces and the emitters
+                     invariant=self.batch_invariant, batch=B)
         P, new = bd.P, bd.new
         R = spec.img_resolution
         Bs = emb_rows
@@ -217,20 +222,20 @@ class UNetEngine:
             if spec.label_dim:
                 pos2 = new(Bs, NC)
                 conv(bufs['labels'], bufs['labels'].shape[1], bufs['labels'].shape[1], Bs, 1, 1, w['label.w'], NC, pos2, NC, 1,
-                     'map_label', bias=w['label.b'], res=pos, res_ld=NC)
+                     'map_label', bias=w['label.b'], res=pos, res_ld=NC, emb=True)
                 src = pos2
-            conv(src, NC, NC, Bs, 1, 1, w['map0.w'], E, e0, E, 1, 'map_layer0', bias=w['map0.b'], act_=DS_ACT_SILU)
-            conv(e0, E, E, Bs, 1, 1, w['map1.w'], E, emb, E, 1, 'map_layer1', bias=w['map1.b'], act_=DS_ACT_SILU)
+            conv(src, NC, NC, Bs, 1, 1, w['map0.w'], E, e0, E, 1, 'map_layer0', bias=w['map0.b'], act_=DS_ACT_SILU, emb=True)
+            conv(e0, E, E, Bs, 1, 1, w['map1.w'], E, emb, E, 1, 'map_layer1', bias=w['map1.b'], act_=DS_ACT_SILU, emb=True)
         else:
-            conv(pos, NC, NC, Bs, 1, 1, w['map0.w'], E, e0, E, 1, 'map_layer0', bias=w['map0.b'], act_=DS_ACT_SILU)
+            conv(pos, NC, NC, Bs, 1, 1, w['map0.w'], E, e0, E, 1, 'map_layer0', bias=w['map0.b'], act_=DS_ACT_SILU, emb=True)
             lab = None
             if spec.label_dim:
                 lab = new(Bs, E)
                 conv(bufs['labels'], bufs['labels'].shape[1], bufs['labels'].shape[1], Bs, 1, 1, w['label.w'], E, lab, E, 1,
-                     'map_label', bias=w['label.b'])
+                     'map_label', bias=w['label.b'], emb=True)
             conv(e0, E, E, Bs, 1, 1, w['map1.w'], E, emb, E, 1, 'map_layer1', bias=w['map1.b'], res=lab, res_ld=E,
-                 act_=DS_ACT_SILU)
-        conv(emb, E, E, Bs, 1, 1, w['aff.w'], self.aff_total, aff, self.aff_total, 1, 'affine_all', bias=w['aff.b'])
+                 act_=DS_ACT_SILU, emb=True)
+        conv(emb, E, E, Bs, 1, 1, w['aff.w'], self.aff_total, aff, self.aff_total, 1, 'affine_all', bias=w['aff.b'], emb=True)
         bufs.update(emb=emb, aff=aff)
 
         # ---- fp16 residual stream -------------------------------------------------------------------------------
@@ -430,6 +435,8 @@ class UNetEngine:
                               S * 3 * cout, S * 3 * cout, S * 3 * cout, S * cout, B, hd, S, S, ch, 1.0 / math.sqrt(ch))
                 at.out_f16 = 1 if a16 else 0
                 at.in_f16 = 3 if a16 else 0
+                if self.batch_invariant and not f16_attn and ch % 128 == 0:
+                    at.variant = 2          # invariant: the channel-split block at every batch (ds_attention_variant)
                 add(lib.ds_attention_f16 if f16_attn else lib.ds_attention, (C.byref(at),), nm + '.attention', keep=(at,))
                 if b.pushes_skip:
                     out2 = bd.new16(M, cout) if f16_out else new(M, cout)
@@ -485,9 +492,12 @@ class EDMDenoiser:
     """
     edm_raw_output = True      # solvers._Run: ds_solver_update applies the EDM preconditioning to the raw output itself
 
-    def __init__(self, spec: arch.UNetSpec, params: Dict[str, torch.Tensor], device='cuda', use_fp16=False, split_fp16=False):
+    def __init__(self, spec: arch.UNetSpec, params: Dict[str, torch.Tensor], device='cuda', use_fp16=False, split_fp16=False,
+                 batch_invariant=False):
+        """batch_invariant: same seed, same bits at any batch (UNetEngine)."""
         self.spec = spec
-        self.engine = UNetEngine(spec, params, device, use_fp16=use_fp16, split_fp16=split_fp16)
+        self.engine = UNetEngine(spec, params, device, use_fp16=use_fp16, split_fp16=split_fp16, batch_invariant=batch_invariant)
+        self.batch_invariant = bool(batch_invariant)
         self.device = self.engine.device
         self.img_resolution = spec.img_resolution
         self.img_channels = spec.in_channels
@@ -500,20 +510,22 @@ class EDMDenoiser:
         self.bottleneck_name = None      # set by the AMED path: 'enc.8x8_block3' / 'enc.8x8_block2'
 
     @classmethod
-    def from_config(cls, name_or_kwargs, seed=0, mode='signal', device='cuda', use_fp16=False, split_fp16=False):
+    def from_config(cls, name_or_kwargs, seed=0, mode='signal', device='cuda', use_fp16=False, split_fp16=False, batch_invariant=False):
         kw = arch.NAMED_CONFIGS[name_or_kwargs] if isinstance(name_or_kwargs, str) else name_or_kwargs
         spec = arch.edm_precond_spec(**kw)
-        return cls(spec, arch.init_params(spec, seed=seed, mode=mode), device, use_fp16=use_fp16, split_fp16=split_fp16)
+        return cls(spec, arch.init_params(spec, seed=seed, mode=mode), device, use_fp16=use_fp16, split_fp16=split_fp16,
+                   batch_invariant=batch_invariant)
 
     @classmethod
-    def from_reference_module(cls, net, device='cuda', use_fp16=None):
+    def from_reference_module(cls, net, device='cuda', use_fp16=None, batch_invariant=False):
         """Build from a live reference ``EDMPrecond`` instance (duck-typed: pickled EDM classes are exec'd from
         source, so ``isinstance`` is useless -- persistence.py:222-233).  ``use_fp16`` None: follow the module's own flag
         (networks_edm.py:472, :486 -- the public ImageNet-64 checkpoint carries use_fp16=True)."""
         spec = spec_from_module(net)
         if use_fp16 is None:
             use_fp16 = bool(getattr(net, 'use_fp16', False))
-        return cls(spec, {k: v for k, v in net.state_dict().items() if 'resample_filter' not in k}, device, use_fp16=use_fp16)
+        return cls(spec, {k: v for k, v in net.state_dict().items() if 'resample_filter' not in k}, device, use_fp16=use_fp16,
+                   batch_invariant=batch_invariant)
 
     def eval(self):
         return self

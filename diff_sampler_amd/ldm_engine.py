@@ -34,7 +34,8 @@ from .engine import fuse_norm16_here
 
 
 class LDMUNetEngine:
-    def __init__(self, spec: ldm_arch.LDMUNetSpec, params: Dict[str, torch.Tensor], device='cuda', use_fp16=False, qkv_f16_min_head=40, f16_downsample=True):
+    def __init__(self, spec: ldm_arch.LDMUNetSpec, params: Dict[str, torch.Tensor], device='cuda', use_fp16=False, qkv_f16_min_head=40, f16_downsample=True,
+                 batch_invariant=False):
         """use_fp16: the reference samples this U-Net under ``autocast("cuda")`` (diff-solvers-main/sample.py:296): convolutions and
         Linear layers multiply fp16 operands (fp32 accumulation here) and emit fp16 tensors.  Here: ResBlock / Upsample convolutions, every
         projection of the transformer blocks and attention on the fp16 kernels, and the activations between layers -- residual stream,
@@ -42,7 +43,9 @@ class LDMUNetEngine:
         norm / softmax arithmetic, the context projections and the time embedding are fp32.  qkv_f16_min_head: q / k / v of the attention
         layers with at least this head size are the fp16 rows their projections emit under autocast (smaller heads: fp32 rows the attention
         kernel rounds itself); f16_downsample: the strided Downsample convolutions read and write the fp16 stream (False: an fp32 copy and the
-        generic fp32 kernel, the round-3 routing) -- A/B knobs of benchmarks, the defaults are what the parity goldens were made with."""
+        generic fp32 kernel, the round-3 routing) -- A/B knobs of benchmarks, the defaults are what the parity goldens were made with.
+        batch_invariant: the batch-invariant route in every plan (engine.UNetEngine)."""
+        self.batch_invariant = bool(batch_invariant)
         self.qkv_f16_min_head = int(qkv_f16_min_head)
         self.f16_downsample = bool(f16_downsample)
         from .engine import FUSE_NORM16_DEFAULT, fuse_norm16_value
@@ -135,7 +138,7 @@ class LDMUNetEngine:
         if key in self._plans:
             return self._plans[key]
         spec, w, lib = self.spec, self.w, self.lib
-        bd = Builder(self.device, conv_mode=(1 if self.use_fp16 else 0), w16_cache=self._w16_cache)
+        bd = Builder(self.device, conv_mode=(1 if self.use_fp16 else 0), w16_cache=self._w16_cache, invariant=self.batch_invariant, batch=N)
         P, new = bd.P, bd.new
         bufs = P.bufs
         R, Cin, MC, E = spec.img_resolution, spec.in_channels, spec.model_channels, spec.time_embed_dim
@@ -153,9 +156,9 @@ class LDMUNetEngine:
         # ---- time embedding (openaimodel.py:726-727) and every ResBlock's emb_layers in one GEMM ---------------------------
         pos, e0, emb, aff = new(emb_rows, MC), new(emb_rows, E), new(emb_rows, E), new(emb_rows, self.aff_total)
         bd.add(lib.ds_noise_embed, (ptr(bufs['c_noise']), emb_rows, ptr(w['freqs']), MC, 2, ptr(pos), MC), 'timestep_embedding')
-        bd.linear(pos, MC, emb_rows, w['te0.w'], E, e0, 'time_embed.0', bias=w['te0.b'], act=DS_ACT_SILU)
-        bd.linear(e0, E, emb_rows, w['te2.w'], E, emb, 'time_embed.2', bias=w['te2.b'], act=DS_ACT_SILU)   # SiLU of emb_layers[0]
-        bd.linear(emb, E, emb_rows, w['aff.w'], self.aff_total, aff, 'emb_layers_all', bias=w['aff.b'])
+        bd.linear(pos, MC, emb_rows, w['te0.w'], E, e0, 'time_embed.0', bias=w['te0.b'], act=DS_ACT_SILU, emb=True)
+        bd.linear(e0, E, emb_rows, w['te2.w'], E, emb, 'time_embed.2', bias=w['te2.b'], act=DS_ACT_SILU, emb=True)   # SiLU of emb_layers[0]
+        bd.linear(emb, E, emb_rows, w['aff.w'], self.aff_total, aff, 'emb_layers_all', bias=w['aff.b'], emb=True)
 
         # ---- fp16 residual stream: under torch.autocast (sample.py:293-297) the reference's convolutions and Linear layers emit fp16
         # tensors, so every activation between layers is fp16.  Every ResBlock / SpatialTransformer / upsampling convolution that runs on
@@ -438,9 +441,11 @@ class CFGDenoiser(CFGSchedule):
     host_sigma_ok = True       # solvers._Run: pass sigma as a Python float (c_noise is host math; nothing to copy or sync)
 
     def __init__(self, spec: ldm_arch.LDMUNetSpec, params: Dict[str, torch.Tensor], device='cuda', guidance_rate=None,
-                 guidance_type=None, use_fp16=False, **engine_kw):
+                 guidance_type=None, use_fp16=False, batch_invariant=False, **engine_kw):
+        """batch_invariant: same seed, same bits at any batch (LDMUNetEngine)."""
         self.spec = spec
-        self.engine = LDMUNetEngine(spec, params, device, use_fp16=use_fp16, **engine_kw)
+        self.engine = LDMUNetEngine(spec, params, device, use_fp16=use_fp16, batch_invariant=batch_invariant, **engine_kw)
+        self.batch_invariant = bool(batch_invariant)
         self.device = self.engine.device
         self.guidance_rate = spec.guidance_rate if guidance_rate is None else guidance_rate
         self.guidance_type = spec.guidance_type if guidance_type is None else guidance_type

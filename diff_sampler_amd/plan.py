@@ -229,11 +229,14 @@ def _native_plan(ops):
 
 
 class Builder:
-    def __init__(self, device, conv_mode=0, w16_cache=None, autotune=True):
+    def __init__(self, device, conv_mode=0, w16_cache=None, autotune=True, invariant=False, batch=None):
         """w16_cache: dict owned by the engine (it outlives the per-batch plans): data_ptr of a row-padded fp32 1x1 / Linear weight
         -> its fp16 packing, made on first use when conv_mode == 1.  autotune: measure the tile shapes of the fp16-activation kernels
-        (see AUTOTUNE above)."""
+        (see AUTOTUNE above).  invariant: the batch-invariant mode: every convolution carries ds_conv_tune.invariant
+        and no rule of this builder looks at the batch -- `batch` (images of the plan) tells the per-image row count of a Linear layer."""
         self.autotune = bool(autotune)
+        self.invariant = bool(invariant)
+        self.batch = batch
         self.w16_cache = w16_cache if w16_cache is not None else {}
         self.P = Plan()
         self.dev = device
@@ -262,13 +265,15 @@ class Builder:
 
     def conv(self, x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, taps, name, x1=None, c1=0, ld1=0, bias=None, cbias=None,
              cbias_ld=0, cbias_rows=1, res=None, res_ld=0, scale=1.0, act=DS_ACT_NONE, norm_coefs=None, norm_act=DS_ACT_NONE,
-             e0=None, ec0=0, e1=None, ec1=0, stride=1, stats=False, w16=None, out_nchw=0, in_f16=False, out_f16=False):
+             e0=None, ec0=0, e1=None, ec1=0, stride=1, stats=False, w16=None, out_nchw=0, in_f16=False, out_f16=False, emb=False):
         """stats=True: the epilogue also leaves the output's per-(64-row block, channel) sums for the consumer's GroupNorm
         (honoured when cout % 64 == 0; otherwise the consumer falls back to a ds_gn_stats pass).
         w16: fp16 weights of the same layer (ops.pack_conv_weight_f16); used -- with the fp16-operand kernel -- when the
         geometry supports it (f16_level), else the fp32 weights `wgt` are.
         in_f16: x0 (and e0) are fp16 NHWC tensors (leading dimensions in halfs) written by ``norm(..., out_f16=True)``: the
-        fp16-activation kernel (csrc/conv3x3_f16dma.hip); needs w16."""
+        fp16-activation kernel (csrc/conv3x3_f16dma.hip); needs w16.
+        emb: a projection of the embedding path (one row per image or one shared row): in the invariant mode the row kernel at every row
+        count (ds_conv_tune.invariant bit 1), so that both sigma forms and every batch give the same embedding rows."""
         if taps == 1 and x0.dtype == torch.float16:
             # 1x1 / Linear on an fp16 tensor (LayerNorm / GroupNorm pass / attention / GEGLU output in fp16 mode): csrc/gemm_f16dma.hip
             assert x1 is None and not ec0 and norm_coefs is None and not out_nchw and stride == 1
@@ -286,7 +291,8 @@ class Builder:
         shift = 0
         if f16:
             wgt, shift = w16
-        elif self.conv_mode == 1 and taps == 1 and stride == 1 and norm_coefs is None and not ec0 and not ec1 and not out_nchw:
+        elif (self.conv_mode == 1 and taps == 1 and stride == 1 and norm_coefs is None and not ec0 and not ec1 and not out_nchw
+              and (not self.invariant or self._rows_per_image_ok(n * h * w))):
             wgt, f16 = self.linear_w16(wgt, n * h * w, c0, c1)
         a = ConvArgs(ptr(x0), ptr(x1), c0, c1, ld0, ld1, n, h, w, taps, ptr(wgt), cout, ptr(bias), ptr(cbias), cbias_ld,
                      cbias_rows, ptr(res), res_ld, scale, act, ptr(out), out_ld, ptr(norm_coefs), norm_act, ptr(e0), ptr(e1),
@@ -297,6 +303,8 @@ class Builder:
         a.out_nchw = out_nchw               # network output written channel-planar (NCHW) by the epilogue
         a.wgt_f16, a.wgt_shift = (self.conv_mode, shift) if f16 else (0, 0)
         a.in_f16 = 1 if in_f16 else 0
+        if self.invariant:
+            a.tune.invariant = 3 if emb else 1
         if out_f16 or out.dtype == torch.float16:          # fp16 output rows: conv0 outputs, projection operands, the fp16 residual stream
             assert in_f16 and out.dtype == torch.float16 and cout % 64 == 0, name
             a.out_f16 = 1
@@ -401,10 +409,17 @@ class Builder:
             self.w16_cache[key] = (pack_linear_weight_f16(wgt), wgt)       # keep the source alive: its address is the key
         return self.w16_cache[key][0], True
 
+    def _rows_per_image_ok(self, rows):
+        """Invariant mode: may a 1x1 / Linear layer over `rows` rows take the fp16-operand GEMM (whole 256-row tiles)?  Only where every
+        batch gives it whole tiles -- a multiple of 256 rows per image -- so the choice never depends on the batch."""
+        return bool(self.batch) and rows % self.batch == 0 and (rows // self.batch) % 256 == 0
+
     def f16_level(self, n, h, w, c0, c1, ec0, ec1):
         """0 = no fp16-operand kernel for this 3x3 layer, 1 = on raw input only, 2 = also with the fused input normalisation."""
         if self.conv_mode == 0 or any(c % (64 if self.conv_mode == 1 else 32) for c in (c0, c1, ec0, ec1)):
             return 0
+        if self.invariant and (h * w) % 256:
+            return 0            # 8x8: the reduced-operand kernels take whole 256-pixel tiles, i.e. only batches that are multiples of four
         fn = self.lib.ds_conv_f16_supported if self.conv_mode == 1 else self.lib.ds_conv_split_supported
         return int(fn(n, h, w, c0, c1, ec0, ec1))
 
@@ -436,7 +451,7 @@ class Builder:
             assert kind == 'apply' and out.dtype == torch.float16 and (raw_out is None or raw_out.dtype == torch.float16)
             a.out_f16, a.raw_out, a.raw_ld = 1, ptr(raw_out), raw_ld
             self._fold_finalize(a, coefs)
-        if kind == 'stats' and n < 256:
+        if kind == 'stats' and n < 256 and not self.invariant:       # (invariant: one workgroup per image at every batch)
             if self.gn_partial is None or self.gn_counters.numel() < n:
                 self.gn_partial = torch.empty(n * _lib.DS_GN_MAX_CHUNKS * 128, dtype=torch.float64, device=self.dev)
                 self.gn_counters = torch.zeros(n, dtype=torch.int32, device=self.dev)

@@ -231,8 +231,11 @@ SOLVER_FNS = dict(euler='euler_sampler', heun='heun_sampler', dpm='dpm_2_sampler
 
 # ------------------------------------------------------------------------------------------------------------------
 def create_model(dataset_name=None, model_path=None, random_init=False, device=None, seed=0, guidance_type=None, guidance_rate=None,
-                 use_fp16=False):
-    """EDM networks (cifar10 / ffhq / afhqv2 / imagenet64; sample.py:80-85) -> (net, 'edm'); Stable Diffusion v1.x latent
+                 use_fp16=False, batch_invariant=False):
+    """batch_invariant: the engines' batch-invariant mode -- a seed's output bits do not depend on --batch, the seeds sharing its batch or
+    the number of ranks.
+
+    EDM networks (cifar10 / ffhq / afhqv2 / imagenet64; sample.py:80-85) -> (net, 'edm'); Stable Diffusion v1.x latent
     U-Net under classifier-free guidance (ms_coco; sample.py:111-116) -> (net, 'ldm').
 
     use_fp16: the fp16-operand kernels (fp32 accumulation and storage).  The reference leaves `--use_fp16` unwired
@@ -253,16 +256,17 @@ def create_model(dataset_name=None, model_path=None, random_init=False, device=N
             sd = sd.get('state_dict', sd)
             pre = 'model.diffusion_model.'
             params = {k[len(pre):]: v.float() for k, v in sd.items() if k.startswith(pre)}
-        return CFGDenoiser(spec, params, device, guidance_rate=(7.5 if guidance_rate is None else guidance_rate), use_fp16=bool(use_fp16)), 'ldm'
+        return CFGDenoiser(spec, params, device, guidance_rate=(7.5 if guidance_rate is None else guidance_rate), use_fp16=bool(use_fp16),
+                           batch_invariant=bool(batch_invariant)), 'ldm'
     if dataset_name not in arch.NAMED_CONFIGS:
         raise ValueError(f'dataset {dataset_name!r}: only the EDM networks are in scope of the HIP engine '
                          f'({sorted(k for k in arch.NAMED_CONFIGS if not k.startswith("tiny"))} and ms_coco); CM / ADM-classifier-guided / LSUN-LDM models run on the reference')
     if random_init or model_path is None:
-        net = EDMDenoiser.from_config(dataset_name, seed=seed, device=device, use_fp16=bool(use_fp16))
+        net = EDMDenoiser.from_config(dataset_name, seed=seed, device=device, use_fp16=bool(use_fp16), batch_invariant=bool(batch_invariant))
     else:
         with open(model_path, 'rb') as f:       # needs the reference's torch_utils/dnnlib importable for unpickling
             ref = pickle.load(f)['ema']
-        net = EDMDenoiser.from_reference_module(ref, device=device, use_fp16=(True if use_fp16 else None))
+        net = EDMDenoiser.from_reference_module(ref, device=device, use_fp16=(True if use_fp16 else None), batch_invariant=bool(batch_invariant))
     net.sigma_min, net.sigma_max = 0.002, 80.0
     return net, 'edm'
 
@@ -356,6 +360,7 @@ def run(dataset_name=None, max_batch_size=64, seeds='0-63', grid=False, outdir=N
     # "image" is a flat colour that encodes its seed, written through the real sharding / per-batch barriers / PNG sink / output tree.
     # It exists so that the N > 1 host path is exercised where there is no GPU; it is not a CPU mode of the sampler.
     stub = bool(solver_kwargs.pop('stub', False))
+    batch_invariant = bool(solver_kwargs.pop('batch_invariant', False))       # --batch_invariant: the engines' mode, not a solver setting
     if stub:
         device = torch.device('cpu')
     else:
@@ -393,7 +398,7 @@ def run(dataset_name=None, max_batch_size=64, seeds='0-63', grid=False, outdir=N
         net, solver_kwargs['model_source'] = create_model(dataset_name, model_path, random_init, device,
                                                           guidance_type=solver_kwargs.get('guidance_type'),
                                                           guidance_rate=solver_kwargs.get('guidance_rate'),
-                                                          use_fp16=solver_kwargs.get('use_fp16', False))
+                                                          use_fp16=solver_kwargs.get('use_fp16', False), batch_invariant=batch_invariant)
     ldm = solver_kwargs['model_source'] == 'ldm'
     cond_table = None
     if ldm and solver_kwargs.get('condition_path'):
@@ -533,6 +538,7 @@ if click is not None:
     @click.option('--denoise_to_zero', help='Whether to denoise from the last time step to 0', type=bool, default=False)
     @click.option('--return_inters', help='Whether to save intermediate outputs', metavar='BOOL', type=bool, default=False)
     @click.option('--use_fp16', help='Whether to use mixed precision', metavar='BOOL', type=bool, default=False)
+    @click.option('--batch_invariant', help='Same seed, same bits at any --batch and world size', metavar='BOOL', type=bool, default=False)
     @click.option('--max_order', help='Max order for solvers', metavar='INT', type=click.IntRange(min=1))
     @click.option('--predict_x0', help='Whether to use data prediction mode', metavar='BOOL', type=bool, default=True)
     @click.option('--lower_order_final', help='Whether to lower the order at final stages', metavar='BOOL', type=bool, default=True)

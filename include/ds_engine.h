@@ -47,7 +47,8 @@ extern "C" {
 #define DS_RESAMPLE_DOWN 1  /* 2x2 box filter, stride 2  (networks_edm.py:77 with resample_filter [1,1]) */
 #define DS_RESAMPLE_UP 2    /* nearest neighbour x2      (networks_edm.py:75 with resample_filter [1,1]) */
 
-DS_API int ds_version(void);      /* ABI version; a host must check it before passing argument structs.  5: ds_conv_route / ds_attention_variant added (the
+DS_API int ds_version(void);      /* ABI version; a host must check it before passing argument structs.  6: ds_conv_tune.invariant appended (the
+                               * batch-invariant route; struct size changed); the row kernel of 1x1 / Linear layers takes any row count.  5: ds_conv_route / ds_attention_variant added (the
                                * library's routing decisions as queries; ds_conv_kernel_id answers negative codes for rejected arguments).  4 (round 6): ds_norm_args.stats0 / stats1 / tune_variant and ds_attn_args.variant
                                * appended (the pass that computes its own GroupNorm statistics; struct size changed).  3 (round 5): ds_conv_args.update appended (the head-fused
                                * solver update; struct size changed), ds_build_experiments() added, ds_conv_args.norm_coefs also accepted with in_f16.
@@ -98,6 +99,15 @@ typedef struct ds_conv_tune {
      * bit 1: no halo DMA after the first slab, bit 2: no epilogue, bit 4: no per-tap barrier, bit 5: no LDS fragment reads; bit 10
      * (results stay correct): fp16 residual rows requested one group ahead instead of early (profiles/r3_gemm_f16dma_epilogue.txt). */
     int ablate;
+    /* ABI 6.  Bit 0: the batch-invariant route.  Every decision that can change the order in which an output element is summed is taken
+     * without looking at the batch: no split-K in any kernel family (`splits` is ignored), neither the half-size-wave 128-pixel tiles (kernel
+     * id 1284) nor the 256 x 192 tiles (2568) -- their outputs are bit-identical, their GroupNorm column sums are added in another order --,
+     * the widest column tiles for fp16-activation layers that leave column sums.  Tile shapes and kernel families stay free only among those that sum every output in the layer's canonical (step, tap, channel)
+     * chain (tests/test_hip_batch_invariant.py).  Bit 1 (with bit 0): a projection of the embedding path -- the row kernel (kernel id 2573)
+     * at every row count where it applies (no residual, per-image bias or column sums); a projection it does not take (the label embeddings
+     * with a residual operand) runs unsplit on the matrix kernels at every row count.  An output row then depends on its own input row and
+     * the layer alone, whatever the batch.  Host side only: no kernel reads it. */
+    int invariant;
 } ds_conv_tune;
 
 typedef struct ds_conv_args {
