@@ -48,8 +48,11 @@ __global__ void __launch_bounds__(256) flash_attn_kernel(const ds_attn_args a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Ks = smem;
     float* Vs = smem + KT * KLD;
-    float* Es = smem + KT * KLD + KT * VLD + 32;   // epilogue transposition patches, 32 x 33 floats per wave
-    float* Rs = Es + 4 * 32 * 33;                  // DSPLIT: the four waves' partial S^T blocks, [wave][register][lane]
+    // D = 512 (the AutoencoderKL mid-block attention, one head of 512 channels): the K / V tiles alone are 130 KB, so the epilogue patches
+    // alias the K tile -- dead once the key loop is over (a barrier separates the two uses) -- and the whole block stays inside 160 KB
+    constexpr bool ES_ALIAS = D >= 512;
+    float* Es = ES_ALIAS ? smem : smem + KT * KLD + KT * VLD + 32;   // epilogue transposition patches, 32 x 33 floats per wave
+    float* Rs = smem + KT * KLD + KT * VLD + 32 + (ES_ALIAS ? 0 : 4 * 32 * 33);   // DSPLIT: the four waves' partial S^T blocks, [wave][register][lane]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hb = lane >> 5, l31 = lane & 31;
@@ -192,6 +195,7 @@ __global__ void __launch_bounds__(256) flash_attn_kernel(const ds_attn_args a) {
             }
         }
     }
+    if constexpr (ES_ALIAS) __syncthreads();        // every wave is done with the last K tile before the patches overwrite it
     if (!active) return;
 
     const float inv = 1.0f / (l + __shfl_xor(l, 32));
@@ -237,6 +241,7 @@ __global__ void __launch_bounds__(256) flash_attn_kernel(const ds_attn_args a) {
 // than 1 024 waves (one per SIMD); ds_attn_args.variant: 1 = query split, 2 = channel split (tests, A/B runs).  Other head sizes: query split.
 extern "C" int ds_attention_variant(const ds_attn_args* a) {
     if (!a) return DS_E_ARG;
+    if (a->d >= 512) return a->d % 128 == 0 ? 2 : 1;
     if (a->d % 128 == 0) {
         const long long waves = (long long)((a->sq + 127) / 128) * a->heads * a->batch * 4;
         if (a->variant == 2 || (a->variant != 1 && waves < 1024)) return 2;
@@ -250,9 +255,9 @@ template <int D>
 int launch(const ds_attn_args* a, hipStream_t stream) {
     constexpr int DB = (D > 32 && (D % 32) == 8) ? D / 32 : (D + 31) / 32;
     constexpr int KT = (D <= 64 && !(D > 32 && (D % 32) == 8)) ? 64 : 32;
-    constexpr int bytes = (KT * (D + 4) + KT * (DB * 32 + 8) + 32 + 4 * 32 * 33) * (int)sizeof(float);
+    constexpr int bytes = (KT * (D + 4) + KT * (DB * 32 + 8) + 32 + (D >= 512 ? 0 : 4 * 32 * 33)) * (int)sizeof(float);
     if constexpr (D % 128 == 0) {
-        if (ds_attention_variant(a) == 2) {
+        if (D >= 512 || ds_attention_variant(a) == 2) {     // 512 channels: the channel split only (a query-split wave would hold 16 O^T blocks)
             constexpr int bytes_d = bytes + 4 * 16 * 64 * (int)sizeof(float);
             DS_ENSURE_DYN_LDS((&flash_attn_kernel<D, true>), bytes_d);
             dim3 grid((a->sq + 31) / 32, a->heads, a->batch);
@@ -261,10 +266,12 @@ int launch(const ds_attn_args* a, hipStream_t stream) {
             return DS_OK;
         }
     }
-    DS_ENSURE_DYN_LDS((&flash_attn_kernel<D>), bytes);
-    dim3 grid((a->sq + 127) / 128, a->heads, a->batch);
-    hipLaunchKernelGGL(flash_attn_kernel<D>, grid, dim3(256), bytes, stream, *a);
-    DS_CHECK_LAUNCH();
+    if constexpr (D < 512) {
+        DS_ENSURE_DYN_LDS((&flash_attn_kernel<D>), bytes);
+        dim3 grid((a->sq + 127) / 128, a->heads, a->batch);
+        hipLaunchKernelGGL(flash_attn_kernel<D>, grid, dim3(256), bytes, stream, *a);
+        DS_CHECK_LAUNCH();
+    }
     return DS_OK;
 }
 
@@ -272,7 +279,7 @@ int launch(const ds_attn_args* a, hipStream_t stream) {
 
 extern "C" int ds_attention_supported(int d) {
     switch (d) {
-        case 8: case 16: case 32: case 40: case 64: case 80: case 96: case 128: case 160: case 256: return 1;
+        case 8: case 16: case 32: case 40: case 64: case 80: case 96: case 128: case 160: case 256: case 512: return 1;
         default: return 0;
     }
 }
@@ -297,6 +304,7 @@ extern "C" int ds_attention(const ds_attn_args* a, void* stream) {
         case 128: return launch<128>(a, s);
         case 160: return launch<160>(a, s);
         case 256: return launch<256>(a, s);
+        case 512: return launch<512>(a, s);
         default: return DS_E_SHAPE;
     }
 }

@@ -369,6 +369,15 @@ int launch_splitk_reduce(const KParams& p, hipStream_t stream) {
 
 }  // namespace igemm
 
+// conv3x3_f16wide.hip: the fp16-activation 3x3 convolution on 4 x 64 patches, for images wider than 64 pixels (kernel id 2575).  Declared here,
+// next to their only caller, and not in igemm_common.h: the persisted tile table (diff_sampler_amd/data/tile_table.json) is tied to the hash
+// of every header of csrc/.
+namespace igemm {
+bool conv3x3_f16wide_applicable(const KParams& p);
+void conv3x3_f16wide_route(const KParams& p, ConvRoute& r);
+int launch_conv3x3_f16wide(KParams& p, const ConvRoute& r, hipStream_t stream);
+}  // namespace igemm
+
 using namespace igemm;
 
 // ds_conv_args.tune -> KParams: per-call kernel selection overrides (include/ds_engine.h); the library keeps no selection state.
@@ -557,7 +566,13 @@ static int route_conv(const ds_conv_args* a, KParams& p, ConvRoute& r) {
         if (a->in_f16) {
             p.ldb = p.K / 2;
             p.out_f16 = a->out_f16 ? 1 : 0; p.res_f16 = a->res_f16 ? 1 : 0;
-            if (!conv3x3_f16dma_applicable(p)) return DS_E_SHAPE;
+            if (!conv3x3_f16dma_applicable(p)) {
+                // images wider than 64 pixels (the AutoencoderKL decoder): the 4 x 64 patch form of the kernel, csrc/conv3x3_f16wide.hip
+                if (a->wgt_shift || !conv3x3_f16wide_applicable(p)) return DS_E_SHAPE;
+                p.part = nullptr; p.part_cap = 0;
+                conv3x3_f16wide_route(p, r);
+                return DS_OK;
+            }
             conv3x3_f16dma_route(p, r);                     // p.part stays: under-filled layers split K (conv3x3_f16dma_splits)
             p.splits = r.splits;
             return DS_OK;
@@ -618,6 +633,7 @@ extern "C" int ds_conv2d_nhwc(const ds_conv_args* a, void* stream) {
         case 2570: return launch_conv3x3_thin(p, s);
         case 2571: return launch_gemm_f16dma(p, s, true);
         case 2573: return launch_gemv_rows(p, s);
+        case 2575: return launch_conv3x3_f16wide(p, r, s);
         default: return launch_conv3x3_halo(p, r, s);      // 128 / 256 / 1284 / 2560 / 2565 / 2568
     }
 }

@@ -231,8 +231,12 @@ SOLVER_FNS = dict(euler='euler_sampler', heun='heun_sampler', dpm='dpm_2_sampler
 
 # ------------------------------------------------------------------------------------------------------------------
 def create_model(dataset_name=None, model_path=None, random_init=False, device=None, seed=0, guidance_type=None, guidance_rate=None,
-                 use_fp16=False, batch_invariant=False):
-    """batch_invariant: the engines' batch-invariant mode -- a seed's output bits do not depend on --batch, the seeds sharing its batch or
+                 use_fp16=False, batch_invariant=False, decode_latents=False):
+    """decode_latents (ms_coco): also build the AutoencoderKL decoder (vae_engine.VAEDecoder: the reference's decode_first_stage, sample.py:299)
+    and hand it over as ``net.decoder`` -- from the checkpoint's ``first_stage_model.decoder.*`` / ``first_stage_model.post_quant_conv.*``
+    tensors, or random-init like the U-Net.
+
+    batch_invariant: the engines' batch-invariant mode -- a seed's output bits do not depend on --batch, the seeds sharing its batch or
     the number of ranks.
 
     EDM networks (cifar10 / ffhq / afhqv2 / imagenet64; sample.py:80-85) -> (net, 'edm'); Stable Diffusion v1.x latent
@@ -249,15 +253,27 @@ def create_model(dataset_name=None, model_path=None, random_init=False, device=N
         from .ldm_engine import CFGDenoiser
         assert guidance_type == 'cfg', 'ms_coco samples with classifier-free guidance (sample.py:112)'
         spec = ldm_arch.ldm_unet_spec(**ldm_arch.NAMED_LDM_CONFIGS['sd15'])
+        vae_params = None
         if random_init or model_path is None:
             params = ldm_arch.init_ldm_params(spec, seed=seed)
         else:                                   # SD checkpoint: the U-Net lives under 'model.diffusion_model.' (ddpm.py:1399)
             sd = torch.load(model_path, map_location='cpu')
             sd = sd.get('state_dict', sd)
-            pre = 'model.diffusion_model.'
-            params = {k[len(pre):]: v.float() for k, v in sd.items() if k.startswith(pre)}
+            params, vae_params = split_sd_checkpoint(sd)
+        decoder = None
+        if decode_latents:
+            from . import vae_arch
+            from .vae_engine import VAEDecoder
+            vspec = vae_arch.vae_decoder_spec(**vae_arch.NAMED_VAE_CONFIGS['sd15'])
+            if random_init or model_path is None:
+                vae_params = vae_arch.init_vae_params(vspec, seed=seed)
+            elif not vae_params:
+                raise ValueError(f'--decode_latents: {model_path} holds no first_stage_model.decoder.* tensors')
+            else:
+                vae_params = vae_arch.vae_params_from_state_dict(vspec, vae_params)
+            decoder = VAEDecoder(vspec, vae_params, device, use_fp16=bool(use_fp16), batch_invariant=bool(batch_invariant))
         return CFGDenoiser(spec, params, device, guidance_rate=(7.5 if guidance_rate is None else guidance_rate), use_fp16=bool(use_fp16),
-                           batch_invariant=bool(batch_invariant)), 'ldm'
+                           batch_invariant=bool(batch_invariant), decoder=decoder), 'ldm'
     if dataset_name not in arch.NAMED_CONFIGS:
         raise ValueError(f'dataset {dataset_name!r}: only the EDM networks are in scope of the HIP engine '
                          f'({sorted(k for k in arch.NAMED_CONFIGS if not k.startswith("tiny"))} and ms_coco); CM / ADM-classifier-guided / LSUN-LDM models run on the reference')
@@ -269,6 +285,16 @@ def create_model(dataset_name=None, model_path=None, random_init=False, device=N
         net = EDMDenoiser.from_reference_module(ref, device=device, use_fp16=(True if use_fp16 else None), batch_invariant=bool(batch_invariant))
     net.sigma_min, net.sigma_max = 0.002, 80.0
     return net, 'edm'
+
+
+def split_sd_checkpoint(sd):
+    """(U-Net tensors keyed below 'model.diffusion_model.', decode-path tensors keyed below 'first_stage_model.') of a Stable Diffusion
+    state_dict (ddpm.py:1399, :461-466); the second dict is empty when the checkpoint carries no first stage."""
+    from . import vae_arch
+    pre = 'model.diffusion_model.'
+    unet = {k[len(pre):]: v.float() for k, v in sd.items() if k.startswith(pre)}
+    vae, _ = vae_arch.split_first_stage(sd)
+    return unet, {k: v.float() for k, v in vae.items()}
 
 
 class PngSink:
@@ -361,6 +387,7 @@ def run(dataset_name=None, max_batch_size=64, seeds='0-63', grid=False, outdir=N
     # It exists so that the N > 1 host path is exercised where there is no GPU; it is not a CPU mode of the sampler.
     stub = bool(solver_kwargs.pop('stub', False))
     batch_invariant = bool(solver_kwargs.pop('batch_invariant', False))       # --batch_invariant: the engines' mode, not a solver setting
+    decode_latents = bool(solver_kwargs.pop('decode_latents', False))         # --decode_latents: ms_coco writes decoded PNGs instead of latents
     if stub:
         device = torch.device('cpu')
     else:
@@ -398,7 +425,8 @@ def run(dataset_name=None, max_batch_size=64, seeds='0-63', grid=False, outdir=N
         net, solver_kwargs['model_source'] = create_model(dataset_name, model_path, random_init, device,
                                                           guidance_type=solver_kwargs.get('guidance_type'),
                                                           guidance_rate=solver_kwargs.get('guidance_rate'),
-                                                          use_fp16=solver_kwargs.get('use_fp16', False), batch_invariant=batch_invariant)
+                                                          use_fp16=solver_kwargs.get('use_fp16', False), batch_invariant=batch_invariant,
+                                                          **(dict(decode_latents=True) if decode_latents else {}))
     ldm = solver_kwargs['model_source'] == 'ldm'
     cond_table = None
     if ldm and solver_kwargs.get('condition_path'):
@@ -500,8 +528,16 @@ def run(dataset_name=None, max_batch_size=64, seeds='0-63', grid=False, outdir=N
                 images = sampler_fn(net, latents, class_labels=class_labels, **solver_kwargs)
         if solver_kwargs.get('return_inters'):
             images = images[-1]
-        if ldm:
-            # latents [B, 4, 64, 64]: decoding them is the VAE's job (net.model.decode_first_stage, sample.py:303), not on this path
+        if ldm and decode_latents:
+            # net.model.decode_first_stage (sample.py:299): latents [B, 4, 64, 64] -> images [B, 3, 512, 512], saved like every other net's
+            with torch.no_grad():
+                images = net.decoder(images)
+            if grid:
+                save_grid(images, outdir)
+            else:
+                save_images(images, batch_seeds, outdir, subdirs, sink=sink)
+        elif ldm:
+            # latents [B, 4, 64, 64], one .npy per seed: the default output of this path (--decode_latents True decodes them)
             import numpy as np
             for seed, z in zip(batch_seeds, images.cpu().numpy()):
                 seed = int(seed)
@@ -539,6 +575,7 @@ if click is not None:
     @click.option('--return_inters', help='Whether to save intermediate outputs', metavar='BOOL', type=bool, default=False)
     @click.option('--use_fp16', help='Whether to use mixed precision', metavar='BOOL', type=bool, default=False)
     @click.option('--batch_invariant', help='Same seed, same bits at any --batch and world size', metavar='BOOL', type=bool, default=False)
+    @click.option('--decode_latents', help='ms_coco: decode the sampled latents with the AutoencoderKL decoder and write PNGs', metavar='BOOL', type=bool, default=False)
     @click.option('--max_order', help='Max order for solvers', metavar='INT', type=click.IntRange(min=1))
     @click.option('--predict_x0', help='Whether to use data prediction mode', metavar='BOOL', type=bool, default=True)
     @click.option('--lower_order_final', help='Whether to lower the order at final stages', metavar='BOOL', type=bool, default=True)

@@ -213,14 +213,16 @@ DS_API int ds_conv2d_nhwc(const ds_conv_args* a, void* stream);
  * embedding path's one-row projections; one fp32 source, bias / scale / SiLU only, cout >= 64; tune.mode != 0 keeps the matrix kernels), 2566 / 2572 =
  * the fp16-activation 3x3 kernel without / with the fused input normalisation (conv3x3_f16dma_kernel), 2567 = the fp16-activation 1x1 / Linear
  * (gemm_f16dma_kernel), 2568 = LDS-halo kernel <4> with 256-pixel x 192-channel tiles, 2569 = the four-wave half-slab fp16-activation 3x3 kernel
- * (tune.f16dma_nw 4, DS_BUILD_EXPERIMENTS builds).  ABI 5: the answer comes from the same routing function as the launch, so for arguments
+ * (tune.f16dma_nw 4, DS_BUILD_EXPERIMENTS builds), 2575 = the fp16-activation 3x3 kernel on 4 x 64 patches for images wider than 64 pixels
+ * (conv3x3_f16wide_kernel: power-of-two sides, one activated fp16 source, no fused normalisation, no appended 1x1 slabs, no split-K; reached only
+ * where 2566 does not apply).  ABI 5: the answer comes from the same routing function as the launch, so for arguments
  * ds_conv2d_nhwc rejects it returns the same negative DS_E_* code (until ABI 4 it answered with a kernel id regardless).  Used by bench.py
  * to attribute time per kernel. */
 DS_API int ds_conv_kernel_id(const ds_conv_args* a);
 
 /* ABI 5: the whole routing decision of a ds_conv2d_nhwc call, without a GPU (host logic only): DS_OK and `info` filled, or the negative DS_E_*
  * code the call would return (info untouched).  f16_groups / f16_widths: the column tiling of the fp16-activation 3x3 kernels (kernel ids
- * 2566 / 2569 / 2572) -- groups of equal tiles, widest first, each width in 64-channel units (320 channels = 3 + 2); 0 groups on every other
+ * 2566 / 2569 / 2572 / 2575) -- groups of equal tiles, widest first, each width in 64-channel units (320 channels = 3 + 2); 0 groups on every other
  * kernel. */
 typedef struct ds_conv_route_info {
     int kernel_id;       /* = ds_conv_kernel_id */
