@@ -9,7 +9,9 @@ network evaluation of the reference, by ~10 hand-written launches per block:
 
 Activations are NHWC fp32 and live in engine-owned workspaces (allocated once per batch size through torch, which
 is only the allocator here); the decoder's ``torch.cat`` is never materialised (both sources are read in place).
-The plan is a list of (C function, prebuilt argument struct): running it is a tight ctypes loop, and because no
+``UNetEngine.plan`` is a short driver: embedding path, then per block ``_block16`` (fp16-activation kernels) or ``_block32`` (fp32 routes)
+up to conv1's arguments, conv1, ``_attention``, and ``_head``; the launches are marshalled by ``plan.Builder``, scratch is preallocated once
+per plan (``_workspaces``).  The plan is a list of (C function, prebuilt argument struct): running it is a tight ctypes loop, and because no
 pointer changes between calls it can be captured in a hipGraph (see ``graph.py``).
 
 ``EDMDenoiser`` is the drop-in for the reference ``net`` object: same call signature and attributes
@@ -20,33 +22,15 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
-from typing import Dict, List
+from types import SimpleNamespace
+from typing import Dict
 
 import torch
 
 from . import _lib, arch
-from ._lib import AttnArgs, DS_ACT_NONE, DS_ACT_SILU, DS_RESAMPLE_NONE, DS_RESAMPLE_DOWN, DS_RESAMPLE_UP
-from .ops import pack_conv_weight, pack_linear_weight, pack_stem_weight
-
-
-from .plan import Builder, Plan as _Plan, ptr as _ptr  # noqa: E402
-
-
-# default of UNetEngine.fuse_norm16: '0' never, '1' every eligible layer, 'auto' the layer classes where the per-layer A/B of round 5 found the
-# fusion faster than pass + convolution (profiles/r5_conv_f16dma_fused_norm_per_layer.txt): 64x64 images and one column tile (cout <= 192).
-# Whole-net A/B of '1' against '0': profiles/r5_conv_f16dma_fused_norm_ab.txt (ImageNet-64 +0.4 %, SD-1.5 -6.8 %).
-FUSE_NORM16_DEFAULT = 'auto'
-
-
-def fuse_norm16_value(text):
-    """'0' / '1' / 'auto' (DS_FUSE_NORM16, or the engines' attribute) -> False / True / 'auto'."""
-    return {'0': False, '1': True}.get(str(text), 'auto')
-
-
-def fuse_norm16_here(mode, side, cout):
-    """Does the 3x3 convolution of this geometry normalise its own LDS halo (conv3x3_f16dma NORM) under `mode`?"""
-    return mode is True or (mode == 'auto' and side == 64 and cout <= 192)
-
+from ._lib import DS_ACT_SILU, DS_RESAMPLE_NONE, DS_RESAMPLE_DOWN, DS_RESAMPLE_UP
+from .ops import pack_conv_weight, pack_conv_weight_f16, pack_conv_weight_split, pack_linear_weight, pack_stem_weight
+from .plan import FUSE_NORM16_DEFAULT, Builder, Plan as _Plan, fuse_norm16_here, fuse_norm16_value, ptr as _ptr
 
 
 class UNetEngine:
@@ -121,12 +105,10 @@ class UNetEngine:
             w[f'{b.name}.conv0.w'] = pack_conv_weight(g(f'{p}.conv0.weight')); w[f'{b.name}.conv0.b'] = g(f'{p}.conv0.bias')
             w[f'{b.name}.conv1.w'] = pack_conv_weight(g(f'{p}.conv1.weight')); w[f'{b.name}.conv1.b'] = g(f'{p}.conv1.bias')
             if self.conv_mode == 1 and b.cin % 64 == 0 and b.cout % 64 == 0:
-                from .ops import pack_conv_weight_f16
                 w[f'{b.name}.conv0.w16'] = (pack_conv_weight_f16(g(f'{p}.conv0.weight')), 0)
                 w[f'{b.name}.conv1.w16'] = (pack_conv_weight_f16(g(f'{p}.conv1.weight'), g(f'{p}.skip.weight') if b.skip_conv else None), 0)
             elif self.conv_mode == 2 and b.cin % 32 == 0 and b.cout % 32 == 0:
                 # ineligible layers (channel counts that are not 32-multiples: tiny / custom nets) keep the exact fp32 kernel
-                from .ops import pack_conv_weight_split
                 w[f'{b.name}.conv0.w16'] = pack_conv_weight_split(g(f'{p}.conv0.weight'))
                 w[f'{b.name}.conv1.w16'] = pack_conv_weight_split(g(f'{p}.conv1.weight'), g(f'{p}.skip.weight') if b.skip_conv else None)
             if b.skip_conv:
@@ -148,7 +130,6 @@ class UNetEngine:
         w['out.g'] = g(f'{m}.{spec.out_norm}.weight'); w['out.b'] = g(f'{m}.{spec.out_norm}.bias')
         w['outc.w'] = pack_conv_weight(g(f'{m}.{spec.out_conv}.weight')); w['outc.b'] = g(f'{m}.{spec.out_conv}.bias')
         if self.conv_mode == 2 and g(f'{m}.{spec.out_conv}.weight').shape[1] % 32 == 0:
-            from .ops import pack_conv_weight_split
             w['outc.w16'] = pack_conv_weight_split(g(f'{m}.{spec.out_conv}.weight'))
         self.w = w
 
@@ -157,328 +138,292 @@ class UNetEngine:
         key = (B, emb_rows, self.fuse_norm16)
         if key in self._plans:
             return self._plans[key]
-        spec, dev, w, lib = self.spec, self.device, self.w, self.lib
-        bd = Builder(dev, conv_mode=self.conv_mode, w16_cache=self._w16_cache,       # owns the plan, its workspaces and the emitters
+        spec, w, lib = self.spec, self.w, self.lib
+        bd = Builder(self.device, conv_mode=self.conv_mode, w16_cache=self._w16_cache,       # owns the plan, its workspaces and the emitters
                      invariant=self.batch_invariant, batch=B)
-        P, new = bd.P, bd.new
-        R = spec.img_resolution
-        Bs = emb_rows
-        E, NC = spec.emb_channels, spec.noise_channels
+        P, new, bufs = bd.P, bd.new, bd.P.bufs
+        R, Bs = spec.img_resolution, emb_rows
         kpad = -(-9 * spec.in_channels // 32) * 32
-        song = spec.model_type == 'SongUNet'
-
-        # ---- inputs / outputs -------------------------------------------------------------------------------
-        bufs = P.bufs
         bufs['x'] = new(B, spec.in_channels, R, R)           # NCHW, un-scaled (c_in is applied by the stem)
         bufs['sigma'] = new(B)                                # per-sample sigma (row 0 only when Bs == 1 and scalar)
-        bufs['sigma_rows'] = torch.zeros(1, dtype=torch.int32, device=dev)
+        bufs['sigma_rows'] = torch.zeros(1, dtype=torch.int32, device=self.device)
         bufs['out'] = new(B, spec.out_channels, R, R)         # raw network output F, channel-planar (NCHW) like the user tensors
         if spec.label_dim:
-            lpad = -(-spec.label_dim // 32) * 32
-            bufs['labels'] = torch.zeros(Bs, lpad, dtype=torch.float32, device=dev)
-
-        # ---- workspace sizing -------------------------------------------------------------------------------
-        max_act = kpad * R * R
-        max_h = 0
-        max_attn = 0
-        max_sc = 0
-        for b in spec.blocks:
-            if b.kind != 'block':
-                max_h = max(max_h, b.cout * b.res_out ** 2)
-                continue
-            hw = b.res_out ** 2
-            max_act = max(max_act, b.cin * hw, b.cout * hw)
-            max_h = max(max_h, b.cout * hw, b.cin * hw)
-            if b.heads:
-                max_attn = max(max_attn, 2 * b.cout * hw)
-                max_sc = max(max_sc, b.heads * hw * hw)
-        act = new(B * max_act)
-        hbuf = new(B * max_h)
-        sres = new(B * max_h)            # resampled skip-path input
-        sproj = new(B * max_h)           # projected skip
-        ncoef = new(B * 3 * max(max(b.cin, b.cout) for b in spec.blocks))      # {mu, A, B} planes of the fused GroupNorm
-        if self.conv_mode == 1:          # fp16 activated tensors: norm0 output, norm1 output, raw copy for the fused skip projection
-            a16_buf, b16_buf, r16_buf, h16_buf = (bd.new16(B * max_act) for _ in range(4))
-        if max_attn:
-            n2 = new(B * max_attn // 2); qk = new(B * max_attn // 2 * 3); ao = new(B * max_attn // 2)
-            if self.conv_mode == 1:
-                n2_16, ao_16, qk_16 = bd.new16(B * max_attn // 2), bd.new16(B * max_attn // 2), bd.new16(B * max_attn // 2 * 3)
-        bufs.update(act=act, hbuf=hbuf, sres=sres, sproj=sproj)
-        # ---- launch emitters: plan.Builder (shared with ldm_engine); thin adapters keep this file's argument names --------------
-        f16_level = bd.f16_level
-        add = bd.add
-
-        def conv(x0, c0, ld0, n, h, wd, wgt, cout, out, out_ld, taps, name, act_=DS_ACT_NONE, **kw):
-            bd.conv(x0, c0, ld0, n, h, wd, wgt, cout, out, out_ld, taps, name, act=act_, **kw)
-
-        def norm(kind, x0, c0, ld0, n, h, wd, name, act_=DS_ACT_NONE, **kw):
-            bd.norm(kind, x0, c0, ld0, n, h, wd, name, act=act_, **kw)
-
-        # ---- embedding path (networks_edm.py:314-324 / :429-439) -----------------------------------------------
-        pos = new(Bs, NC); e0 = new(Bs, E); emb = new(Bs, E); aff = new(Bs, self.aff_total)
-        add(lib.ds_noise_embed, (_ptr(bufs['sigma']), Bs, _ptr(w['freqs']), NC, int(spec.swap_sincos), _ptr(pos), NC), 'noise_embed')
-        if song:
-            src = pos
-            if spec.label_dim:
-                pos2 = new(Bs, NC)
-                conv(bufs['labels'], bufs['labels'].shape[1], bufs['labels'].shape[1], Bs, 1, 1, w['label.w'], NC, pos2, NC, 1,
-                     'map_label', bias=w['label.b'], res=pos, res_ld=NC, emb=True)
-                src = pos2
-            conv(src, NC, NC, Bs, 1, 1, w['map0.w'], E, e0, E, 1, 'map_layer0', bias=w['map0.b'], act_=DS_ACT_SILU, emb=True)
-            conv(e0, E, E, Bs, 1, 1, w['map1.w'], E, emb, E, 1, 'map_layer1', bias=w['map1.b'], act_=DS_ACT_SILU, emb=True)
-        else:
-            conv(pos, NC, NC, Bs, 1, 1, w['map0.w'], E, e0, E, 1, 'map_layer0', bias=w['map0.b'], act_=DS_ACT_SILU, emb=True)
-            lab = None
-            if spec.label_dim:
-                lab = new(Bs, E)
-                conv(bufs['labels'], bufs['labels'].shape[1], bufs['labels'].shape[1], Bs, 1, 1, w['label.w'], E, lab, E, 1,
-                     'map_label', bias=w['label.b'], emb=True)
-            conv(e0, E, E, Bs, 1, 1, w['map1.w'], E, emb, E, 1, 'map_layer1', bias=w['map1.b'], res=lab, res_ld=E,
-                 act_=DS_ACT_SILU, emb=True)
-        conv(emb, E, E, Bs, 1, 1, w['aff.w'], self.aff_total, aff, self.aff_total, 1, 'affine_all', bias=w['aff.b'], emb=True)
-        bufs.update(emb=emb, aff=aff)
-
+            bufs['labels'] = torch.zeros(Bs, -(-spec.label_dim // 32) * 32, dtype=torch.float32, device=self.device)
+        ws = self._workspaces(bd, B, Bs, kpad)
+        ws.aff = self._embedding(bd, Bs)
         # ---- fp16 residual stream -------------------------------------------------------------------------------
         # The reference's fp16 mode keeps EVERY activation of the U-Net body in fp16 (networks_edm.py:486 `x.to(dtype)`, :165-179 run in
         # that dtype): when every block of this plan runs on the fp16-activation kernels, block outputs (the residual stream, the skip
         # stack) are stored as fp16 rows too -- half the bytes of every epilogue and normalisation pass.  Arithmetic on them is fp32
         # (values are widened when loaded).  Otherwise the stream stays fp32 (the mixed layout of smaller / unusual geometries).
-        def dma16_ok(b):
-            if self.conv_mode != 1 or w.get(f'{b.name}.conv0.w16') is None or w.get(f'{b.name}.conv1.w16') is None:
-                return False
-            Ho, M_ = b.res_out, B * b.res_out ** 2
-            if not (lib.ds_conv_f16dma_supported(B, Ho, Ho, b.cin, 0, b.cout)
-                    and lib.ds_conv_f16dma_supported(B, Ho, Ho, b.cout, b.cin if b.skip_conv else 0, b.cout)):
-                return False
-            return True
-
-        def attn16_ok(b):          # attention block on the fp16 kernels end to end (CIFAR-10's single 256-wide head is not: fp32 kernel)
-            M_ = B * b.res_out ** 2
-            return bool(self.conv_mode == 1 and lib.ds_attention_f16_supported(b.cout // b.heads)
-                        and lib.ds_gemm_f16dma_supported(M_, b.cout, 3 * b.cout) and lib.ds_gemm_f16dma_supported(M_, b.cout, b.cout))
-        stream16 = self.conv_mode == 1 and all(dma16_ok(b) for b in spec.blocks if b.kind == 'block')
-        P.stream16 = stream16
-        # a block whose attention runs on the fp32 kernels keeps fp32 outputs; every consumer reads a tensor in the dtype it has
-        blk16 = lambda b: stream16 and (not b.heads or attn16_ok(b))
+        P.stream16 = ws.stream16 = self.conv_mode == 1 and all(self._dma16(bd, B, b) for b in spec.blocks if b.kind == 'block')
         P.f16_views = []          # (address, bytes) of fp32-typed storage that some launches use as fp16 rows (tests/test_plan_cpu.py's dtype lint)
-
-        def as16(t):              # decoder ping-pong storage viewed as fp16 rows
-            P.f16_views.append((t.data_ptr(), t.numel() * 2))
-            return t.view(torch.float16)[:t.numel()]
-
-        # ---- stem ---------------------------------------------------------------------------------------------
-        x_cur = None          # (tensor, channels)
-        skips: List[tuple] = []
-        dec_pp = [None, None]
-        dec_i = 0
+        x_cur, skips = None, []
         for b in spec.blocks:
-            n, Hin, Ho = B, b.res_in, b.res_out
-            M = B * Ho * Ho
+            nm, Ho, cout = b.name, b.res_out, b.cout
             if b.kind == 'conv':
-                add(lib.ds_stem_im2col, (_ptr(bufs['x']), _ptr(bufs['sigma']), Bs, spec.sigma_data, B, spec.in_channels, R, R,
-                                         _ptr(act), kpad), 'stem_im2col')
-                out = new(M, b.cout)
-                conv(act, kpad, kpad, B, R, R, w[f'{b.name}.w'], b.cout, out, b.cout, 1, b.name, bias=w[f'{b.name}.b'], stats=True)
-                x_cur = (out, b.cout)
-                skips.append(x_cur)
-                bufs[b.name] = out
-                continue
-            # sources of this block's input
-            x0, c0 = x_cur
-            x1, c1 = (None, 0)
-            if b.pops_skip:
-                x1, c1 = skips.pop()
-                assert c1 == b.skip_cin and c0 + c1 == b.cin
-            cin, cout = b.cin, b.cout
-            G_in, G_out = arch.num_groups(cin), arch.num_groups(cout)
-            rs = DS_RESAMPLE_DOWN if b.down else (DS_RESAMPLE_UP if b.up else DS_RESAMPLE_NONE)
-            nm = b.name
-            fuse = bool(lib.ds_conv3x3_halo_supported(Ho, Ho))     # GroupNorm+SiLU applied by the conv's halo loader
-            w16_0, w16_1 = w.get(f'{nm}.conv0.w16'), w.get(f'{nm}.conv1.w16')
-            if w16_0 is not None and f16_level(n, Ho, Ho, cin, 0, 0, 0) == 1:
-                fuse = False        # fp16 operands without the fused normalisation (8x8: four images per tile): normalise in a pass
-            aoff = self.aff_off[nm]
-            cb = dict(cbias=aff[:, aoff:], cbias_ld=self.aff_total, cbias_rows=Bs) if not b.adaptive_scale else {}
-            # fp16 mode, the reference's storage (networks_edm.py:486 runs the body on x.to(float16)): norm + SiLU (+ resample, + the
-            # decoder's concatenation) are ONE pass that writes the activated tensor in fp16, and the convolution is a pure matrix
-            # kernel on fp16 activations (csrc/conv3x3_f16dma.hip).  Norm arithmetic is fp32; the block output is fp16 under `stream16`.
-            dma16 = (w16_0 is not None and w16_1 is not None and self.conv_mode == 1
-                     and lib.ds_conv_f16dma_supported(n, Ho, Ho, cin, 0, cout)
-                     and lib.ds_conv_f16dma_supported(n, Ho, Ho, cout, cin if b.skip_conv else 0, cout))
-            if dma16:
-                a16, b16 = a16_buf[:M * cin].view(M, cin), b16_buf[:M * cout].view(M, cout)
-                h16 = h16_buf[:M * cout].view(M, cout)       # conv0 output: only read by norm1 -> stored in fp16 (networks_edm.py:486)
-                # raw (un-normalised) fp16 copy of the block input: operand of the fused 1x1 skip projection, and -- fp16 stream -- the
-                # resampled identity skip.  Not needed when the input already is one fp16 tensor of the right geometry.
-                direct = stream16 and x1 is None and rs == DS_RESAMPLE_NONE and x0.dtype == torch.float16
-                need_raw = (b.skip_conv and not direct) or (stream16 and not b.skip_conv and rs != DS_RESAMPLE_NONE)
-                r16 = r16_buf[:M * cin].view(M, cin) if need_raw else None
-                # Round 5, `fuse_norm16`: where every source of a convolution is a raw fp16 tensor of the layer's own geometry, the GroupNorm
-                # affine + SiLU is applied by the convolution itself to its LDS halo (conv3x3_f16dma NORM: same arithmetic, same bits) and the
-                # ds_norm_act pass -- with it the materialised concatenation and the raw copy for the skip projection -- disappears; the
-                # statistics launch (ds_gn_finalize over the producers' column sums) stays.  Resampling blocks keep the pass for conv0.
-                raw16 = lambda t: t is None or t.dtype == torch.float16
-                fz_here = fuse_norm16_here(self.fuse_norm16, Ho, cout)
-                fz0 = bool(fz_here and stream16 and rs == DS_RESAMPLE_NONE and raw16(x0) and raw16(x1) and c0 % 64 == 0 and c1 % 64 == 0)
-                fz1 = bool(fz_here and stream16)
-                norm('stats', x0, c0, c0, n, Hin, Hin, nm + '.norm0.stats', x1=x1, c1=c1, ld1=c1, groups=G_in, eps=b.eps,
-                     gamma=w[f'{nm}.norm0.g'], beta=w[f'{nm}.norm0.b'], coefs=ncoef)
-                if fz0:
-                    r16 = None
-                    conv(x0, c0, c0, n, Ho, Ho, w[f'{nm}.conv0.w'], cout, h16, cout, 9, nm + '.conv0', x1=x1, c1=c1, ld1=c1,
-                         bias=w[f'{nm}.conv0.b'], stats=True, w16=w16_0, in_f16=True, out_f16=True, norm_coefs=ncoef, norm_act=DS_ACT_SILU, **cb)
-                else:
-                    norm('apply', x0, c0, c0, n, Hin, Hin, nm + '.norm0', x1=x1, c1=c1, ld1=c1, groups=G_in, eps=b.eps, use_stats=False,
-                         act_=DS_ACT_SILU, resample=rs, out=a16, out_ld=cin, out_f16=True, raw_out=r16, raw_ld=cin, coefs=ncoef)
-                    conv(a16, cin, cin, n, Ho, Ho, w[f'{nm}.conv0.w'], cout, h16, cout, 9, nm + '.conv0', bias=w[f'{nm}.conv0.b'], stats=True,
-                         w16=w16_0, in_f16=True, out_f16=True, **cb)
-                ss = dict(scale=aff[:, aoff:], shift=aff[:, aoff + cout:], ss_ld=self.aff_total, ss_rows=Bs) if b.adaptive_scale else {}
-                norm('stats', h16, cout, cout, n, Ho, Ho, nm + '.norm1.stats', groups=G_out, eps=b.eps, gamma=w[f'{nm}.norm1.g'],
-                     beta=w[f'{nm}.norm1.b'], coefs=ncoef, **ss)             # from conv0's epilogue sums (fp32), incl. the adaptive scale / shift
-                if not fz1:
-                    norm('apply', h16, cout, cout, n, Ho, Ho, nm + '.norm1', groups=G_out, eps=b.eps, use_stats=False, act_=DS_ACT_SILU,
-                         out=b16, out_ld=cout, out_f16=True, in_f16=True, coefs=ncoef)
-                if b.skip_conv:          # 1x1 skip projection fused into conv1 as extra K columns on the raw (resampled) fp16 input
-                    c1_w, c1_b = w[f'{nm}.conv1s.w'], w[f'{nm}.conv1s.b']
-                    if fz0 and fz1:      # both raw sources straight from the stream: nothing was copied
-                        c1_skip = dict(e0=x0, ec0=c0, e1=x1, ec1=c1)
-                    else:
-                        c1_skip = dict(e0=x0 if direct else r16, ec0=cin)
-                elif stream16 and rs != DS_RESAMPLE_NONE:
-                    c1_w, c1_b = w[f'{nm}.conv1.w'], w[f'{nm}.conv1.b']
-                    c1_skip = dict(res=r16, res_ld=cout)          # resampled raw input, already written by the norm0 pass
-                else:
-                    s0 = x0
-                    if rs != DS_RESAMPLE_NONE:
-                        norm('apply', x0, c0, c0, n, Hin, Hin, nm + '.skip.resample', x1=x1, c1=c1, ld1=c1, use_stats=False,
-                             resample=rs, out=sres, out_ld=cin)
-                        s0 = sres
-                    assert x1 is None and c0 == cout
-                    c1_w, c1_b = w[f'{nm}.conv1.w'], w[f'{nm}.conv1.b']
-                    c1_skip = dict(res=s0, res_ld=cout)
-                if fz1:
-                    c1_in, c1_norm = h16, dict(in_f16=True, norm_coefs=ncoef, norm_act=DS_ACT_SILU)
-                else:
-                    c1_in, c1_norm = b16, dict(in_f16=True)
-            # norm0 + silu (+resample) -> conv0 (+bias, + per-image embedding for the non-adaptive variant)
-            elif fuse and rs == DS_RESAMPLE_NONE:
-                norm('stats', x0, c0, c0, n, Hin, Hin, nm + '.norm0.stats', x1=x1, c1=c1, ld1=c1, groups=G_in, eps=b.eps,
-                     gamma=w[f'{nm}.norm0.g'], beta=w[f'{nm}.norm0.b'], coefs=ncoef)
-                conv(x0, c0, c0, n, Ho, Ho, w[f'{nm}.conv0.w'], cout, hbuf, cout, 9, nm + '.conv0', x1=x1, c1=c1, ld1=c1,
-                     bias=w[f'{nm}.conv0.b'], norm_coefs=ncoef, norm_act=DS_ACT_SILU, stats=True, w16=w16_0, **cb)
+                bd.add(lib.ds_stem_im2col, (_ptr(bufs['x']), _ptr(bufs['sigma']), Bs, spec.sigma_data, B, spec.in_channels, R, R,
+                                            _ptr(ws.act), kpad), 'stem_im2col')
+                out = new(B * Ho * Ho, cout)
+                bd.conv(ws.act, kpad, kpad, B, R, R, w[f'{nm}.w'], cout, out, cout, 1, nm, bias=w[f'{nm}.b'], stats=True)
             else:
-                norm('stats', x0, c0, c0, n, Hin, Hin, nm + '.norm0.stats', x1=x1, c1=c1, ld1=c1, groups=G_in, eps=b.eps)
-                norm('apply', x0, c0, c0, n, Hin, Hin, nm + '.norm0', x1=x1, c1=c1, ld1=c1, groups=G_in, eps=b.eps,
-                     gamma=w[f'{nm}.norm0.g'], beta=w[f'{nm}.norm0.b'], act_=DS_ACT_SILU, resample=rs, out=act, out_ld=cin)
-                conv(act, cin, cin, n, Ho, Ho, w[f'{nm}.conv0.w'], cout, hbuf, cout, 9, nm + '.conv0', bias=w[f'{nm}.conv0.b'], stats=True,
-                     w16=w16_0, **cb)
-            # norm1 (+adaptive scale/shift) + silu
-            ss = dict(scale=aff[:, aoff:], shift=aff[:, aoff + cout:], ss_ld=self.aff_total, ss_rows=Bs) if b.adaptive_scale else {}
-            if dma16:
-                pass
-            elif fuse:
-                norm('stats', hbuf, cout, cout, n, Ho, Ho, nm + '.norm1.stats', groups=G_out, eps=b.eps, gamma=w[f'{nm}.norm1.g'],
-                     beta=w[f'{nm}.norm1.b'], coefs=ncoef, **ss)
-                c1_in, c1_norm = hbuf, dict(norm_coefs=ncoef, norm_act=DS_ACT_SILU)
-            else:
-                norm('stats', hbuf, cout, cout, n, Ho, Ho, nm + '.norm1.stats', groups=G_out, eps=b.eps)
-                norm('apply', hbuf, cout, cout, n, Ho, Ho, nm + '.norm1', groups=G_out, eps=b.eps, gamma=w[f'{nm}.norm1.g'],
-                     beta=w[f'{nm}.norm1.b'], act_=DS_ACT_SILU, out=act, out_ld=cout, **ss)
-                c1_in, c1_norm = act, {}
-            # skip path: raw (resampled) input, projected by a 1x1 that is fused into conv1 as extra K columns
-            s0, sc0, s1, sc1 = x0, c0, x1, c1
-            if dma16:
-                pass
-            elif rs != DS_RESAMPLE_NONE:
-                norm('apply', x0, c0, c0, n, Hin, Hin, nm + '.skip.resample', x1=x1, c1=c1, ld1=c1, use_stats=False,
-                     resample=rs, out=sres, out_ld=cin)
-                s0, sc0, s1, sc1 = sres, cin, None, 0
-            if dma16:
-                pass
-            elif b.skip_conv:
-                c1_w, c1_b = w[f'{nm}.conv1s.w'], w[f'{nm}.conv1s.b']
-                c1_skip = dict(e0=s0, ec0=sc0, e1=s1, ec1=sc1)
-            else:
-                assert s1 is None and sc0 == cout
-                c1_w, c1_b = w[f'{nm}.conv1.w'], w[f'{nm}.conv1.b']
-                c1_skip = dict(res=s0, res_ld=cout)
-            # output buffer: encoder outputs are kept for the skip stack, decoder outputs ping-pong
-            f16_out = blk16(b)
-            if b.pushes_skip:
-                out = bd.new16(M, cout) if f16_out else new(M, cout)
-            else:
-                if dec_pp[dec_i] is None or dec_pp[dec_i].numel() < M * cout:
-                    dec_pp[dec_i] = new(B * max_h)
-                out = as16(dec_pp[dec_i]) if f16_out else dec_pp[dec_i]
-                dec_i ^= 1
-            if b.heads:
-                mid = out
-                out2 = None
-            conv(c1_in, cout, cout, n, Ho, Ho, c1_w, cout, out, cout, 9, nm + '.conv1', bias=c1_b, scale=b.skip_scale, stats=True,
-                 w16=w16_1, **c1_norm, **c1_skip)
-            if b.heads:
-                S = Ho * Ho
-                hd = b.heads
-                ch = cout // hd
-                f16_attn = self.conv_mode == 1 and lib.ds_attention_f16_supported(ch)     # networks_edm.py:98-110 with fp16 q / k / v
-                # fp16 mode: the GroupNorm output and the attention output are only operands of the qkv / proj 1x1s -> fp16 rows,
-                # streamed by the fp16-activation GEMM (csrc/gemm_f16dma.hip)
-                a16 = bool(f16_attn and lib.ds_gemm_f16dma_supported(M, cout, 3 * cout) and lib.ds_gemm_f16dma_supported(M, cout, cout))
-                n2_, ao_ = (n2_16[:M * cout].view(M, cout), ao_16[:M * cout].view(M, cout)) if a16 else (n2, ao)
-                norm('stats', out, cout, cout, n, Ho, Ho, nm + '.norm2.stats', groups=G_out, eps=b.eps)
-                norm('apply', out, cout, cout, n, Ho, Ho, nm + '.norm2', groups=G_out, eps=b.eps, gamma=w[f'{nm}.norm2.g'],
-                     beta=w[f'{nm}.norm2.b'], out=n2_, out_ld=cout, out_f16=a16)
-                qk_ = qk_16 if a16 else qk          # fp16 mode: q | k | v are the fp16 rows the reference's qkv projection emits (networks_edm.py:171-173)
-                conv(n2_, cout, cout, n, Ho, Ho, w[f'{nm}.qkv.w'], 3 * cout, qk_, 3 * cout, 1, nm + '.qkv', bias=w[f'{nm}.qkv.b'])
-                # softmax(Q K^T / sqrt(ch)) V per (image, head), scores kept on chip (networks_edm.py:171-176)
-                at = AttnArgs(_ptr(qk_), _ptr(qk_[cout:]), _ptr(qk_[2 * cout:]), _ptr(ao_), 3 * cout, 3 * cout, 3 * cout, cout,
-                              S * 3 * cout, S * 3 * cout, S * 3 * cout, S * cout, B, hd, S, S, ch, 1.0 / math.sqrt(ch))
-                at.out_f16 = 1 if a16 else 0
-                at.in_f16 = 3 if a16 else 0
-                if self.batch_invariant and not f16_attn and ch % 128 == 0:
-                    at.variant = 2          # invariant: the channel-split block at every batch (ds_attention_variant)
-                add(lib.ds_attention_f16 if f16_attn else lib.ds_attention, (C.byref(at),), nm + '.attention', keep=(at,))
-                if b.pushes_skip:
-                    out2 = bd.new16(M, cout) if f16_out else new(M, cout)
-                else:
-                    if dec_pp[dec_i] is None:
-                        dec_pp[dec_i] = new(B * max_h)
-                    out2 = as16(dec_pp[dec_i]) if f16_out else dec_pp[dec_i]
-                    dec_i ^= 1
-                conv(ao_, cout, cout, n, Ho, Ho, w[f'{nm}.proj.w'], cout, out2, cout, 1, nm + '.proj', bias=w[f'{nm}.proj.b'],
-                     res=out, res_ld=cout, scale=b.skip_scale, stats=True)
-                out = out2
+                x0, c0 = x_cur
+                x1, c1 = (None, 0)
+                if b.pops_skip:
+                    x1, c1 = skips.pop()
+                    assert c1 == b.skip_cin and c0 + c1 == b.cin
+                # a block whose attention runs on the fp32 kernels keeps fp32 outputs; every consumer reads a tensor in the dtype it has
+                f16_out = ws.stream16 and (not b.heads or self._attn16(B, b))
+                block = self._block16 if self._dma16(bd, B, b) else self._block32
+                c1_in, c1_w, c1_kw = block(bd, ws, b, x0, c0, x1, c1)
+                out = self._block_out(bd, ws, b, f16_out)
+                bd.conv(c1_in, cout, cout, B, Ho, Ho, c1_w, cout, out, cout, 9, nm + '.conv1', scale=b.skip_scale, stats=True,
+                        w16=w.get(f'{nm}.conv1.w16'), **c1_kw)
+                if b.heads:
+                    out = self._attention(bd, ws, b, out, f16_out)
             x_cur = (out, cout)
             bufs[nm] = out
-            if b.pushes_skip:
+            if b.kind == 'conv' or b.pushes_skip:
                 skips.append(x_cur)
         assert not skips
-        # ---- output head ------------------------------------------------------------------------------------------
-        xo, co = x_cur
-        if lib.ds_conv3x3_halo_supported(R, R) and xo.dtype == torch.float32:
-            norm('stats', xo, co, co, B, R, R, 'out.norm.stats', groups=arch.num_groups(co), eps=spec.out_eps, gamma=w['out.g'],
-                 beta=w['out.b'], coefs=ncoef)
-            conv(xo, co, co, B, R, R, w['outc.w'], spec.out_channels, bufs['out'], 4, 9, 'out.conv', bias=w['outc.b'],
-                 norm_coefs=ncoef, norm_act=DS_ACT_SILU, out_nchw=1, w16=w.get('outc.w16'))
-        else:
-            norm('stats', xo, co, co, B, R, R, 'out.norm.stats', groups=arch.num_groups(co), eps=spec.out_eps)
-            norm('apply', xo, co, co, B, R, R, 'out.norm', groups=arch.num_groups(co), eps=spec.out_eps, gamma=w['out.g'],
-                 beta=w['out.b'], act_=DS_ACT_SILU, out=act, out_ld=co)
-            conv(act, co, co, B, R, R, w['outc.w'], spec.out_channels, bufs['out'], 4, 9, 'out.conv', bias=w['outc.b'], out_nchw=1)
-        # ---- the solver update fused into the head (round 5, ds_conv_args.update): the head launch carries a pointer to ONE persistent
-        # ds_update_args of this plan; EDMDenoiser.raw(update=...) fills it before a run and clears its outputs afterwards (x_out == m_out ==
-        # NULL = plain head).  Possible where the head runs on conv3x3_thin_kernel with a channel-planar output (ds_conv_kernel_id 2570).
-        last = P.ops[-1]
-        head = last.keep[0] if (last.fn is lib.ds_conv2d_nhwc and last.keep) else None         # the last launch IS the head convolution
-        P.head_update = _lib.UpdateArgs()
-        P.head_fusable = bool(head is not None and head.out_nchw and not head.wgt_f16 and lib.ds_conv_kernel_id(C.byref(head)) == 2570)
-        if P.head_fusable:
-            head.update = C.cast(C.pointer(P.head_update), C.c_void_p)
-        from .plan import release_tuning_scratch
-        release_tuning_scratch()            # the tile measurement's 512 MiB flush buffer does not outlive the plan build
-        self._plans[key] = P
+        self._head(bd, ws, *x_cur)
+        self._plans[key] = bd.finish()
         return P
 
+    def _workspaces(self, bd, B, Bs, kpad):
+        """The scratch every block of a plan shares (launches are serial), sized for the largest layer and allocated once."""
+        spec, new = self.spec, bd.new
+        max_act, max_h, max_attn = kpad * spec.img_resolution ** 2, 0, 0
+        for b in spec.blocks:
+            hw = b.res_out ** 2
+            max_h = max(max_h, b.cout * hw)
+            if b.kind == 'block':
+                max_act = max(max_act, b.cin * hw, b.cout * hw)
+                max_h = max(max_h, b.cin * hw)
+                if b.heads:
+                    max_attn = max(max_attn, 2 * b.cout * hw)
+        ws = SimpleNamespace(B=B, Bs=Bs, max_h=max_h, dec_pp=[None, None], dec_i=0)
+        ws.act, ws.hbuf = new(B * max_act), new(B * max_h)
+        ws.sres = new(B * max_h)            # resampled skip-path input
+        ws.sproj = new(B * max_h)           # projected skip
+        bd.coefs = new(B * 3 * max(max(b.cin, b.cout) for b in spec.blocks))      # {mu, A, B} planes of the fused GroupNorm
+        if self.conv_mode == 1:          # fp16 activated tensors: norm0 output, norm1 output, raw copy for the fused skip projection, conv0 output
+            ws.a16, ws.b16, ws.r16, ws.h16 = (bd.new16(B * max_act) for _ in range(4))
+        if max_attn:
+            ws.n2, ws.qk, ws.ao = new(B * max_attn // 2), new(B * max_attn // 2 * 3), new(B * max_attn // 2)
+            if self.conv_mode == 1:
+                ws.n2_16, ws.ao_16, ws.qk_16 = bd.new16(B * max_attn // 2), bd.new16(B * max_attn // 2), bd.new16(B * max_attn // 2 * 3)
+        bd.P.bufs.update(act=ws.act, hbuf=ws.hbuf, sres=ws.sres, sproj=ws.sproj)
+        return ws
+
+    def _embedding(self, bd, Bs):
+        """Embedding path (networks_edm.py:314-324 / :429-439) and every block's affine layer in one GEMM; returns its output [Bs, aff_total]."""
+        spec, w, new, bufs = self.spec, self.w, bd.new, bd.P.bufs
+        E, NC = spec.emb_channels, spec.noise_channels
+        pos, e0, emb, aff = new(Bs, NC), new(Bs, E), new(Bs, E), new(Bs, self.aff_total)
+        lab = bufs.get('labels')
+        lpad = lab.shape[1] if lab is not None else 0
+        bd.add(self.lib.ds_noise_embed, (_ptr(bufs['sigma']), Bs, _ptr(w['freqs']), NC, int(spec.swap_sincos), _ptr(pos), NC), 'noise_embed')
+        if spec.model_type == 'SongUNet':
+            src = pos
+            if lab is not None:
+                src = new(Bs, NC)
+                bd.linear(lab, lpad, Bs, w['label.w'], NC, src, 'map_label', bias=w['label.b'], res=pos, res_ld=NC, emb=True)
+            bd.linear(src, NC, Bs, w['map0.w'], E, e0, 'map_layer0', bias=w['map0.b'], act=DS_ACT_SILU, emb=True)
+            bd.linear(e0, E, Bs, w['map1.w'], E, emb, 'map_layer1', bias=w['map1.b'], act=DS_ACT_SILU, emb=True)
+        else:
+            bd.linear(pos, NC, Bs, w['map0.w'], E, e0, 'map_layer0', bias=w['map0.b'], act=DS_ACT_SILU, emb=True)
+            lab_e = None
+            if lab is not None:
+                lab_e = new(Bs, E)
+                bd.linear(lab, lpad, Bs, w['label.w'], E, lab_e, 'map_label', bias=w['label.b'], emb=True)
+            bd.linear(e0, E, Bs, w['map1.w'], E, emb, 'map_layer1', bias=w['map1.b'], res=lab_e, res_ld=E, act=DS_ACT_SILU, emb=True)
+        bd.linear(emb, E, Bs, w['aff.w'], self.aff_total, aff, 'affine_all', bias=w['aff.b'], emb=True)
+        bufs.update(emb=emb, aff=aff)
+        return aff
+
+    def _dma16(self, bd, B, b):
+        """Do both 3x3 convolutions of the block run on the fp16-activation kernels (conv1 with the fused skip projection's columns)?"""
+        return bool(bd.f16_conv_ok(B, b.res_out, b.cin, 0, b.cout) and bd.f16_conv_ok(B, b.res_out, b.cout, b.cin if b.skip_conv else 0, b.cout))
+
+    def _attn16(self, B, b):
+        """Attention block on the fp16 kernels end to end (CIFAR-10's single 256-wide head is not: fp32 kernel)?"""
+        M, lib = B * b.res_out ** 2, self.lib
+        return bool(self.conv_mode == 1 and lib.ds_attention_f16_supported(b.cout // b.heads)
+                    and lib.ds_gemm_f16dma_supported(M, b.cout, 3 * b.cout) and lib.ds_gemm_f16dma_supported(M, b.cout, b.cout))
+
+    def _emb_kw(self, ws, b):
+        """(conv0's per-image embedding bias, norm1's adaptive scale / shift) of a block: one of the two is empty."""
+        off = self.aff_off[b.name]
+        if b.adaptive_scale:
+            return {}, dict(scale=ws.aff[:, off:], shift=ws.aff[:, off + b.cout:], ss_ld=self.aff_total, ss_rows=ws.Bs)
+        return dict(cbias=ws.aff[:, off:], cbias_ld=self.aff_total, cbias_rows=ws.Bs), {}
+
+    def _block16(self, bd, ws, b, x0, c0, x1, c1):
+        """norm0 .. norm1 of a block on the fp16-activation kernels; returns (input, weights, keywords) of its conv1.
+        fp16 mode, the reference's storage (networks_edm.py:486 runs the body on x.to(float16)): norm + SiLU (+ resample, + the decoder's
+        concatenation) are ONE pass that writes the activated tensor in fp16, and the convolution is a pure matrix kernel on fp16
+        activations (csrc/conv3x3_f16dma.hip).  Norm arithmetic is fp32; the block output is fp16 under `stream16`."""
+        w, nm, n, Hin, Ho, cin, cout, ncoef = self.w, b.name, ws.B, b.res_in, b.res_out, b.cin, b.cout, bd.coefs
+        M = n * Ho * Ho
+        G_in, G_out = arch.num_groups(cin), arch.num_groups(cout)
+        rs = DS_RESAMPLE_DOWN if b.down else (DS_RESAMPLE_UP if b.up else DS_RESAMPLE_NONE)
+        cb, ss = self._emb_kw(ws, b)
+        a16, b16 = ws.a16[:M * cin].view(M, cin), ws.b16[:M * cout].view(M, cout)
+        h16 = ws.h16[:M * cout].view(M, cout)       # conv0 output: only read by norm1 -> stored in fp16 (networks_edm.py:486)
+        # raw (un-normalised) fp16 copy of the block input: operand of the fused 1x1 skip projection, and -- fp16 stream -- the
+        # resampled identity skip.  Not needed when the input already is one fp16 tensor of the right geometry.
+        direct = ws.stream16 and x1 is None and rs == DS_RESAMPLE_NONE and x0.dtype == torch.float16
+        need_raw = (b.skip_conv and not direct) or (ws.stream16 and not b.skip_conv and rs != DS_RESAMPLE_NONE)
+        r16 = ws.r16[:M * cin].view(M, cin) if need_raw else None
+        # `fuse_norm16`: where every source of a convolution is a raw fp16 tensor of the layer's own geometry, the GroupNorm affine + SiLU
+        # is applied by the convolution itself to its LDS halo (conv3x3_f16dma NORM: same arithmetic, same bits) and the ds_norm_act pass
+        # -- with it the materialised concatenation and the raw copy for the skip projection -- disappears; the statistics launch
+        # (ds_gn_finalize over the producers' column sums) stays.  Resampling blocks keep the pass for conv0.
+        fz0 = bool(ws.stream16 and rs == DS_RESAMPLE_NONE and bd.fuses_norm16(self.fuse_norm16, Ho, cout, x0, c0, x1, c1))
+        fz1 = bool(ws.stream16 and bd.fuses_norm16(self.fuse_norm16, Ho, cout, h16, cout))
+        conv0 = dict(bias=w[f'{nm}.conv0.b'], stats=True, w16=w[f'{nm}.conv0.w16'], in_f16=True, out_f16=True, **cb)
+        bd.norm('stats', x0, c0, c0, n, Hin, Hin, nm + '.norm0.stats', x1=x1, c1=c1, ld1=c1, groups=G_in, eps=b.eps,
+                gamma=w[f'{nm}.norm0.g'], beta=w[f'{nm}.norm0.b'], coefs=ncoef)
+        if fz0:
+            r16 = None
+            bd.conv(x0, c0, c0, n, Ho, Ho, w[f'{nm}.conv0.w'], cout, h16, cout, 9, nm + '.conv0', x1=x1, c1=c1, ld1=c1, norm_coefs=ncoef,
+                    norm_act=DS_ACT_SILU, **conv0)
+        else:
+            bd.norm('apply', x0, c0, c0, n, Hin, Hin, nm + '.norm0', x1=x1, c1=c1, ld1=c1, groups=G_in, eps=b.eps, use_stats=False,
+                    act=DS_ACT_SILU, resample=rs, out=a16, out_ld=cin, out_f16=True, raw_out=r16, raw_ld=cin, coefs=ncoef)
+            bd.conv(a16, cin, cin, n, Ho, Ho, w[f'{nm}.conv0.w'], cout, h16, cout, 9, nm + '.conv0', **conv0)
+        bd.norm('stats', h16, cout, cout, n, Ho, Ho, nm + '.norm1.stats', groups=G_out, eps=b.eps, gamma=w[f'{nm}.norm1.g'],
+                beta=w[f'{nm}.norm1.b'], coefs=ncoef, **ss)             # from conv0's epilogue sums (fp32), incl. the adaptive scale / shift
+        if fz1:
+            c1_in, kw = h16, dict(in_f16=True, norm_coefs=ncoef, norm_act=DS_ACT_SILU)
+        else:
+            bd.norm('apply', h16, cout, cout, n, Ho, Ho, nm + '.norm1', groups=G_out, eps=b.eps, use_stats=False, act=DS_ACT_SILU,
+                    out=b16, out_ld=cout, out_f16=True, in_f16=True, coefs=ncoef)
+            c1_in, kw = b16, dict(in_f16=True)
+        if b.skip_conv:          # 1x1 skip projection fused into conv1 as extra K columns on the raw (resampled) fp16 input
+            if fz0 and fz1:      # both raw sources straight from the stream: nothing was copied
+                kw.update(e0=x0, ec0=c0, e1=x1, ec1=c1)
+            else:
+                kw.update(e0=x0 if direct else r16, ec0=cin)
+            return c1_in, w[f'{nm}.conv1s.w'], dict(kw, bias=w[f'{nm}.conv1s.b'])
+        if ws.stream16 and rs != DS_RESAMPLE_NONE:
+            kw.update(res=r16, res_ld=cout)          # resampled raw input, already written by the norm0 pass
+        else:
+            s0 = x0
+            if rs != DS_RESAMPLE_NONE:
+                bd.norm('apply', x0, c0, c0, n, Hin, Hin, nm + '.skip.resample', x1=x1, c1=c1, ld1=c1, use_stats=False,
+                        resample=rs, out=ws.sres, out_ld=cin)
+                s0 = ws.sres
+            assert x1 is None and c0 == cout
+            kw.update(res=s0, res_ld=cout)
+        return c1_in, w[f'{nm}.conv1.w'], dict(kw, bias=w[f'{nm}.conv1.b'])
+
+    def _block32(self, bd, ws, b, x0, c0, x1, c1):
+        """norm0 .. norm1 and the skip path of a block on fp32 activations; returns (input, weights, keywords) of its conv1.  GroupNorm +
+        SiLU ride in the 3x3 convolution's halo loader where the LDS-halo kernel takes the shape, else they are a pass (always for a
+        resampling norm0)."""
+        w, nm, n, Hin, Ho, cin, cout, ncoef = self.w, b.name, ws.B, b.res_in, b.res_out, b.cin, b.cout, bd.coefs
+        G_in, G_out = arch.num_groups(cin), arch.num_groups(cout)
+        rs = DS_RESAMPLE_DOWN if b.down else (DS_RESAMPLE_UP if b.up else DS_RESAMPLE_NONE)
+        cb, ss = self._emb_kw(ws, b)
+        src = dict(x1=x1, c1=c1, ld1=c1)
+        w16_0 = w.get(f'{nm}.conv0.w16')
+        fuse = bool(self.lib.ds_conv3x3_halo_supported(Ho, Ho))     # GroupNorm+SiLU applied by the conv's halo loader
+        if w16_0 is not None and bd.f16_level(n, Ho, Ho, cin, 0, 0, 0) == 1:
+            fuse = False        # fp16 operands without the fused normalisation (8x8: four images per tile): normalise in a pass
+        conv0 = dict(bias=w[f'{nm}.conv0.b'], stats=True, w16=w16_0, **cb)      # (+ per-image embedding for the non-adaptive variant)
+        if fuse and rs == DS_RESAMPLE_NONE:
+            bd.norm('stats', x0, c0, c0, n, Hin, Hin, nm + '.norm0.stats', groups=G_in, eps=b.eps, gamma=w[f'{nm}.norm0.g'],
+                    beta=w[f'{nm}.norm0.b'], coefs=ncoef, **src)
+            bd.conv(x0, c0, c0, n, Ho, Ho, w[f'{nm}.conv0.w'], cout, ws.hbuf, cout, 9, nm + '.conv0', norm_coefs=ncoef, norm_act=DS_ACT_SILU,
+                    **src, **conv0)
+        else:
+            bd.norm('stats', x0, c0, c0, n, Hin, Hin, nm + '.norm0.stats', groups=G_in, eps=b.eps, **src)
+            bd.norm('apply', x0, c0, c0, n, Hin, Hin, nm + '.norm0', groups=G_in, eps=b.eps, gamma=w[f'{nm}.norm0.g'], beta=w[f'{nm}.norm0.b'],
+                    act=DS_ACT_SILU, resample=rs, out=ws.act, out_ld=cin, **src)
+            bd.conv(ws.act, cin, cin, n, Ho, Ho, w[f'{nm}.conv0.w'], cout, ws.hbuf, cout, 9, nm + '.conv0', **conv0)
+        # norm1 (+adaptive scale/shift) + silu
+        if fuse:
+            bd.norm('stats', ws.hbuf, cout, cout, n, Ho, Ho, nm + '.norm1.stats', groups=G_out, eps=b.eps, gamma=w[f'{nm}.norm1.g'],
+                    beta=w[f'{nm}.norm1.b'], coefs=ncoef, **ss)
+            c1_in, kw = ws.hbuf, dict(norm_coefs=ncoef, norm_act=DS_ACT_SILU)
+        else:
+            bd.norm('stats', ws.hbuf, cout, cout, n, Ho, Ho, nm + '.norm1.stats', groups=G_out, eps=b.eps)
+            bd.norm('apply', ws.hbuf, cout, cout, n, Ho, Ho, nm + '.norm1', groups=G_out, eps=b.eps, gamma=w[f'{nm}.norm1.g'],
+                    beta=w[f'{nm}.norm1.b'], act=DS_ACT_SILU, out=ws.act, out_ld=cout, **ss)
+            c1_in, kw = ws.act, {}
+        # skip path: raw (resampled) input, projected by a 1x1 that is fused into conv1 as extra K columns
+        s0, sc0, s1, sc1 = x0, c0, x1, c1
+        if rs != DS_RESAMPLE_NONE:
+            bd.norm('apply', x0, c0, c0, n, Hin, Hin, nm + '.skip.resample', use_stats=False, resample=rs, out=ws.sres, out_ld=cin, **src)
+            s0, sc0, s1, sc1 = ws.sres, cin, None, 0
+        if b.skip_conv:
+            return c1_in, w[f'{nm}.conv1s.w'], dict(kw, bias=w[f'{nm}.conv1s.b'], e0=s0, ec0=sc0, e1=s1, ec1=sc1)
+        assert s1 is None and sc0 == cout
+        return c1_in, w[f'{nm}.conv1.w'], dict(kw, bias=w[f'{nm}.conv1.b'], res=s0, res_ld=cout)
+
+    def _block_out(self, bd, ws, b, f16):
+        """Output buffer of a block (and of its attention): encoder outputs are kept for the skip stack, decoder outputs ping-pong between two
+        fp32-sized buffers that blocks use in either dtype."""
+        M = ws.B * b.res_out ** 2
+        if b.pushes_skip:
+            return bd.new16(M, b.cout) if f16 else bd.new(M, b.cout)
+        t = ws.dec_pp[ws.dec_i]
+        if t is None:
+            t = ws.dec_pp[ws.dec_i] = bd.new(ws.B * ws.max_h)
+        ws.dec_i ^= 1
+        if f16:
+            bd.P.f16_views.append((t.data_ptr(), t.numel() * 2))
+            return t.view(torch.float16)[:t.numel()]
+        return t
+
+    def _attention(self, bd, ws, b, x, f16_out):
+        """GroupNorm -> packed q | k | v 1x1 -> fused attention (networks_edm.py:171-176: softmax(Q K^T / sqrt(ch)) V per (image, head), scores
+        kept on chip) -> 1x1 proj (+ residual) on the block's conv1 output `x`; returns the block output."""
+        w, nm, n, Ho, cout, hd = self.w, b.name, ws.B, b.res_out, b.cout, b.heads
+        S, ch = Ho * Ho, cout // hd
+        M = n * S
+        G = arch.num_groups(cout)
+        # fp16 mode: the GroupNorm output and the attention output are only operands of the qkv / proj 1x1s, and q | k | v are the rows the
+        # reference's qkv projection emits (networks_edm.py:171-173) -> fp16 rows, streamed by the fp16-activation GEMM (csrc/gemm_f16dma.hip)
+        if self._attn16(n, b):
+            n2, ao, qk = ws.n2_16[:M * cout].view(M, cout), ws.ao_16[:M * cout].view(M, cout), ws.qk_16
+        else:
+            n2, ao, qk = ws.n2, ws.ao, ws.qk
+        bd.norm('stats', x, cout, cout, n, Ho, Ho, nm + '.norm2.stats', groups=G, eps=b.eps)
+        bd.norm('apply', x, cout, cout, n, Ho, Ho, nm + '.norm2', groups=G, eps=b.eps, gamma=w[f'{nm}.norm2.g'], beta=w[f'{nm}.norm2.b'],
+                out=n2, out_ld=cout, out_f16=(n2.dtype == torch.float16))
+        bd.conv(n2, cout, cout, n, Ho, Ho, w[f'{nm}.qkv.w'], 3 * cout, qk, 3 * cout, 1, nm + '.qkv', bias=w[f'{nm}.qkv.b'])
+        bd.attention(qk, qk[cout:], qk[2 * cout:], ao, nm + '.attention', batch=n, heads=hd, sq=S, skv=S, d=ch, ldq=3 * cout, ldk=3 * cout,
+                     ldv=3 * cout, ldo=cout, q_bs=S * 3 * cout, k_bs=S * 3 * cout, v_bs=S * 3 * cout, o_bs=S * cout, scale=1.0 / math.sqrt(ch))
+        out = self._block_out(bd, ws, b, f16_out)
+        bd.conv(ao, cout, cout, n, Ho, Ho, w[f'{nm}.proj.w'], cout, out, cout, 1, nm + '.proj', bias=w[f'{nm}.proj.b'], res=x, res_ld=cout,
+                scale=b.skip_scale, stats=True)
+        return out
+
+    def _head(self, bd, ws, xo, co):
+        """Output head: GroupNorm + SiLU + 3x3 conv to the channel-planar network output, with the solver update fused where it can be."""
+        spec, w, lib, P = self.spec, self.w, self.lib, bd.P
+        B, R, G = ws.B, spec.img_resolution, arch.num_groups(co)
+        if lib.ds_conv3x3_halo_supported(R, R) and xo.dtype == torch.float32:
+            bd.norm('stats', xo, co, co, B, R, R, 'out.norm.stats', groups=G, eps=spec.out_eps, gamma=w['out.g'], beta=w['out.b'], coefs=bd.coefs)
+            bd.conv(xo, co, co, B, R, R, w['outc.w'], spec.out_channels, P.bufs['out'], 4, 9, 'out.conv', bias=w['outc.b'],
+                    norm_coefs=bd.coefs, norm_act=DS_ACT_SILU, out_nchw=1, w16=w.get('outc.w16'))
+        else:
+            bd.norm('stats', xo, co, co, B, R, R, 'out.norm.stats', groups=G, eps=spec.out_eps)
+            bd.norm('apply', xo, co, co, B, R, R, 'out.norm', groups=G, eps=spec.out_eps, gamma=w['out.g'], beta=w['out.b'], act=DS_ACT_SILU,
+                    out=ws.act, out_ld=co)
+            bd.conv(ws.act, co, co, B, R, R, w['outc.w'], spec.out_channels, P.bufs['out'], 4, 9, 'out.conv', bias=w['outc.b'], out_nchw=1)
+        # ---- the solver update fused into the head (ds_conv_args.update): the head launch carries a pointer to ONE persistent
+        # ds_update_args of this plan; EDMDenoiser.raw(update=...) fills it before a run and clears its outputs afterwards (x_out == m_out ==
+        # NULL = plain head).  Possible where the head runs on conv3x3_thin_kernel with a channel-planar output (ds_conv_kernel_id 2570).
+        head = P.ops[-1].keep[0]
+        P.head_update = _lib.UpdateArgs()
+        P.head_fusable = bool(head.out_nchw and not head.wgt_f16 and lib.ds_conv_kernel_id(C.byref(head)) == 2570)
+        if P.head_fusable:
+            head.update = C.cast(C.pointer(P.head_update), C.c_void_p)
 
     def flops(self, B):
         return arch.flops_per_image(self.spec) * B

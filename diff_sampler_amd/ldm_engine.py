@@ -13,6 +13,8 @@ One evaluation = one flat plan of libdsamd launches over NHWC fp32 workspaces:
     CFG                 the conditional and unconditional halves run as ONE 2B-image evaluation (networks_edm.py:679-683);
                         ``ds_cfg_denoise`` forms F_u + g (F_c - F_u) and D = x - sigma F in one pass.
 
+ResBlock halves, the head and Upsample are emitted by plan.Builder (gn_conv3x3, upsample_conv: shared with the AutoencoderKL decoder, the
+routing rules live there); their temporaries are recycled (Builder.alloc / free), layer outputs and the skip stack live as long as the plan.
 NHWC makes ``rearrange('b c h w -> b (h w) c')`` free: the transformer consumes the convolution outputs in place, and the
 decoder's ``torch.cat([h, hs.pop()])`` is never materialised (dual-source convolutions).  Everything is fp32 (the
 reference runs this U-Net under autocast; fp32 is the stricter contract -- DESIGN.md section 2).
@@ -27,10 +29,9 @@ from typing import Dict
 import torch
 
 from . import _lib, ldm_arch, ops
-from ._lib import DS_ACT_GEGLU, DS_ACT_SILU, DS_RESAMPLE_UP
-from .ops import pack_conv_weight, pack_linear_weight, pack_stem_weight
-from .plan import Builder, Plan, ptr
-from .engine import fuse_norm16_here
+from ._lib import DS_ACT_GEGLU, DS_ACT_SILU
+from .ops import pack_conv_weight, pack_conv_weight_f16, pack_linear_weight, pack_stem_weight
+from .plan import FUSE_NORM16_DEFAULT, Builder, Plan, fuse_norm16_value, ptr
 
 
 class LDMUNetEngine:
@@ -48,7 +49,6 @@ class LDMUNetEngine:
         self.batch_invariant = bool(batch_invariant)
         self.qkv_f16_min_head = int(qkv_f16_min_head)
         self.f16_downsample = bool(f16_downsample)
-        from .engine import FUSE_NORM16_DEFAULT, fuse_norm16_value
         self.fuse_norm16 = fuse_norm16_value(os.environ.get('DS_FUSE_NORM16', FUSE_NORM16_DEFAULT))     # see engine.UNetEngine.fuse_norm16 ('auto': SD-1.5 has no such layer class)
         self.spec = spec
         self.device = torch.device(device)
@@ -91,7 +91,6 @@ class LDMUNetEngine:
                         b1 = (b1 + g(f'{p}.skip_connection.bias')).contiguous()
                     w[f'{p}.c1.w'], w[f'{p}.c1.b'] = c1, b1
                     if self.use_fp16 and l.cin % 64 == 0 and l.cout % 64 == 0:
-                        from .ops import pack_conv_weight_f16
                         w[f'{p}.c0.w16'] = (pack_conv_weight_f16(g(f'{p}.in_layers.2.weight')), 0)
                         w[f'{p}.c1.w16'] = (pack_conv_weight_f16(g(f'{p}.out_layers.3.weight'),
                                                                  g(f'{p}.skip_connection.weight') if l.skip_conv else None), 0)
@@ -120,12 +119,10 @@ class LDMUNetEngine:
                 elif l.kind == 'down':
                     w[f'{p}.w'], w[f'{p}.b'] = pack_conv_weight(g(f'{p}.op.weight')), g(f'{p}.op.bias')
                     if self.use_fp16 and l.cin % 64 == 0 and l.cout % 64 == 0:
-                        from .ops import pack_conv_weight_f16
                         w[f'{p}.w16'] = (pack_conv_weight_f16(g(f'{p}.op.weight')), 0)     # [slab][tap][64]: the stride-1 packing, gathered by the GEMM
                 elif l.kind == 'up':
                     w[f'{p}.w'], w[f'{p}.b'] = pack_conv_weight(g(f'{p}.conv.weight')), g(f'{p}.conv.bias')
                     if self.use_fp16 and l.cin % 64 == 0:
-                        from .ops import pack_conv_weight_f16
                         w[f'{p}.w16'] = (pack_conv_weight_f16(g(f'{p}.conv.weight')), 0)
         w['out.g'], w['out.b'] = g('out.0.weight'), g('out.0.bias')
         w['outc.w'], w['outc.b'] = pack_conv_weight(g('out.2.weight')), g('out.2.bias')
@@ -150,8 +147,7 @@ class LDMUNetEngine:
         bufs['c_noise'] = new(emb_rows)
         bufs['context'] = new(N * ctx_len, spec.context_dim)
         bufs['out'] = new(N * R * R, 4)
-        cmax = max(max(l.cin, l.cout) for b in spec.blocks for l in b.layers)
-        ncoef = new(N * 3 * cmax)
+        bd.coefs = new(N * 3 * max(max(l.cin, l.cout) for b in spec.blocks for l in b.layers))
 
         # ---- time embedding (openaimodel.py:726-727) and every ResBlock's emb_layers in one GEMM ---------------------------
         pos, e0, emb, aff = new(emb_rows, MC), new(emb_rows, E), new(emb_rows, E), new(emb_rows, self.aff_total)
@@ -164,108 +160,43 @@ class LDMUNetEngine:
         # tensors, so every activation between layers is fp16.  Every ResBlock / SpatialTransformer / upsampling convolution that runs on
         # the fp16-activation kernels stores its output (the residual stream h, the skip stack hs, the transformer's x) as fp16 rows
         # too; arithmetic on them is fp32 (widened on load).  A layer without such a kernel at its geometry reads an fp32 copy
-        # (widen) and writes fp32; every consumer takes a tensor in the dtype it has.
+        # (Builder.widen) and writes fp32; every consumer takes a tensor in the dtype it has.
         stream16 = bd.conv_mode == 1
         P.stream16 = stream16
         new_act = (lambda *shape: bd.new16(*shape)) if stream16 else new
 
-        def widen(t, c, side, name):
-            """fp32 copy of an fp16 stream tensor, for a layer that has no fp16-activation kernel at this geometry (8x8 images of a
-            batch that is not a multiple of four; the strided convolutions)."""
-            if t is None or t.dtype != torch.float16:
-                return t
-            wide = new(N * side * side, c)
-            bd.norm('apply', t, c, c, N, side, side, name + '.widen', use_stats=False, out=wide, out_ld=c)
-            return wide
-
-        def gn_conv(x0, c0, x1, c1, side, gk, bk, eps, wgt, bias, cout, out, out_ld, name, w16=None, dma16=False, raw16=None, e16=None, **kw):
-            """GroupNorm(32) + SiLU + 3x3 conv over the concatenation [x0 | x1]; the normalisation rides in the conv's loader
-            when the LDS-halo kernel takes the shape, otherwise it is a separate pass (also when the fp16-operand kernel is
-            available for the normalised tensor but not with the fused normalisation: 8x8 images)."""
-            cin = c0 + c1
-            if dma16:
-                # fp16 mode (the reference runs this U-Net under autocast, sample.py:293-297): one pass writes GroupNorm + SiLU of the
-                # concatenation as an fp16 tensor (and, for a block with a skip_connection, the raw fp16 copy `raw16` that projection
-                # reads), the convolution is the fp16-activation matrix kernel (csrc/conv3x3_f16dma.hip).  `e16` = (raw fp16 tensor,
-                # channels) of a fused skip_connection; an fp16 `out` (a tensor that only feeds the next normalisation) is stored as such
-                bd.norm('stats', x0, c0, c0, N, side, side, name + '.gn.stats', x1=x1, c1=c1, ld1=c1, groups=32, eps=eps, gamma=gk,
-                        beta=bk, coefs=ncoef)
-                raw_ok = lambda t: t is None or t.dtype == torch.float16
-                if fuse_norm16_here(self.fuse_norm16, side, cout) and raw_ok(x0) and raw_ok(x1) and c0 % 64 == 0 and c1 % 64 == 0 and raw16 is None:
-                    # round 5: the convolution normalises its own LDS halo on the raw fp16 sources (conv3x3_f16dma NORM): no pass, no
-                    # materialised concatenation; a fused skip_connection reads its raw sources in place (e16 may name two)
-                    ex = {}
-                    if e16 is not None:
-                        ex = dict(e0=e16[0], ec0=e16[1])
-                        if len(e16) > 2 and e16[2] is not None:
-                            ex.update(e1=e16[2], ec1=e16[3])
-                    bd.conv(x0, c0, c0, N, side, side, wgt, cout, out, out_ld, 9, name, x1=x1, c1=c1, ld1=c1, bias=bias, stats=True, w16=w16,
-                            in_f16=True, out_f16=(out.dtype == torch.float16), norm_coefs=ncoef, norm_act=DS_ACT_SILU, **ex, **kw)
-                    return
-                a16 = bd.new16(N * side * side, cin)
-                bd.norm('apply', x0, c0, c0, N, side, side, name + '.gn', x1=x1, c1=c1, ld1=c1, groups=32, eps=eps, use_stats=False,
-                        act=DS_ACT_SILU, out=a16, out_ld=cin, out_f16=True, raw_out=raw16, raw_ld=cin, coefs=ncoef,
-                        in_f16=(x0.dtype == torch.float16))
-                # the pass form takes ONE raw source for a fused skip_connection (the materialised copy `raw16`, or the single fp16 input): a
-                # two-source e16 belongs to the fused branch above only -- res_layer evaluates the same predicate; if the two ever disagreed the
-                # second source would be dropped silently (ADVICE r5)
-                assert e16 is None or len(e16) == 2 or e16[2] is None, (name, 'two raw skip sources need the fused normalisation')
-                ex = dict(e0=e16[0], ec0=e16[1]) if e16 is not None else {}
-                bd.conv(a16, cin, cin, N, side, side, wgt, cout, out, out_ld, 9, name, bias=bias, stats=True, w16=w16, in_f16=True,
-                        out_f16=(out.dtype == torch.float16), **ex, **kw)
-                return
-            unfused_f16 = w16 is not None and bd.f16_level(N, side, side, cin, 0, kw.get('ec0', 0), kw.get('ec1', 0)) == 1
-            if lib.ds_conv3x3_halo_supported(side, side) and not unfused_f16 and x0.dtype == torch.float32 and (x1 is None or x1.dtype == torch.float32):
-                bd.norm('stats', x0, c0, c0, N, side, side, name + '.gn.stats', x1=x1, c1=c1, ld1=c1, groups=32, eps=eps, gamma=gk,
-                        beta=bk, coefs=ncoef)
-                bd.conv(x0, c0, c0, N, side, side, wgt, cout, out, out_ld, 9, name, x1=x1, c1=c1, ld1=c1, bias=bias, norm_coefs=ncoef,
-                        norm_act=DS_ACT_SILU, stats=True, w16=w16, **kw)
-            else:
-                tmp = new(N * side * side, cin)
-                bd.norm('stats', x0, c0, c0, N, side, side, name + '.gn.stats', x1=x1, c1=c1, ld1=c1, groups=32, eps=eps)
-                bd.norm('apply', x0, c0, c0, N, side, side, name + '.gn', x1=x1, c1=c1, ld1=c1, groups=32, eps=eps, gamma=gk, beta=bk,
-                        act=DS_ACT_SILU, out=tmp, out_ld=cin)
-                bd.conv(tmp, cin, cin, N, side, side, wgt, cout, out, out_ld, 9, name, bias=bias, stats=True, w16=w16, **kw)
-
         def res_layer(l, x0, c0, x1, c1):
             p, res, cout = l.key, l.res_out, l.cout
             M = N * res * res
-            ao = self.aff_off[p]
             cin = c0 + c1
-            w16_0, w16_1 = w.get(f'{p}.c0.w16'), w.get(f'{p}.c1.w16')
-            dma16 = bool(w16_0 is not None and w16_1 is not None and bd.conv_mode == 1
-                         and lib.ds_conv_f16dma_supported(N, res, res, cin, 0, cout)
-                         and lib.ds_conv_f16dma_supported(N, res, res, cout, cin if l.skip_conv else 0, cout))
-            out = new_act(M, cout) if dma16 else new(M, cout)
-            if dma16:
-                h1 = bd.new16(M, cout)                       # in_layers output: only read by the out_layers normalisation
-                direct = x1 is None and x0.dtype == torch.float16          # the input already is one fp16 tensor: no raw copy for the skip_connection
-                # fuse_norm16: both raw fp16 sources are read in place by in_layers AND by the fused skip_connection: no raw copy at all
-                both_raw = bool(fuse_norm16_here(self.fuse_norm16, res, cout) and x0.dtype == torch.float16 and (x1 is None or x1.dtype == torch.float16)
-                                and c0 % 64 == 0 and c1 % 64 == 0)
-                r16 = bd.new16(M, cin) if l.skip_conv and not direct and not both_raw else None
-                gn_conv(x0, c0, x1, c1, res, w[f'{p}.n0.g'], w[f'{p}.n0.b'], 1e-5, w[f'{p}.c0.w'], w[f'{p}.c0.b'], cout, h1, cout,
-                        p + '.in_layers', w16=w16_0, dma16=True, raw16=r16, cbias=aff[:, ao:], cbias_ld=self.aff_total, cbias_rows=emb_rows)
-                if l.skip_conv and both_raw and not direct:
-                    skip = dict(e16=(x0, c0, x1, c1))
-                else:
-                    skip = dict(e16=(x0 if direct else r16, cin)) if l.skip_conv else dict(res=x0, res_ld=cout)
-                if not l.skip_conv:
-                    assert x1 is None and c0 == cout
-                gn_conv(h1, cout, None, 0, res, w[f'{p}.n1.g'], w[f'{p}.n1.b'], 1e-5, w[f'{p}.c1.w'], w[f'{p}.c1.b'], cout, out, cout,
-                        p + '.out_layers', w16=w16_1, dma16=True, **skip)
-                return out, cout
-            x0, x1 = widen(x0, c0, res, p + '.x0'), widen(x1, c1, res, p + '.x1')
-            h1 = new(M, cout)
-            gn_conv(x0, c0, x1, c1, res, w[f'{p}.n0.g'], w[f'{p}.n0.b'], 1e-5, w[f'{p}.c0.w'], w[f'{p}.c0.b'], cout, h1, cout,
-                    p + '.in_layers', w16=w.get(f'{p}.c0.w16'), cbias=aff[:, ao:], cbias_ld=self.aff_total, cbias_rows=emb_rows)
-            if l.skip_conv:
-                skip = dict(e0=x0, ec0=c0, e1=x1, ec1=c1)
-            else:
+            f16 = bool(bd.f16_conv_ok(N, res, cin, 0, cout) and bd.f16_conv_ok(N, res, cout, cin if l.skip_conv else 0, cout))
+            conv0 = dict(w16=w.get(f'{p}.c0.w16'), f16=f16, fuse_norm16=self.fuse_norm16, cbias=aff[:, self.aff_off[p]:], cbias_ld=self.aff_total, cbias_rows=emb_rows)
+            conv1 = dict(w16=w.get(f'{p}.c1.w16'), f16=f16, fuse_norm16=self.fuse_norm16)
+            if not l.skip_conv:
                 assert x1 is None and c0 == cout
-                skip = dict(res=x0, res_ld=cout)
-            gn_conv(h1, cout, None, 0, res, w[f'{p}.n1.g'], w[f'{p}.n1.b'], 1e-5, w[f'{p}.c1.w'], w[f'{p}.c1.b'], cout, out, cout,
-                    p + '.out_layers', w16=w.get(f'{p}.c1.w16'), **skip)
+            if f16:
+                # the 1x1 skip_connection rides in the second convolution as extra K columns on raw fp16 rows: the input itself when it is
+                # one fp16 tensor, both raw sources in place when in_layers normalises its own halo (fuses_norm16), else a raw copy the
+                # in_layers pass writes next to the activated tensor
+                direct = x1 is None and x0.dtype == torch.float16
+                if not l.skip_conv:
+                    conv1.update(res=x0, res_ld=cout)
+                elif direct:
+                    conv1.update(e16=(x0, cin))
+                elif bd.fuses_norm16(self.fuse_norm16, res, cout, x0, c0, x1, c1):
+                    conv1.update(e16=(x0, c0, x1, c1))
+                else:
+                    conv0.update(raw16=bd.new16(M, cin))
+                    conv1.update(e16=(conv0['raw16'], cin))
+            else:
+                x0, x1 = bd.widen(x0, c0, N, res, p + '.x0'), bd.widen(x1, c1, N, res, p + '.x1')
+                conv1.update(dict(e0=x0, ec0=c0, e1=x1, ec1=c1) if l.skip_conv else dict(res=x0, res_ld=cout))
+            h1 = bd.new16(M, cout) if f16 else new(M, cout)      # in_layers output: only read by the out_layers normalisation
+            out = new_act(M, cout) if f16 else new(M, cout)
+            bd.gn_conv3x3(x0, c0, x1, c1, N, res, w[f'{p}.n0.g'], w[f'{p}.n0.b'], w[f'{p}.c0.w'], w[f'{p}.c0.b'], cout, h1, cout, p + '.in_layers',
+                          **conv0)
+            bd.gn_conv3x3(h1, cout, None, 0, N, res, w[f'{p}.n1.g'], w[f'{p}.n1.b'], w[f'{p}.c1.w'], w[f'{p}.c1.b'], cout, out, cout,
+                          p + '.out_layers', **conv1)
             return out, cout
 
         def st_layer(l, x_in, c):
@@ -283,7 +214,7 @@ class LDMUNetEngine:
             mk = bd.new16 if h16 else new
             ts = new_act if h16 else new                     # the transformer's residual stream t0 .. t3 and its output
             if not h16:
-                x_in = widen(x_in, c, res, p + '.x')
+                x_in = bd.widen(x_in, c, N, res, p + '.x')
             n2, t0, ln, ao = mk(M, c), ts(M, c), mk(M, c), mk(M, c)
             bd.norm('stats', x_in, c, c, N, res, res, p + '.norm.stats', groups=32, eps=1e-6)
             bd.norm('apply', x_in, c, c, N, res, res, p + '.norm', groups=32, eps=1e-6, gamma=w[f'{p}.n.g'], beta=w[f'{p}.n.b'],
@@ -352,42 +283,25 @@ class LDMUNetEngine:
                                 bias=w[f'{p}.b'], stride=2, stats=True, w16=w[f'{p}.w16'], in_f16=True)
                     else:
                         out = new(N * l.res_out ** 2, l.cout)
-                        cur = (widen(cur[0], l.cin, l.res_in, p), l.cin)      # the strided convolution reads fp32 rows
+                        cur = (bd.widen(cur[0], l.cin, N, l.res_in, p), l.cin)      # the strided convolution reads fp32 rows
                         bd.conv(cur[0], l.cin, l.cin, N, l.res_out, l.res_out, w[f'{p}.w'], l.cout, out, l.cout, 9, p + '.op',
                                 bias=w[f'{p}.b'], stride=2, stats=True)
                     cur = (out, l.cout)
                 elif l.kind == 'up':
-                    f16up = bool(w.get(f'{p}.w16') is not None and bd.conv_mode == 1 and lib.ds_conv_f16dma_supported(N, l.res_out, l.res_out, l.cin, 0, l.cout))
-                    out = new_act(N * l.res_out ** 2, l.cout) if f16up else new(N * l.res_out ** 2, l.cout)
-                    if w.get(f'{p}.w16') is not None and bd.conv_mode == 1 and lib.ds_conv_f16dma_supported(N, l.res_out, l.res_out, l.cin, 0, l.cout):
-                        up = bd.new16(N * l.res_out ** 2, l.cin)     # nearest x2 of the raw tensor, stored in fp16 for the matrix kernel
-                        bd.norm('apply', cur[0], l.cin, l.cin, N, l.res_in, l.res_in, p + '.nearest', use_stats=False,
-                                resample=DS_RESAMPLE_UP, out=up, out_ld=l.cin, out_f16=True)
-                        bd.conv(up, l.cin, l.cin, N, l.res_out, l.res_out, w[f'{p}.w'], l.cout, out, l.cout, 9, p + '.conv', bias=w[f'{p}.b'],
-                                stats=True, w16=w.get(f'{p}.w16'), in_f16=True)
-                    else:
-                        up = new(N * l.res_out ** 2, l.cin)
-                        bd.norm('apply', cur[0], l.cin, l.cin, N, l.res_in, l.res_in, p + '.nearest', use_stats=False,
-                                resample=DS_RESAMPLE_UP, out=up, out_ld=l.cin)
-                        bd.conv(up, l.cin, l.cin, N, l.res_out, l.res_out, w[f'{p}.w'], l.cout, out, l.cout, 9, p + '.conv', bias=w[f'{p}.b'],
-                                stats=True, w16=w.get(f'{p}.w16'))
-                    cur = (out, l.cout)
+                    cur = (bd.upsample_conv(cur[0], l.cin, N, l.res_in, w[f'{p}.w'], w[f'{p}.b'], l.cout, p, w16=w.get(f'{p}.w16')), l.cout)
                 bufs[p] = cur[0]
             if b.pushes_skip:
                 skips.append(cur)
         assert not skips
-        gn_conv(cur[0], cur[1], None, 0, R, w['out.g'], w['out.b'], 1e-5, w['outc.w'], w['outc.b'], spec.out_channels, bufs['out'], 4,
-                'out')
+        bd.gn_conv3x3(cur[0], cur[1], None, 0, N, R, w['out.g'], w['out.b'], w['outc.w'], w['outc.b'], spec.out_channels, bufs['out'], 4, 'out')
+        bd.finish()
         # The cross-attention key / value projections (ldm/modules/attention.py:168-176: to_k(context), to_v(context)) depend on the text
         # context only -- not on x or sigma -- so they form their own small plan that CFGDenoiser runs once per context, not once per
         # network evaluation (16 launches of 361 at SD-1.5 size)
-        from .plan import Plan
         P.ctx = Plan()
         P.ctx.ops = [op for op in P.ops if op.name.endswith('.attn2.kv')]
         P.ops = [op for op in P.ops if not op.name.endswith('.attn2.kv')]
         P.ctx_key = None
-        from .plan import release_tuning_scratch
-        release_tuning_scratch()            # the tile measurement's 512 MiB flush buffer does not outlive the plan build
         self._plans[key] = P
         return P
 

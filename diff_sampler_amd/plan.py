@@ -2,7 +2,10 @@
 
 A plan is compiled once per (network, batch size); running it is a tight ctypes loop, and because no pointer changes
 between runs it can be captured into a hipGraph (``graph.py``).  ``Builder`` is the small DSL the engines use to emit
-launches; it only marshals arguments -- every operation is a libdsamd kernel.
+launches; it only marshals arguments -- every operation is a libdsamd kernel.  Two levels: one launch (``conv``, ``norm``,
+``attention``, ...) and the blocks more than one network is made of (``gn_conv3x3``, ``upsample_conv``, ``widen``), which decide WHICH
+launches a block becomes and take their temporaries from the builder's recycling allocator (``alloc`` / ``free``); ``finish`` ends
+every plan build.
 """
 from __future__ import annotations
 
@@ -13,7 +16,7 @@ from typing import Dict, List
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, ConvArgs, GemmArgs, GnFinalizeArgs, NormArgs, DS_ACT_NONE, DS_RESAMPLE_NONE
+from ._lib import AttnArgs, ConvArgs, GemmArgs, GnFinalizeArgs, NormArgs, DS_ACT_NONE, DS_ACT_SILU, DS_RESAMPLE_NONE, DS_RESAMPLE_UP
 
 
 SPLITK_WORKSPACE_FLOATS = 64 << 20      # 256 MiB per plan
@@ -53,6 +56,21 @@ _FLUSH: Dict[int, torch.Tensor] = {}     # device index -> the 512 MiB scratch w
 TILE_TABLE_FILE = os.environ.get('DS_TILE_TABLE', os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', 'tile_table.json'))
 TILE_TABLE_KERNELS = ('conv3x3_f16dma.hip', 'gemm_f16dma.hip')
 _TABLE = {'loaded': False, 'entries': {}, 'why': None}
+
+# default of the engines' fuse_norm16: '0' never, '1' every eligible layer, 'auto' the layer classes where the per-layer A/B of round 5 found the
+# fusion faster than pass + convolution (profiles/r5_conv_f16dma_fused_norm_per_layer.txt): 64x64 images and one column tile (cout <= 192).
+# Whole-net A/B of '1' against '0': profiles/r5_conv_f16dma_fused_norm_ab.txt (ImageNet-64 +0.4 %, SD-1.5 -6.8 %).
+FUSE_NORM16_DEFAULT = 'auto'
+
+
+def fuse_norm16_value(text):
+    """'0' / '1' / 'auto' (DS_FUSE_NORM16, or the engines' attribute) -> False / True / 'auto'."""
+    return {'0': False, '1': True}.get(str(text), 'auto')
+
+
+def fuse_norm16_here(mode, side, cout):
+    """Does the 3x3 convolution of this geometry normalise its own LDS halo (conv3x3_f16dma NORM) under `mode`?"""
+    return mode is True or (mode == 'auto' and side == 64 and cout <= 192)
 
 
 def _table_hashes():
@@ -237,6 +255,9 @@ class Builder:
         self.autotune = bool(autotune)
         self.invariant = bool(invariant)
         self.batch = batch
+        self.coefs = None                   # {mu, A, B} planes of the GroupNorm emitters: allocated by the engine, which knows the widest layer
+        self.free_list = []                 # alloc / free: base tensors (1-D) whose last reader has been emitted
+        self.base = {}                      # data_ptr of a view handed out by alloc -> its base tensor
         self.w16_cache = w16_cache if w16_cache is not None else {}
         self.P = Plan()
         self.dev = device
@@ -262,6 +283,133 @@ class Builder:
 
     def add(self, fn, args, name, keep=()):
         self.P.ops.append(Op(fn, args, name, keep))
+
+    # ---- workspace recycling (launches of a plan are serial) ---------------------------------------------------------------------
+    def alloc(self, rows, cols, f16=False):
+        """[rows, cols] workspace: a freed buffer of the same dtype that is large enough (the smallest such), else a new plan-owned tensor."""
+        dt = torch.float16 if f16 else torch.float32
+        n = rows * cols
+        fit = [t for t in self.free_list if t.dtype == dt and t.numel() >= n]
+        if fit:
+            b = min(fit, key=lambda t: t.numel())
+            self.free_list = [t for t in self.free_list if t is not b]
+        else:
+            b = (self.new16 if f16 else self.new)(n)
+        v = b[:n].view(rows, cols)
+        self.base[v.data_ptr()] = b
+        return v
+
+    def free(self, *views):
+        """Makes buffers of alloc() available to LATER launches: call it once the last reader is emitted."""
+        for v in views:
+            if v is None:
+                continue
+            b = self.base.pop(v.data_ptr(), None)
+            if b is not None:
+                self.stats_of.pop(v.data_ptr(), None)       # column sums of a recycled tensor describe nothing
+                self.free_list.append(b)
+
+    # ---- blocks ----------------------------------------------------------------------------------------------------------------------
+    def widen(self, t, c, n, side, name):
+        """`t`, or -- for an fp16 stream tensor -- an fp32 copy from alloc(), for a layer that has no fp16-activation kernel at this
+        geometry.  The source is not freed: it may sit on a skip stack."""
+        if t is None or t.dtype != torch.float16:
+            return t
+        wide = self.alloc(n * side * side, c)
+        self.norm('apply', t, c, c, n, side, side, name + '.widen', use_stats=False, out=wide, out_ld=c)
+        return wide
+
+    def f16_conv_ok(self, n, side, cin, extra, cout, wide=False):
+        """Does this stride-1 3x3 layer (`extra` = channels of a fused 1x1 skip projection) run on an fp16-activation kernel?  fp16 mode and
+        whole 64-channel slabs only (the layers that have an fp16 weight packing); conv3x3_f16dma's own rule, which ends at 64 pixels.
+        wide: above 64 pixels the layer may take the patch kernel (csrc/conv3x3_f16wide.hip: power-of-two sides).  That kernel has one
+        source, no fused skip columns, no fused normalisation and no per-image bias row, so only a caller whose layers above 64 pixels are
+        all of that kind asks (the AutoencoderKL decoder); the denoisers' layers above 64 pixels keep the fp32 routes."""
+        if self.conv_mode != 1 or cin % 64 or cout % 64:
+            return False
+        if side > 64:
+            return bool(wide and not extra and side & (side - 1) == 0)
+        return bool(self.lib.ds_conv_f16dma_supported(n, side, side, cin, extra, cout))
+
+    @staticmethod
+    def fuses_norm16(mode, side, cout, x0, c0, x1=None, c1=0):
+        """fp16-activation 3x3 layer: does the convolution normalise its own LDS halo (conv3x3_f16dma NORM: no pass, no materialised
+        concatenation)?  Where `mode` (an engine's fuse_norm16) asks for it and every source is a raw fp16 tensor of whole 64-channel slabs."""
+        raw = lambda t: t is None or t.dtype == torch.float16
+        return bool(fuse_norm16_here(mode, side, cout) and raw(x0) and raw(x1) and c0 % 64 == 0 and c1 % 64 == 0)
+
+    def gn_conv3x3(self, x0, c0, x1, c1, n, side, gamma, beta, wgt, bias, cout, out, out_ld, name, eps=1e-5, groups=32, w16=None, f16=False,
+                   fuse_norm16=False, raw16=None, e16=None, **kw):
+        """GroupNorm + SiLU + 3x3 conv over the concatenation [x0 | x1] (x1 may be None), `kw` to the convolution.  Three routes:
+        f16 -- the caller found f16_conv_ok() for this layer and allocated `out` (and a block's intermediate tensor) to match: one pass
+        writes the activated tensor as fp16 rows (and `raw16`, the raw fp16 copy a fused skip projection reads) and the convolution is the
+        fp16-activation matrix kernel, or (fuses_norm16 under the mode `fuse_norm16`) the convolution normalises its own LDS halo on the raw sources.  `e16` = (tensor,
+        channels) or (tensor, channels, tensor, channels): raw fp16 source(s) of a fused 1x1 skip projection; an fp16 `out` is stored as such.
+        Otherwise fp32 activations: the normalisation rides in the LDS-halo kernel's loader where that kernel takes the shape, else a
+        separate pass (also when the fp16-operand kernel is available for the normalised tensor but not with the fused normalisation)."""
+        assert self.coefs is not None and self.coefs.numel() >= 3 * n * (c0 + c1), (name, 'the engine sizes Builder.coefs for its widest layer')
+        cin = c0 + c1
+        src = dict(x1=x1, c1=c1, ld1=c1)
+        gn_stats = lambda **k: self.norm('stats', x0, c0, c0, n, side, side, name + '.gn.stats', groups=groups, eps=eps, **src, **k)
+        gn_apply = lambda **k: self.norm('apply', x0, c0, c0, n, side, side, name + '.gn', groups=groups, eps=eps, act=DS_ACT_SILU, **src, **k)
+        if f16:
+            assert w16 is not None and self.conv_mode == 1, name
+            ex = dict(zip(('e0', 'ec0', 'e1', 'ec1'), e16 or ()))
+            kw = dict(kw, bias=bias, stats=True, w16=w16, in_f16=True, out_f16=(out.dtype == torch.float16))
+            gn_stats(gamma=gamma, beta=beta, coefs=self.coefs)
+            if raw16 is None and self.fuses_norm16(fuse_norm16, side, cout, x0, c0, x1, c1):
+                self.conv(x0, c0, c0, n, side, side, wgt, cout, out, out_ld, 9, name, **src, norm_coefs=self.coefs, norm_act=DS_ACT_SILU, **ex, **kw)
+                return
+            # the pass form takes ONE raw source for a fused skip projection (the copy `raw16`, or the single fp16 input): two belong to the
+            # fused form only, and a caller that decided otherwise must not lose the second one silently
+            assert 'e1' not in ex, (name, 'two raw skip sources need the fused normalisation')
+            a16 = self.alloc(n * side * side, cin, f16=True)
+            gn_apply(use_stats=False, out=a16, out_ld=cin, out_f16=True, raw_out=raw16, raw_ld=cin, coefs=self.coefs, in_f16=(x0.dtype == torch.float16))
+            self.conv(a16, cin, cin, n, side, side, wgt, cout, out, out_ld, 9, name, **ex, **kw)
+            self.free(a16)
+            return
+        kw = dict(kw, bias=bias, stats=True, w16=w16)
+        unfused_f16 = w16 is not None and self.f16_level(n, side, side, cin, 0, kw.get('ec0', 0), kw.get('ec1', 0)) == 1
+        if self.lib.ds_conv3x3_halo_supported(side, side) and not unfused_f16 and x0.dtype == torch.float32 and (x1 is None or x1.dtype == torch.float32):
+            gn_stats(gamma=gamma, beta=beta, coefs=self.coefs)
+            self.conv(x0, c0, c0, n, side, side, wgt, cout, out, out_ld, 9, name, **src, norm_coefs=self.coefs, norm_act=DS_ACT_SILU, **kw)
+        else:
+            tmp = self.alloc(n * side * side, cin)
+            gn_stats()
+            gn_apply(gamma=gamma, beta=beta, out=tmp, out_ld=cin)
+            self.conv(tmp, cin, cin, n, side, side, wgt, cout, out, out_ld, 9, name, **kw)
+            self.free(tmp)
+
+    def upsample_conv(self, x, cin, n, side_in, wgt, bias, cout, name, w16=None, wide=False, out_f32=False, free_src=False):
+        """Nearest x2 of the raw tensor -> 3x3 conv; returns the output from alloc().  On the fp16-activation kernel (the pass writes fp16
+        rows, the output joins the fp16 stream unless `out_f32`) where f16_conv_ok() (asked with `wide`) and there is an fp16 packing `w16`, else fp32.
+        free_src: `x` is an alloc() buffer without another reader -- recycled as soon as the pass has read it."""
+        side = 2 * side_in
+        M = n * side * side
+        f16 = w16 is not None and self.f16_conv_ok(n, side, cin, 0, cout, wide)
+        up = self.alloc(M, cin, f16=f16)
+        self.norm('apply', x, cin, cin, n, side_in, side_in, name + '.nearest', use_stats=False, resample=DS_RESAMPLE_UP, out=up, out_ld=cin,
+                  out_f16=f16)
+        if free_src:
+            self.free(x)
+        out = self.alloc(M, cout, f16=(f16 and not out_f32))
+        self.conv(up, cin, cin, n, side, side, wgt, cout, out, cout, 9, name + '.conv', bias=bias, stats=True, w16=w16, in_f16=f16)
+        self.free(up)
+        return out
+
+    def finish(self):
+        """Ends a plan build: a missing kernel is an error now, not at the first run (P.kernel_ids: launch name -> ds_conv_kernel_id), and
+        the tile measurement's 512 MiB flush buffer does not outlive the build."""
+        P = self.P
+        P.kernel_ids = {}
+        for op in P.ops:
+            if op.fn is self.lib.ds_conv2d_nhwc:
+                kid = self.lib.ds_conv_kernel_id(C.byref(op.keep[0]))
+                if kid < 0:
+                    _lib.check(kid, f'plan: no kernel for {op.name}')
+                P.kernel_ids[op.name] = kid
+        release_tuning_scratch()
+        return P
 
     def conv(self, x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, taps, name, x1=None, c1=0, ld1=0, bias=None, cbias=None,
              cbias_ld=0, cbias_rows=1, res=None, res_ld=0, scale=1.0, act=DS_ACT_NONE, norm_coefs=None, norm_act=DS_ACT_NONE,
@@ -503,6 +651,8 @@ class Builder:
         # fp16 q / k / v (the projections' outputs in the fp16 stream) are recognised by their dtype: bit 0 = q, bit 1 = k and v
         a.in_f16 = (1 if q.dtype == torch.float16 else 0) | (2 if k.dtype == torch.float16 else 0)
         assert k.dtype == v.dtype and (not a.in_f16 or f16), name
+        if self.invariant and not f16 and d % 128 == 0:
+            a.variant = 2           # invariant: the channel-split block at every batch (ds_attention_variant)
         self.add(self.lib.ds_attention_f16 if f16 else self.lib.ds_attention, (C.byref(a),), name, keep=(a,))
 
     def layernorm(self, x, ldx, gamma, beta, eps, y, ldy, rows, cols, name):

@@ -20,55 +20,23 @@ kernel id 2575) above -- and the tensors between them are fp16 rows; GroupNorm s
 The tensors around the mid-block attention and the input of the head stay fp32 rows (their consumers read fp32).  use_fp16=False: fp32
 everywhere; above 64 pixels wide that is the generic gather kernel.
 
-Workspaces belong to the plan and are recycled as soon as their last reader is emitted (launches of a plan are serial): a decode keeps
+The blocks are emitted by plan.Builder (gn_conv3x3, upsample_conv, widen, attention), shared with the latent U-Net.  Workspaces belong to
+the plan and are recycled as soon as their last reader is emitted (Builder.alloc / free; launches of a plan are serial): a decode keeps
 about three full-resolution tensors alive, not one per layer.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict
 
 import torch
 
 from . import _lib, vae_arch
-from ._lib import DS_ACT_SILU, DS_RESAMPLE_UP
+from ._lib import DS_ACT_SILU
 from .ops import pack_conv_weight, pack_conv_weight_f16, pack_stem_weight
 from .plan import Builder, Plan, ptr
 
 KERNEL_ID_F16WIDE = 2575        # ds_conv_kernel_id of csrc/conv3x3_f16wide.hip
 EPS = 1e-6                      # model.py:38-39
-
-
-class _Pool:
-    """Workspace recycling on top of plan.Builder: alloc() hands out a freed buffer of the same dtype that is large enough (the smallest
-    such), else a new plan-owned tensor; free() makes a buffer available to LATER launches."""
-
-    def __init__(self, bd: Builder):
-        self.bd = bd
-        self.free_list = []     # base tensors (1-D)
-        self.base = {}          # data_ptr of a view -> its base tensor
-
-    def alloc(self, rows, cols, f16=False):
-        dt = torch.float16 if f16 else torch.float32
-        n = rows * cols
-        fit = [t for t in self.free_list if t.dtype == dt and t.numel() >= n]
-        if fit:
-            b = min(fit, key=lambda t: t.numel())
-            self.free_list = [t for t in self.free_list if t is not b]
-        else:
-            b = (self.bd.new16 if f16 else self.bd.new)(n)
-        v = b[:n].view(rows, cols)
-        self.base[v.data_ptr()] = b
-        return v
-
-    def free(self, *views):
-        for v in views:
-            if v is None:
-                continue
-            b = self.base.pop(v.data_ptr(), None)
-            if b is not None:
-                self.bd.stats_of.pop(v.data_ptr(), None)       # column sums of a recycled tensor describe nothing
-                self.free_list.append(b)
 
 
 class VAEDecoder:
@@ -143,17 +111,6 @@ class VAEDecoder:
         self.w = w
 
     # ------------------------------------------------------------------------------------------ plan
-    def _f16_conv_ok(self, N, side, cin, cout):
-        """Does this 3x3 layer run on an fp16-activation kernel (use_fp16 only)?  Up to 64 pixels wide: conv3x3_f16dma's own rule; above:
-        the patch kernel's (power-of-two sides, whole 64-channel slabs and column tiles)."""
-        if not self.use_fp16 or cin % 64 or cout % 64:
-            return False
-        if side > 64:
-            return side & (side - 1) == 0
-        if self.batch_invariant and (side * side) % 256:
-            return False            # 8 x 8 images: whole 256-pixel tiles only at batches that are multiples of four (plan.Builder.f16_level)
-        return bool(self.lib.ds_conv_f16dma_supported(N, side, side, cin, 0, cout))
-
     def plan(self, N: int) -> Plan:
         if N in self._plans:
             return self._plans[N]
@@ -161,7 +118,6 @@ class VAEDecoder:
         bd = Builder(self.device, conv_mode=(1 if self.use_fp16 else 0), w16_cache=self._w16_cache, autotune=False,
                      invariant=self.batch_invariant, batch=N)
         P, new = bd.P, bd.new
-        pool = _Pool(bd)
         bufs = P.bufs
         R, RO = spec.latent_resolution, spec.img_resolution
         zc = spec.z_channels
@@ -169,63 +125,40 @@ class VAEDecoder:
         bufs['x'][:, zc] = 1.0                       # the ones plane (see _pack); written once, the latents go to planes [0, zc)
         bufs['one'] = new(1, zero=True)              # ds_stem_im2col scales by 1 / sqrt(sigma^2 + sigma_data^2): sigma 0, sigma_data 1
         bufs['out'] = new(N, spec.out_ch, RO, RO)
-        cmax = max(max(l.cin, l.cout) for l in spec.layers)
-        ncoef = new(N * 3 * cmax)
+        bd.coefs = new(N * 3 * max(max(l.cin, l.cout) for l in spec.layers))
         layers = spec.layers
+        # This decoder's own rule, on top of Builder.f16_conv_ok: in the invariant mode its 8 x 8 layers (images that do not fill a 256-pixel
+        # tile) stay on the fp32 kernels.  The denoisers run such layers on the fp16-activation kernels in that mode too.
+        fp32_only = lambda side: self.batch_invariant and (side * side) % 256
 
-        def widen(t, c, side, name):
-            if t.dtype != torch.float16:
-                return t
-            wide = pool.alloc(N * side * side, c)
-            bd.norm('apply', t, c, c, N, side, side, name + '.widen', use_stats=False, out=wide, out_ld=c)
-            pool.free(t)
+        def fp32_rows(t, c, side, name):
+            """`t` as fp32 rows: an fp16 tensor is widened and recycled."""
+            wide = bd.widen(t, c, N, side, name)
+            if wide is not t:
+                bd.free(t)
             return wide
-
-        def gn_conv(x, cin, side, gk, bk, wkey, cout, out, name, f16, res=None):
-            """GroupNorm(32) + swish + 3x3 conv (+ residual).  f16: the pass writes the activated tensor as fp16 rows and the convolution is an
-            fp16-activation matrix kernel; else fp32, the normalisation fused into the LDS-halo kernel's loader where that kernel exists."""
-            M = N * side * side
-            kw = dict(bias=w[f'{wkey}.b'], stats=True)
-            if res is not None:
-                kw.update(res=res, res_ld=cout)
-            if f16:
-                bd.norm('stats', x, cin, cin, N, side, side, name + '.gn.stats', groups=32, eps=EPS, gamma=gk, beta=bk, coefs=ncoef)
-                a16 = pool.alloc(M, cin, f16=True)
-                bd.norm('apply', x, cin, cin, N, side, side, name + '.gn', groups=32, eps=EPS, use_stats=False, act=DS_ACT_SILU, out=a16,
-                        out_ld=cin, out_f16=True, coefs=ncoef, in_f16=(x.dtype == torch.float16))
-                bd.conv(a16, cin, cin, N, side, side, w[f'{wkey}.w'], cout, out, cout, 9, name, w16=w[f'{wkey}.w16'], in_f16=True,
-                        out_f16=(out.dtype == torch.float16), **kw)
-                pool.free(a16)
-            elif lib.ds_conv3x3_halo_supported(side, side):
-                bd.norm('stats', x, cin, cin, N, side, side, name + '.gn.stats', groups=32, eps=EPS, gamma=gk, beta=bk, coefs=ncoef)
-                bd.conv(x, cin, cin, N, side, side, w[f'{wkey}.w'], cout, out, cout, 9, name, norm_coefs=ncoef, norm_act=DS_ACT_SILU, **kw)
-            else:
-                tmp = pool.alloc(M, cin)
-                bd.norm('stats', x, cin, cin, N, side, side, name + '.gn.stats', groups=32, eps=EPS)
-                bd.norm('apply', x, cin, cin, N, side, side, name + '.gn', groups=32, eps=EPS, gamma=gk, beta=bk, act=DS_ACT_SILU,
-                        out=tmp, out_ld=cin)
-                bd.conv(tmp, cin, cin, N, side, side, w[f'{wkey}.w'], cout, out, cout, 9, name, **kw)
-                pool.free(tmp)
 
         def res_layer(l, x, out_f32):
             p, side, cin, cout = l.key, l.res_out, l.cin, l.cout
             M = N * side * side
-            f16 = self._f16_conv_ok(N, side, cin, cout) and self._f16_conv_ok(N, side, cout, cout)
+            f16 = bool(not fp32_only(side) and bd.f16_conv_ok(N, side, cin, 0, cout, wide=True) and bd.f16_conv_ok(N, side, cout, 0, cout, wide=True))
             if not f16:
-                x = widen(x, cin, side, p + '.x')
-            h1 = pool.alloc(M, cout, f16=f16)
-            gn_conv(x, cin, side, w[f'{p}.n1.g'], w[f'{p}.n1.b'], f'{p}.c1', cout, h1, p + '.conv1', f16)
+                x = fp32_rows(x, cin, side, p + '.x')
+            h1 = bd.alloc(M, cout, f16=f16)
+            bd.gn_conv3x3(x, cin, None, 0, N, side, w[f'{p}.n1.g'], w[f'{p}.n1.b'], w[f'{p}.c1.w'], w[f'{p}.c1.b'], cout, h1, cout, p + '.conv1',
+                          eps=EPS, w16=w.get(f'{p}.c1.w16') if f16 else None, f16=f16)
             short = x
             if cin != cout:         # nin_shortcut (model.py:135-139): a 1x1 convolution of the raw input, added by conv2's epilogue
                 s16 = f16 and x.dtype == torch.float16 and bool(lib.ds_gemm_f16dma_supported(M, cin, cout))
                 if f16 and x.dtype == torch.float16 and not s16:
                     raise NotImplementedError(f'{p}.nin_shortcut: no fp16-activation GEMM for {M} x {cin} -> {cout}')
-                short = pool.alloc(M, cout, f16=s16)
+                short = bd.alloc(M, cout, f16=s16)
                 bd.conv(x, cin, cin, N, side, side, w[f'{p}.nin.w'], cout, short, cout, 1, p + '.nin_shortcut', bias=w[f'{p}.nin.b'])
-                pool.free(x)
-            out = pool.alloc(M, cout, f16=(f16 and not out_f32))
-            gn_conv(h1, cout, side, w[f'{p}.n2.g'], w[f'{p}.n2.b'], f'{p}.c2', cout, out, p + '.conv2', f16, res=short)
-            pool.free(h1, short)
+                bd.free(x)
+            out = bd.alloc(M, cout, f16=(f16 and not out_f32))
+            bd.gn_conv3x3(h1, cout, None, 0, N, side, w[f'{p}.n2.g'], w[f'{p}.n2.b'], w[f'{p}.c2.w'], w[f'{p}.c2.b'], cout, out, cout, p + '.conv2',
+                          eps=EPS, w16=w.get(f'{p}.c2.w16') if f16 else None, f16=f16, res=short, res_ld=cout)
+            bd.free(h1, short)
             return out
 
         def attn_layer(l, x):
@@ -234,22 +167,22 @@ class VAEDecoder:
             M = N * S
             if not lib.ds_attention_supported(c):
                 raise NotImplementedError(f'attention head size {c} has no kernel instantiation')
-            x = widen(x, c, side, p + '.x')
+            x = fp32_rows(x, c, side, p + '.x')
             h16 = bool(self.use_fp16 and lib.ds_gemm_f16dma_supported(M, c, 3 * c))
-            n = pool.alloc(M, c, f16=h16)
+            n = bd.alloc(M, c, f16=h16)
             bd.norm('stats', x, c, c, N, side, side, p + '.norm.stats', groups=32, eps=EPS)
             bd.norm('apply', x, c, c, N, side, side, p + '.norm', groups=32, eps=EPS, gamma=w[f'{p}.n.g'], beta=w[f'{p}.n.b'], out=n, out_ld=c,
                     out_f16=h16)
-            qkv = pool.alloc(M, 3 * c)
+            qkv = bd.alloc(M, 3 * c)
             bd.conv(n, c, c, N, side, side, w[f'{p}.qkv.w'], 3 * c, qkv, 3 * c, 1, p + '.qkv', bias=w[f'{p}.qkv.b'])
-            pool.free(n)
-            ao = pool.alloc(M, c)
+            bd.free(n)
+            ao = bd.alloc(M, c)
             bd.attention(qkv, qkv[:, c:], qkv[:, 2 * c:], ao, p + '.attention', batch=N, heads=1, sq=S, skv=S, d=c, ldq=3 * c, ldk=3 * c,
                          ldv=3 * c, ldo=c, q_bs=S * 3 * c, k_bs=S * 3 * c, v_bs=S * 3 * c, o_bs=S * c, scale=float(c) ** -0.5)
-            pool.free(qkv)
-            out = pool.alloc(M, c)
+            bd.free(qkv)
+            out = bd.alloc(M, c)
             bd.conv(ao, c, c, N, side, side, w[f'{p}.po.w'], c, out, c, 1, p + '.proj_out', bias=w[f'{p}.po.b'], res=x, res_ld=c, stats=True)
-            pool.free(ao, x)
+            bd.free(ao, x)
             return out
 
         cur = None
@@ -258,43 +191,27 @@ class VAEDecoder:
             nxt = layers[i + 1].kind if i + 1 < len(layers) else None
             out_f32 = nxt in ('attn', 'conv_out')            # their kernels read fp32 rows
             if l.kind == 'conv_in':
-                col = pool.alloc(N * R * R, 64)
+                col = bd.alloc(N * R * R, 64)
                 bd.add(lib.ds_stem_im2col, (ptr(bufs['x']), ptr(bufs['one']), 1, 1.0, N, zc + 1, R, R, ptr(col), 64), 'post_quant_conv.im2col')
-                cur = pool.alloc(N * R * R, l.cout)
+                cur = bd.alloc(N * R * R, l.cout)
                 bd.conv(col, 64, 64, N, R, R, w[f'{p}.w'], l.cout, cur, l.cout, 1, p, bias=w[f'{p}.b'], stats=True)
-                pool.free(col)
+                bd.free(col)
             elif l.kind == 'res':
                 cur = res_layer(l, cur, out_f32)
             elif l.kind == 'attn':
                 cur = attn_layer(l, cur)
-            elif l.kind == 'up':
-                side, M = l.res_out, N * l.res_out ** 2
-                f16 = self._f16_conv_ok(N, side, l.cin, l.cout)
-                up = pool.alloc(M, l.cin, f16=f16)          # nearest x2 of the raw tensor (model.py:54)
-                bd.norm('apply', cur, l.cin, l.cin, N, l.res_in, l.res_in, p + '.nearest', use_stats=False, resample=DS_RESAMPLE_UP,
-                        out=up, out_ld=l.cin, out_f16=f16)
-                pool.free(cur)
-                cur = pool.alloc(M, l.cout, f16=(f16 and not out_f32))
-                bd.conv(up, l.cin, l.cin, N, side, side, w[f'{p}.w'], l.cout, cur, l.cout, 9, p + '.conv', bias=w[f'{p}.b'], stats=True,
-                        **(dict(w16=w[f'{p}.w16'], in_f16=True) if f16 else {}))
-                pool.free(up)
+            elif l.kind == 'up':            # nearest x2 of the raw tensor (model.py:54) -> 3x3 conv
+                cur = bd.upsample_conv(cur, l.cin, N, l.res_in, w[f'{p}.w'], w[f'{p}.b'], l.cout, p,
+                                       w16=None if fp32_only(l.res_out) else w.get(f'{p}.w16'), wide=True, out_f32=out_f32, free_src=True)
             elif l.kind == 'conv_out':
                 side = l.res_out
-                cur = widen(cur, l.cin, side, p + '.x')
+                cur = fp32_rows(cur, l.cin, side, p + '.x')
                 bd.norm('stats', cur, l.cin, l.cin, N, side, side, 'decoder.norm_out.stats', groups=32, eps=EPS, gamma=w['out.g'],
-                        beta=w['out.b'], coefs=ncoef)
-                bd.conv(cur, l.cin, l.cin, N, side, side, w[f'{p}.w'], l.cout, bufs['out'], 4, 9, p, bias=w[f'{p}.b'], norm_coefs=ncoef,
+                        beta=w['out.b'], coefs=bd.coefs)
+                bd.conv(cur, l.cin, l.cin, N, side, side, w[f'{p}.w'], l.cout, bufs['out'], 4, 9, p, bias=w[f'{p}.b'], norm_coefs=bd.coefs,
                         norm_act=DS_ACT_SILU, out_nchw=1)
-                pool.free(cur)
-        # a missing kernel is an error at plan time, not at the first decode
-        P.kernel_ids = {}
-        for op in P.ops:
-            if op.fn is lib.ds_conv2d_nhwc:
-                kid = lib.ds_conv_kernel_id(C.byref(op.keep[0]))
-                if kid < 0:
-                    _lib.check(kid, f'VAEDecoder plan: no kernel for {op.name}')
-                P.kernel_ids[op.name] = kid
-        self._plans[N] = P
+                bd.free(cur)
+        self._plans[N] = bd.finish()
         return P
 
     # ------------------------------------------------------------------------------------------ evaluation

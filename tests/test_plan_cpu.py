@@ -150,35 +150,44 @@ def _dtype_lint(P, lib):
 
 
 @pytest.mark.parametrize('name,B,kw', [('cifar10', 4, dict(use_fp16=True)), ('imagenet64', 4, dict(use_fp16=True)), ('imagenet64', 2, dict(use_fp16=True)),
-                                       ('ffhq', 8, dict(use_fp16=True)), ('cifar10', 8, dict()), ('cifar10', 8, dict(split_fp16=True))])
+                                       ('ffhq', 8, dict(use_fp16=True)), ('cifar10', 8, dict()), ('cifar10', 8, dict(split_fp16=True)),
+                                       ('vae.sd15', 1, dict(use_fp16=True)), ('vae.sd15', 3, dict(use_fp16=True)), ('vae.tiny_vae', 2, dict(use_fp16=True))])
 def test_plan_flags_match_the_dtypes_of_the_tensors_they_point_to(name, B, kw):
     """The fp16 residual stream is dtype-driven (plan.Builder sets in_f16 / res_f16 / out_f16 from the tensors it is handed): lint the
     whole plan, including the mixed cases -- the fp32 stem output concatenated with an fp16 stream tensor, CIFAR-10's fp32 attention
-    blocks inside an fp16 stream, batches whose 8x8 layers have no fp16-activation kernel (no fp16 stream then)."""
+    blocks inside an fp16 stream, batches whose 8x8 layers have no fp16-activation kernel (no fp16 stream then) -- and the AutoencoderKL
+    decoder ('vae.<config>'), whose fp16 and fp32 workspaces are recycled from layer to layer (plan.Builder.alloc / free)."""
     lib = _lib.load()
-    spec, eng = _engine(name, **kw)
-    P = eng.plan(B, B)
+    if name.startswith('vae.'):
+        from diff_sampler_amd.vae_engine import VAEDecoder
+        P = VAEDecoder.from_config(name[4:], device='cpu', **kw).plan(B)
+        stream16 = True                                   # the tensors between its fp16-activation layers are fp16 rows at every batch
+    else:
+        spec, eng = _engine(name, **kw)
+        P = eng.plan(B, B)
+        stream16 = P.stream16
     n = _dtype_lint(P, lib)
     assert n > 100
     n16 = sum(1 for op in P.ops if op.fn is lib.ds_conv2d_nhwc and op.keep[0].res_f16)
-    if kw.get('use_fp16') and P.stream16:
+    if kw.get('use_fp16') and stream16:
         assert n16 >= 5, n16
     else:
         assert n16 == 0
 
 
-@pytest.mark.parametrize('N', [2, 4])
-def test_ldm_plan_flags_match_the_dtypes_of_the_tensors_they_point_to(N):
+@pytest.mark.parametrize('N,kw', [pytest.param(2, {}, id='2'), pytest.param(4, {}, id='4'), pytest.param(2, dict(batch_invariant=True), id='2-invariant'),
+                                  pytest.param(4, dict(batch_invariant=True), id='4-invariant')])
+def test_ldm_plan_flags_match_the_dtypes_of_the_tensors_they_point_to(N, kw):
     """The same lint on the latent-diffusion plan (SD-1.5 layer structure at reduced width): the fp16 stream through ResBlocks,
     transformer blocks, upsampling and -- round 4 -- the three strided Downsample convolutions (the gather form of the fp16-activation GEMM:
     fp16 rows in and out, no widened copy); no widened fp32 copies at all since round 6 (the 8x8 layers of a batch that is not a multiple of four
-    take the fp16-activation convolution with empty image slots in their last tile)."""
+    take the fp16-activation convolution with empty image slots in their last tile).  Also in the batch-invariant mode; the plan's fp16 and
+    fp32 temporaries are recycled (plan.Builder.alloc / free), so a flag / dtype mismatch would show here."""
     import diff_sampler_amd.ldm_arch as la
     from diff_sampler_amd.ldm_engine import LDMUNetEngine
     lib = _lib.load()
-    kw = dict(la.NAMED_LDM_CONFIGS['sd15'])
-    spec = la.ldm_unet_spec(**kw)
-    eng = LDMUNetEngine(spec, la.init_ldm_params(spec, seed=0), device='cpu', use_fp16=True)
+    spec = la.ldm_unet_spec(**dict(la.NAMED_LDM_CONFIGS['sd15']))
+    eng = LDMUNetEngine(spec, la.init_ldm_params(spec, seed=0), device='cpu', use_fp16=True, **kw)
     P = eng.plan(N, 1, 77)
     assert P.stream16
     n = _dtype_lint(P, lib)
