@@ -30,7 +30,7 @@ _tune_state = threading.local()
 
 
 class tuning:
-    """``with _lib.tuning(variant=3, mode=256): ...`` -- every ConvArgs CONSTRUCTED on this thread inside the block carries these
+    """``with _lib.tuning(variant=6, mode=256): ...`` -- every ConvArgs CONSTRUCTED on this thread inside the block carries these
     ds_conv_tune overrides (benchmarks, A/B runs, tests).  The state is this thread's default for argument construction on the Python
     side; libdsamd.so itself is stateless: the overrides travel inside each call's (or plan entry's) argument struct."""
 

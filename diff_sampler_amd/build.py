@@ -11,19 +11,13 @@ LIB = os.path.join(CSRC, 'libdsamd.so')
 ARCH = 'gfx950'
 # extra device-compiler flags (experiments: DS_HIPCC_FLAGS="-mllvm -amdgpu-mfma-vgpr-form=0")
 EXTRA_FLAGS = os.environ.get('DS_HIPCC_FLAGS', '').split()
-# DS_BUILD_EXPERIMENTS=1: also build the kernel variants that are kept only as A/B records (docs/HISTORY.md) -- never chosen by the engines:
-# conv3x3_f16dmah.hip (four-wave half-slab fp16 convolution, measured 4 - 19 % slower), conv3x3_halo2_kernel<., 0 / 1> (the hand-scheduled fp32
-# twin and the fp32-activation fp16 kernel that conv3x3_f16dma superseded).  The default library holds the product kernels only;
-# ds_build_experiments() tells a host (and the tests of those variants) which build it loaded.
-EXPERIMENTS = os.environ.get('DS_BUILD_EXPERIMENTS', '0') == '1'
-EXPERIMENT_SOURCES = ('conv3x3_f16dmah.hip',)
 # -fvisibility=hidden: only the DS_API entry points of include/ds_engine.h are exported (tests/test_abi_cpu.py checks the symbol table)
-BASE_FLAGS = ['-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden'] + (['-DDS_BUILD_EXPERIMENTS=1'] if EXPERIMENTS else [])
+BASE_FLAGS = ['-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden']
 STAMP = os.path.join(CSRC, '.build_flags')
 
 
 def sources():
-    return sorted(s for s in glob.glob(os.path.join(CSRC, '*.hip')) if EXPERIMENTS or os.path.basename(s) not in EXPERIMENT_SOURCES)
+    return sorted(glob.glob(os.path.join(CSRC, '*.hip')))
 
 
 def _flags_stamp():

@@ -528,9 +528,8 @@ bool conv3x3_f16dma_applicable(const KParams& p) {
 // The starting width is chosen by a small cost model: a launch of t workgroups takes ceil(t / 256) rounds of tiles, and a tile of
 // 64 * nb columns costs about 1 + nb (the halo stream, the A-fragment reads, prologue and epilogue do not shrink with the width), so
 // a layer with few pixel tiles takes narrower column tiles to cover the 256 CUs.
-// `half`: the four-wave half-slab variant (conv3x3_f16dmah.hip): 128-pixel tiles, two workgroups per CU = 512 tile slots per round.
-static int tiling(const KParams& p, int nb0, int (*out)[3], int* cost, bool half = false) {
-    const int mtiles = (p.M + (half ? 127 : 255)) / (half ? 128 : 256), slots = half ? 512 : 256;
+static int tiling(const KParams& p, int nb0, int (*out)[3], int* cost) {
+    const int mtiles = (p.M + 255) / 256, slots = 256;
     int n = 0, col = 0, c = 0;
     for (int w = nb0; w >= 1 && col < p.N; --w) {
         const int t = (p.N - col) / (64 * w);
@@ -544,21 +543,17 @@ static int tiling(const KParams& p, int nb0, int (*out)[3], int* cost, bool half
     return n;
 }
 
-static int conv3x3_f16dma_plan(const KParams& p, int (*out)[3], bool half) {
-#ifdef DS_BUILD_EXPERIMENTS
-    const int cap = half ? conv3x3_f16dmah_max_nb(p.W) : max_nb(p);
-#else
+static int conv3x3_f16dma_plan(const KParams& p, int (*out)[3]) {
     const int cap = max_nb(p);
-#endif
     int cost;
-    if (p.t_nb > 0) return tiling(p, p.t_nb < cap ? p.t_nb : cap, out, &cost, half);
+    if (p.t_nb > 0) return tiling(p, p.t_nb < cap ? p.t_nb : cap, out, &cost);
     int best_nb = cap, best_cost = 0x7fffffff, best_n = 99;
     for (int nb = cap; nb >= 1; --nb) {
         int tmp[4][3];
-        const int n = tiling(p, nb, tmp, &cost, half);
+        const int n = tiling(p, nb, tmp, &cost);
         if (cost < best_cost || (cost == best_cost && n < best_n)) { best_cost = cost; best_n = n; best_nb = nb; }
     }
-    return tiling(p, best_nb, out, &cost, half);
+    return tiling(p, best_nb, out, &cost);
 }
 
 // Split-K (see the header): S > 1 when the WIDEST tiling of the layer (fewest LDS operand bytes per MFMA) fills at most half of the 256 CUs and
@@ -585,35 +580,16 @@ static int conv3x3_f16dma_splits(const KParams& p, int (*plan)[3], int* n) {
     return (int)s;
 }
 
-// Which layers take the four-wave half-slab variant (two workgroups per CU, conv3x3_f16dmah.hip).  ds_conv_args.tune.f16dma_nw forces it
-// (4) or the eight-wave kernel (8); otherwise by layer class, from the A/B of profiles/r4_conv_f16dmah_ab.txt.
-static bool conv3x3_f16dma_use_half(const KParams& p) {
-#ifdef DS_BUILD_EXPERIMENTS                                    // a recorded negative result: built with DS_BUILD_EXPERIMENTS=1 only, never a default
-    return p.t_nw == 4 && conv3x3_f16dmah_applicable(p);
-#else
-    (void)p;
-    return false;
-#endif
-}
-
 void conv3x3_f16dma_route(const KParams& p, ConvRoute& r) {
-    const bool half = conv3x3_f16dma_use_half(p);
-    r.kernel_id = half ? 2569 : (p.norm ? 2572 : 2566);
-    r.ngroups = conv3x3_f16dma_plan(p, r.groups, half);
-    r.splits = half ? 1 : conv3x3_f16dma_splits(p, r.groups, &r.ngroups);
+    r.kernel_id = p.norm ? 2572 : 2566;
+    r.ngroups = conv3x3_f16dma_plan(p, r.groups);
+    r.splits = conv3x3_f16dma_splits(p, r.groups, &r.ngroups);
 }
 
 int launch_conv3x3_f16dma(KParams& p, const ConvRoute& r, hipStream_t stream) {
     for (int i = 0; i < r.ngroups; ++i) {
         const int col = r.groups[i][0], tiles = r.groups[i][1], nb = r.groups[i][2];
         int rc;
-#ifdef DS_BUILD_EXPERIMENTS
-        if (r.kernel_id == 2569) {
-            rc = launch_conv3x3_f16dmah_tiles(p, nb, col, tiles, stream);
-            if (rc) return rc;
-            continue;
-        }
-#endif
         switch (p.W) {
             case 8: rc = launch_w<8>(p, nb, col, tiles, stream); break;
             case 16: rc = launch_w<16>(p, nb, col, tiles, stream); break;

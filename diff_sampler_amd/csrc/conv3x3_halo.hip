@@ -629,10 +629,7 @@ int launch_wm(KParams& p, const ConvRoute& r, hipStream_t stream) {
     if (wide > 0) {
         const Geo g = geometry(p, 64 * WM, 2);
         int rc;
-        if (r.halo2) {
-            KParams q = p;
-            rc = launch_conv3x3_halo2(q, wide, 0, stream);
-        } else if (r.half_wave) {
+        if (r.half_wave) {
             if constexpr (WM == 2 && GLDS) rc = launch_one<2, true, 4, 0, 1>(p, geometry(p, 128, 4), n256, wide, stream);
             else rc = DS_E_ARG;
         } else if constexpr (GLDS) {
@@ -681,7 +678,7 @@ bool conv3x3_halo_supported(const KParams& p) { return geometry(p, 128).ok; }
 // 192-column tiles for every column of the ADM channel counts (multiples of 192 but not of 256: 192 / 384 / 576; round 3; variant bit 13:
 // off), else 256-column tiles for the first 256-multiples where they apply (384 = 256 + 128, 576 = 2 x 256 + 64, 320 = 256 + 64), the rest on
 // 128-column tiles and a 64-column tail.  Kernel ids: 0 = unsupported, 128 / 256 = M tile of the 128-column kernels, 2565 = the 256 x 256
-// tiles, 2568 = the 256 x 192 tiles, 1284 = 128-pixel tiles on 8 half-size waves, 2560 = the second-generation kernel (tune.variant 3).
+// tiles, 2568 = the 256 x 192 tiles, 1284 = 128-pixel tiles on 8 half-size waves.
 void conv3x3_halo_route(const KParams& layer, ConvRoute& r) {
     KParams p = layer;
     const Geo g128 = geometry(p, 128), g256 = geometry(p, 256);
@@ -709,9 +706,8 @@ void conv3x3_halo_route(const KParams& layer, ConvRoute& r) {
     const int nrest = p.N - r.n256, full = nrest / BN, rem = nrest - full * BN;
     r.tail64 = rem > 0 && rem <= 64 && geometry(p, 64 * WM, 1).ok && use_tail64(p);
     r.n128 = r.tail64 ? full : (nrest + BN - 1) / BN;
-    r.halo2 = WM == 4 && use_glds(p) && (p.t_variant & 31) == 3 && p.splits == 1 && r.n256 == 0 && conv3x3_halo2_applicable(p, r.n128, 0);
     r.half_wave = WM == 2 && use_glds(p) && half_wave_tiles(p, r.n256, r.n128);
-    r.kernel_id = r.halo2 ? 2560 : r.n256 ? 2565 : r.half_wave ? 1284 : r.tile;
+    r.kernel_id = r.n256 ? 2565 : r.half_wave ? 1284 : r.tile;
 }
 
 int launch_conv3x3_halo(KParams& p, const ConvRoute& r, hipStream_t stream) {

@@ -531,8 +531,8 @@ static int route_conv(const ds_conv_args* a, KParams& p, ConvRoute& r) {
     }
     if (a->wgt_f16) {
         if (a->update && (a->update->x_out || a->update->m_out)) return DS_E_ARG;      // the fused solver update exists in the fp32 head kernel only
-        // fp16 operands (1) or split fp16 hi/lo operands (2): second-generation halo kernel only, every 128-column tile (the ragged
-        // last one included)
+        // fp16 operands (1): the 1x1 kernels and the fp16-activation kernels; split fp16 hi/lo operands (2): the second-generation halo
+        // kernel only, every 128-column tile (the ragged last one included)
         if (a->wgt_f16 == 1 && a->taps == 1 && stride == 1) {
             // 1x1 / Linear with fp16 operands: weights [cout_pad][K] halfs in plain K order
             if (a->wgt_shift) return DS_E_ARG;
@@ -577,13 +577,13 @@ static int route_conv(const ds_conv_args* a, KParams& p, ConvRoute& r) {
             p.splits = r.splits;
             return DS_OK;
         }
+        if (a->wgt_f16 != 2) return DS_E_SHAPE;             // fp16 operands on fp32 activations: no kernel (fp16 activations or split operands)
         r.n128 = (p.N + BN - 1) / BN;
-        // row pitch of the fp16 weight matrix in float units: fp16 = K halfs per row, split = 2 K halfs (hi and lo)
-        p.ldb = a->wgt_f16 == 1 ? p.K / 2 : p.K;
+        p.ldb = p.K;                                        // row pitch of the split weight matrix in float units: 2 K halfs (hi and lo)
         p.acc_scale = 1.0f / (float)(1 << a->wgt_shift);
         p.part = nullptr; p.part_cap = 0;
-        if (!conv3x3_halo2_applicable(p, r.n128, a->wgt_f16)) return DS_E_SHAPE;
-        r.kernel_id = a->wgt_f16 == 2 ? 2563 : 2562;
+        if (!conv3x3_halo2_applicable(p, r.n128)) return DS_E_SHAPE;
+        r.kernel_id = 2563;
         return DS_OK;
     }
     const bool generic = p.t_mode == 1;                    // tune.mode 1: the generic gather kernel (A/B runs, cross-checks)
@@ -626,15 +626,15 @@ extern "C" int ds_conv2d_nhwc(const ds_conv_args* a, void* stream) {
     switch (r.kernel_id) {
         case 0: return launch<0>(p, 1, s);
         case 2561: return launch_gemm_dma8(p, s);
-        case 2562: case 2563: return launch_conv3x3_halo2(p, r.n128, a->wgt_f16, s);
+        case 2563: return launch_conv3x3_halo2(p, r.n128, s);
         case 2564: return launch_gemm_f16(p, s);
-        case 2566: case 2569: case 2572: return launch_conv3x3_f16dma(p, r, s);
+        case 2566: case 2572: return launch_conv3x3_f16dma(p, r, s);
         case 2567: return launch_gemm_f16dma(p, s);
         case 2570: return launch_conv3x3_thin(p, s);
         case 2571: return launch_gemm_f16dma(p, s, true);
         case 2573: return launch_gemv_rows(p, s);
         case 2575: return launch_conv3x3_f16wide(p, r, s);
-        default: return launch_conv3x3_halo(p, r, s);      // 128 / 256 / 1284 / 2560 / 2565 / 2568
+        default: return launch_conv3x3_halo(p, r, s);      // 128 / 256 / 1284 / 2565 / 2568
     }
 }
 
@@ -659,14 +659,8 @@ extern "C" int ds_conv_route(const ds_conv_args* a, ds_conv_route_info* info) {
     return DS_OK;
 }
 
-static int reduced_supported(int mode, int n, int h, int w, int c0, int c1, int ec0, int ec1) {
-    KParams p{};
-    p.taps = 9; p.H = h; p.W = w; p.HW = h * w; p.M = n * h * w; p.N = 128; p.c0 = c0; p.c1 = c1; p.ec0 = ec0; p.ec1 = ec1;
-    p.nrows_b = 128;
-    if (!conv3x3_halo2_applicable(p, 1, mode)) return 0;
-    return w >= 16 ? 2 : 1;                      // 8x8: four images per tile, the per-image normalisation planes are not fused
-}
-extern "C" int ds_conv_f16_supported(int n, int h, int w, int c0, int c1, int ec0, int ec1) { return reduced_supported(1, n, h, w, c0, c1, ec0, ec1); }
+// fp16 operands on fp32 activations in a 3x3 layer: no kernel (the fp16-activation kernels replaced it); the entry point stays for the ABI
+extern "C" int ds_conv_f16_supported(int, int, int, int, int, int, int) { return 0; }
 extern "C" int ds_conv_f16dma_supported(int n, int h, int w, int c0, int ec0, int cout) {
     KParams p{};
     p.taps = 9; p.stride = 1; p.H = h; p.W = w; p.HW = h * w; p.M = n * h * w; p.N = cout; p.c0 = c0; p.ec0 = ec0;
@@ -693,7 +687,13 @@ extern "C" int ds_gemm_f16_supported(long long rows, int c0, int c1) {
     p.taps = 1; p.stride = 1; p.M = (int)rows; p.N = 128; p.K = c0 + c1; p.c0 = c0; p.c1 = c1; p.nrows_b = 128;
     return gemm_f16_applicable(p) ? 1 : 0;
 }
-extern "C" int ds_conv_split_supported(int n, int h, int w, int c0, int c1, int ec0, int ec1) { return reduced_supported(2, n, h, w, c0, c1, ec0, ec1); }
+extern "C" int ds_conv_split_supported(int n, int h, int w, int c0, int c1, int ec0, int ec1) {
+    KParams p{};
+    p.taps = 9; p.H = h; p.W = w; p.HW = h * w; p.M = n * h * w; p.N = 128; p.c0 = c0; p.c1 = c1; p.ec0 = ec0; p.ec1 = ec1;
+    p.nrows_b = 128;
+    if (!conv3x3_halo2_applicable(p, 1)) return 0;
+    return w >= 16 ? 2 : 1;                      // 8x8: four images per tile, the per-image normalisation planes are not fused
+}
 
 extern "C" int ds_conv3x3_halo_supported(int h, int w) {
     KParams p{};

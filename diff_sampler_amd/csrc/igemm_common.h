@@ -614,10 +614,10 @@ struct ConvRoute {
     int kernel_id;                 // ds_conv_kernel_id (include/ds_engine.h)
     int splits;                    // split-K factor (1 = none)
     // LDS-halo kernels: M tile (128 / 256) and the column ranges of the layer -- every column on 192-column tiles (cols192), or [0, n256) on
-    // 256-column tiles, then n128 tiles of 128 columns (on the second-generation kernel: halo2, on half-size waves: half_wave) and a
-    // 64-column tail (tail64).  n128 is also the tile count of the fp16-operand halo kernels (kernel ids 2562 / 2563).
+    // 256-column tiles, then n128 tiles of 128 columns (on half-size waves: half_wave) and a 64-column tail (tail64).  n128 is also the
+    // tile count of the split-fp16 halo kernel (kernel id 2563).
     int tile, n256, n128;
-    bool cols192, tail64, half_wave, halo2;
+    bool cols192, tail64, half_wave;
     // fp16-activation 3x3 kernel: column tiling, groups of (first column, tiles, width in 64-channel units), widest first
     int ngroups;
     int groups[4][3];
@@ -628,9 +628,9 @@ bool conv3x3_halo_supported(const KParams& p);
 void conv3x3_halo_route(const KParams& p, ConvRoute& r);    // tile, split-K factor, column ranges, kernel id
 int launch_conv3x3_halo(KParams& p, const ConvRoute& r, hipStream_t stream);
 
-// conv3x3_halo2.hip: second-generation 256 x 128 tile (static tap schedule, double halo buffer)
-bool conv3x3_halo2_applicable(const KParams& p, int wide, int mode);   // mode 0 fp32 / 1 fp16 / 2 split-fp16
-int launch_conv3x3_halo2(KParams& p, int wide, int mode, hipStream_t stream);
+// conv3x3_halo2.hip: second-generation 256 x 128 tile (static tap schedule, double halo buffer), split fp16 hi/lo operands
+bool conv3x3_halo2_applicable(const KParams& p, int wide);
+int launch_conv3x3_halo2(KParams& p, int wide, hipStream_t stream);
 
 // conv3x3_f16dma.hip: 3x3 on fp16 activations, both operands by LDS-DMA, 256-pixel x 64/128/192/256-channel tiles
 // conv3x3_thin.hip: 3x3 layers with at most four output channels (the network heads)
@@ -638,13 +638,8 @@ bool conv3x3_thin_applicable(const KParams& p);
 int conv3x3_thin_check_update(const KParams& p);              // DS_E_ARG: the fused solver update (KParams.upd) does not fit the head
 int launch_conv3x3_thin(KParams& p, hipStream_t stream);
 bool conv3x3_f16dma_applicable(const KParams& p);
-void conv3x3_f16dma_route(const KParams& p, ConvRoute& r);  // kernel id (2566 / 2572, 2569), column tiling, split-K factor
+void conv3x3_f16dma_route(const KParams& p, ConvRoute& r);  // kernel id (2566 / 2572), column tiling, split-K factor
 int launch_conv3x3_f16dma(KParams& p, const ConvRoute& r, hipStream_t stream);
-
-// conv3x3_f16dmah.hip: the same convolution on 128-pixel tiles with 32-channel half slabs, four waves, two workgroups per CU
-bool conv3x3_f16dmah_applicable(const KParams& p);
-int conv3x3_f16dmah_max_nb(int W);
-int launch_conv3x3_f16dmah_tiles(const KParams& p, int nb, int n_begin, int ntiles, hipStream_t stream);
 
 // gemm_f16dma.hip: 1x1 / Linear on fp16 activations (both operands by LDS-DMA)
 bool gemm_f16dma_applicable(const KParams& p);

@@ -632,15 +632,12 @@ extern "C" int ds_copy_rows(const float* src, int src_ld, float* dst, int dst_ld
     return DS_OK;
 }
 
-extern "C" int ds_build_experiments(void) {          // bit 0: DS_BUILD_EXPERIMENTS (A/B-record kernels present); bit 1: DS_RACE_STRESS (tests-only delayed build)
-    int flags = 0;
-#ifdef DS_BUILD_EXPERIMENTS
-    flags |= 1;
-#endif
+extern "C" int ds_build_experiments(void) {          // bit 0: always clear (no build holds A/B-record kernels any more); bit 1: DS_RACE_STRESS (tests-only delayed build)
 #ifdef DS_RACE_STRESS
-    flags |= 2;
+    return 2;
+#else
+    return 0;
 #endif
-    return flags;
 }
 extern "C" int ds_version(void) { return 6; }      // ABI 6: ds_conv_tune.invariant appended; ABI 5: ds_conv_route, ds_attention_variant; ABI 4: ds_norm_args.stats0 / stats1 / tune_variant appended; ABI 3: ds_conv_args.update appended (head-fused solver update), ds_build_experiments(); ABI 2: ds_conv_args.tune / ds_update_args.variant, ds_fid_moments
 

@@ -55,10 +55,9 @@ DS_API int ds_version(void);      /* ABI version; a host must check it before pa
                                * 2 (round 4): ds_conv_args.tune / ds_update_args.variant appended (struct sizes changed), ds_fid_moments added, the
                                * process-global ds_debug_* setters removed. */
 DS_API const char* ds_error_string(int code);
-DS_API int ds_build_experiments(void);   /* build flags.  Bit 0: built with DS_BUILD_EXPERIMENTS=1 -- the library also holds the kernel variants kept as A/B records
-                                          * (conv3x3_f16dmah, conv3x3_halo2 modes 0 / 1: reachable through ds_conv_args.tune only, never chosen by default);
-                                          * clear: the product kernels only -- ds_conv_f16_supported() answers 0 and tune.f16dma_nw = 4 / tune.variant = 3 are
-                                          * ignored for 3x3 layers.  Bit 1 (round 6): a DS_RACE_STRESS build -- tests only: the same kernels with ~2 us delays in the
+DS_API int ds_build_experiments(void);   /* build flags.  Bit 0: always clear (until ABI 6 a build could also hold kernel variants kept as A/B records, docs/HISTORY.md;
+                                          * there is one build now, the product kernels only -- ds_conv_f16_supported() answers 0 and tune.f16dma_nw = 4 /
+                                          * tune.variant = 3 are ignored for 3x3 layers).  Bit 1 (round 6): a DS_RACE_STRESS build -- tests only: the same kernels with ~2 us delays in the
                                           * waves that produce shared LDS contents (csrc/ds_common.h); never shipped as libdsamd.so. */
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -82,7 +81,7 @@ typedef struct ds_conv_tune {
      * any other layer.  (Any non-zero mode or variant keeps the matrix kernels.) */
     int mode;
     /* Kernel variant of the LDS-halo 3x3 convolution.  Low five bits: 0 = default, 1 = software-pipelined tap loop of the 128-column
-     * tiles, 3 = second-generation kernel (conv3x3_halo2.hip) where it applies, 6 / 7 = 256 x 256 tiles forced (tests at small sizes)
+     * tiles, 3 = no kernel of its own any more (once the fp32 twin of conv3x3_halo2.hip), 6 / 7 = 256 x 256 tiles forced (tests at small sizes)
      * / switched off, other values = timing ablations compiled only with -DDS_CONV_ABLATIONS (wrong results on purpose; + 0x10000:
      * ablations of the 256 x 256 tile).  Bit 8 (256): the 256 x 256 tile's plain kernel instead of its default (scalar-addressed weight
      * DMA + non-temporal epilogue); bit 9 (512): multi-image tiles read their GroupNorm coefficient planes from global memory instead of
@@ -93,8 +92,8 @@ typedef struct ds_conv_tune {
     int splits;        /* > 0: split-K factor of a convolution that has a workspace (clamped to what the layer allows; 1 = never split).  The
                         * fp16-activation 3x3 kernel (in_f16) splits on its own where its widest tiling covers at most half of the CUs */
     int f16dma_nb;     /* fp16-activation kernels: column-tile width 64 * nb, nb = 1..4 */
-    int f16dma_nw;     /* fp16-activation GEMM: 4 / 8 = 128- / 256-row variant; fp16-activation 3x3: 4 = the four-wave half-slab kernel on
-                        * 128-pixel tiles (two workgroups per CU, kernel id 2569), 8 = the eight-wave kernel on 256-pixel tiles (2566) */
+    int f16dma_nw;     /* fp16-activation GEMM: 4 / 8 = 128- / 256-row variant; fp16-activation 3x3: ignored (one kernel, eight waves on
+                        * 256-pixel tiles, kernel id 2566 / 2572) */
     /* fp16-activation kernels, benchmarks only (results are WRONG when bits 0 - 5 are set): bit 0: no weight DMA after the prologue,
      * bit 1: no halo DMA after the first slab, bit 2: no epilogue, bit 4: no per-tap barrier, bit 5: no LDS fragment reads; bit 10
      * (results stay correct): fp16 residual rows requested one group ahead instead of early (profiles/r3_gemm_f16dma_epilogue.txt). */
@@ -156,8 +155,8 @@ typedef struct ds_conv_args {
     /* 1: REDUCED-PRECISION OPERANDS, the reference's `use_fp16` / autocast mode (networks_edm.py:486, sample.py:296): `wgt` holds fp16
      * weights packed for 64-channel slabs ([cout_pad][K] halfs, K = (slab64 * 9 + tap) * 64 + c, then the 1x1 extra columns in
      * 64-channel blocks), the kernel rounds the (normalised, activated) input to fp16 while it stages it and multiplies on
-     * v_mfma_f32_32x32x16_f16 with fp32 accumulation; inputs, bias / residual / output tensors stay fp32.  taps == 9 only, and only
-     * where ds_conv_f16_supported() says so -- otherwise DS_E_SHAPE (there is no silent fp32 fallback). */
+     * v_mfma_f32_32x32x16_f16 with fp32 accumulation; inputs, bias / residual / output tensors stay fp32.  On a 3x3 layer only with fp16
+     * activations (in_f16): on fp32 activations ds_conv_f16_supported() answers 0 and the call DS_E_SHAPE (there is no silent fp32 fallback). */
     int wgt_f16;
     /* wgt_f16 == 2: SPLIT-fp16 OPERANDS, fp32 emulated on the fp16 matrix pipe.  Every operand x is represented as hi + lo with
      * hi = fp16(x), lo = fp16(x - hi); a product is hi*hi + hi*lo + lo*hi with fp32 accumulation (the dropped lo*lo term and the
@@ -204,7 +203,7 @@ DS_API int ds_conv2d_nhwc(const ds_conv_args* a, void* stream);
 
 /* Which kernel ds_conv2d_nhwc dispatches this call to: 0 = generic gather kernel (igemm_f32_kernel<0>), 128 / 256 =
  * LDS-halo kernel with that M tile (conv3x3_halo_kernel<2> / <4>), 2561 = 8-wave LDS-DMA 1x1 / Linear kernel
- * (gemm_dma8_kernel), 2562 = fp16-operand halo kernel (conv3x3_halo2_kernel<W, 1>), 2560 = the same kernel on fp32 operands (tune.variant 3), 2563 = split-fp16 (fp32-emulated) halo kernel
+ * (gemm_dma8_kernel), 2563 = split-fp16 (fp32-emulated) halo kernel
  * (conv3x3_halo2_kernel<W, 2>), 2564 = fp16-operand 1x1 / Linear kernel (gemm_f16_kernel), 2565 = LDS-halo kernel <4> with
  * 256-pixel x 256-channel tiles (64 x 128 per wave; channel counts that are multiples of 256 on 16-, 32- and 64-column images), 1284 =
  * LDS-halo kernel with 128-pixel tiles on eight waves of 64 x 32 (layers with at most one tile per CU), 2570 = the thin-output 3x3 kernel
@@ -212,8 +211,7 @@ DS_API int ds_conv2d_nhwc(const ds_conv_args* a, void* stream);
  * 3x3 convolution on fp16 rows (gemm_f16dma_kernel<.., GATHER>), 2573 (round 6) = the 1x1 / Linear on at most four rows (gemv_rows_kernel: the
  * embedding path's one-row projections; one fp32 source, bias / scale / SiLU only, cout >= 64; tune.mode != 0 keeps the matrix kernels), 2566 / 2572 =
  * the fp16-activation 3x3 kernel without / with the fused input normalisation (conv3x3_f16dma_kernel), 2567 = the fp16-activation 1x1 / Linear
- * (gemm_f16dma_kernel), 2568 = LDS-halo kernel <4> with 256-pixel x 192-channel tiles, 2569 = the four-wave half-slab fp16-activation 3x3 kernel
- * (tune.f16dma_nw 4, DS_BUILD_EXPERIMENTS builds), 2575 = the fp16-activation 3x3 kernel on 4 x 64 patches for images wider than 64 pixels
+ * (gemm_f16dma_kernel), 2568 = LDS-halo kernel <4> with 256-pixel x 192-channel tiles, 2575 = the fp16-activation 3x3 kernel on 4 x 64 patches for images wider than 64 pixels
  * (conv3x3_f16wide_kernel: power-of-two sides, one activated fp16 source, no fused normalisation, no appended 1x1 slabs, no split-K; reached only
  * where 2566 does not apply).  ABI 5: the answer comes from the same routing function as the launch, so for arguments
  * ds_conv2d_nhwc rejects it returns the same negative DS_E_* code (until ABI 4 it answered with a kernel id regardless).  Used by bench.py
@@ -222,7 +220,7 @@ DS_API int ds_conv_kernel_id(const ds_conv_args* a);
 
 /* ABI 5: the whole routing decision of a ds_conv2d_nhwc call, without a GPU (host logic only): DS_OK and `info` filled, or the negative DS_E_*
  * code the call would return (info untouched).  f16_groups / f16_widths: the column tiling of the fp16-activation 3x3 kernels (kernel ids
- * 2566 / 2569 / 2572 / 2575) -- groups of equal tiles, widest first, each width in 64-channel units (320 channels = 3 + 2); 0 groups on every other
+ * 2566 / 2572 / 2575) -- groups of equal tiles, widest first, each width in 64-channel units (320 channels = 3 + 2); 0 groups on every other
  * kernel. */
 typedef struct ds_conv_route_info {
     int kernel_id;       /* = ds_conv_kernel_id */
@@ -375,9 +373,9 @@ typedef struct ds_attn_args {
                         multiples of 8; ldv, v_bs of 4) -- the fp16 tensors the reference's qkv projection emits in its fp16 mode
                         (networks_edm.py:171-173; attention.py:168-176 under autocast); `scale` then multiplies the fp32 scores */
     int variant;     /* ABI 4.  ds_attention_f16: 0 = the library's choice (the kernel with one 32-query block per wave,
-                        rounds 2 - 6); 1 = the same, explicitly; 2 = two query blocks per wave, skewed by half a phase (round 6 experiment, measured
-                        5 - 8 % slower and therefore never chosen; head sizes <= 64, else DS_E_SHAPE) -- for benchmarks and tests: results do not
-                        depend on it.  ds_attention (fp32), head sizes that are multiples of 128: 0 = the library's choice -- the channel-split block
+                        rounds 2 - 6); 1 = the same, explicitly; 2 = accepted for compatibility and served by the same kernel (it once chose a kernel with
+                        two query blocks per wave, measured 5 - 8 % slower and removed: docs/HISTORY.md; head sizes <= 64, else DS_E_SHAPE):
+                        results do not depend on it.  ds_attention (fp32), head sizes that are multiples of 128: 0 = the library's choice -- the channel-split block
                         (32 queries, four waves x d / 4 channels) while the query-split grid has fewer than 1 024 waves, i.e. small batches of the
                         single 256-wide head; 1 = query split, 2 = channel split.  The two agree to fp32 rounding (the scores are summed in a
                         different order), not bit for bit; other head sizes ignore the field */

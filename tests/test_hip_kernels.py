@@ -531,19 +531,6 @@ def test_geglu_fused_into_projection(rows, k, inner):
     assert _rel(out.cpu(), y[:, :inner] * F.gelu(y[:, inner:])) < TOL
 
 
-HALO2_CASES = [
-    # B, H(=W), c0, c1, cout, (ec0, ec1), norm, act
-    (1, 16, 32, 0, 128, (0, 0), False, False),        # one tile, one slab
-    (2, 16, 64, 32, 128, (0, 0), True, True),          # dual source
-    (1, 32, 64, 0, 256, (0, 0), True, True),           # 4 row tiles x 2 column tiles per image
-    (2, 32, 32, 32, 128, (64, 32), True, True),        # fused 1x1 skip projection slabs (dual extra source)
-    (1, 32, 96, 0, 192, (32, 0), True, False),         # ragged channel count: 128-column tile here + 64-column tail on kernel 1
-    (1, 64, 32, 0, 128, (0, 0), True, True),           # W = 64 (7 halo slots per thread)
-    (1, 64, 32, 32, 128, (32, 0), False, False),
-    (3, 16, 288, 0, 128, (0, 0), True, True),          # 9 slabs (weight-buffer parity flips every slab)
-]
-
-
 def _run_halo_case(case, variant, workspace=False, tile=256, want_kid=None):
     """One fused 3x3 layer (dual source, fused normalisation + SiLU, 1x1 skip columns, bias, per-image bias, residual, scale,
     epilogue statistics) through ds_conv2d_nhwc with the 256-pixel tile forced and the given kernel variant; checked against ATen."""
@@ -597,8 +584,6 @@ def _run_halo_case(case, variant, workspace=False, tile=256, want_kid=None):
     rc = lib.ds_conv2d_nhwc(C.byref(a), _lib.stream_ptr())
     torch.cuda.synchronize()
     assert rc == 0, lib.ds_error_string(rc)
-    if variant == 3:
-        assert kid == 2560, 'the layer was not routed to the second-generation kernel'
     if want_kid is not None:
         assert kid == want_kid, (kid, want_kid)
     if (variant & 31) == 6:
@@ -611,23 +596,6 @@ def _run_halo_case(case, variant, workspace=False, tile=256, want_kid=None):
         st = stats.cpu().reshape(-1, 2, cout)
         blocks = want.reshape(-1, 64, cout)
         assert _rel(st[:, 0], blocks.sum(1)) < 1e-4 and _rel(st[:, 1], (blocks ** 2).sum(1)) < 1e-4
-
-
-def _need_experiments():
-    """The kernel variants kept as A/B records (conv3x3_halo2 modes 0 / 1, conv3x3_f16dmah) are compiled only with DS_BUILD_EXPERIMENTS=1
-    (diff_sampler_amd/build.py); the default library -- what the engines run -- does not hold them."""
-    from diff_sampler_amd import _lib
-    if not _lib.load().ds_build_experiments() & 1:
-        pytest.skip('experimental kernel variant: build with DS_BUILD_EXPERIMENTS=1')
-
-
-
-@pytest.mark.parametrize('case', HALO2_CASES)
-def test_conv_halo2_kernel_matches_aten(case):
-    """Second-generation 256 x 128 halo kernel (conv3x3_halo2.hip), routed by ds_conv_tune.variant = 3 with the 256-pixel tile
-    forced; the routing itself is asserted through the launch counter."""
-    _need_experiments()
-    _run_halo_case(case, 3)
 
 
 WIDE_N_CASES = [
@@ -701,101 +669,16 @@ def test_conv_half_wave_tiles_match_aten(case, variant):
     (two per SIMD) instead of four of 64 x 64 (kernel id 1284; variant bit 11 switches back to the four-wave kernel, id 128)."""
     _run_halo_case(case, variant, workspace=True, tile=128, want_kid=1284 if variant == 0 else 128)
 
-F16_CASES = [
-    # B, H(=W), c0, c1, cout, (ec0, ec1), norm, act
-    (1, 16, 64, 0, 128, (0, 0), False, False),
-    (2, 16, 128, 64, 128, (0, 0), True, True),          # dual source, 3 slabs
-    (1, 32, 64, 0, 256, (0, 0), True, True),
-    (2, 32, 64, 64, 192, (128, 64), True, True),        # skip-projection slabs; ragged 192 = one full + one half-empty tile
-    (1, 64, 64, 0, 128, (64, 0), True, False),          # W = 64
-    (4, 8, 128, 0, 128, (0, 0), False, False),          # 8x8: four images per tile, raw input
-    (8, 8, 64, 64, 320, (64, 0), False, False),
-    (3, 16, 576, 0, 64, (0, 0), True, True),            # 9 slabs, cout below one tile
-]
-
-
-@pytest.mark.parametrize('case', F16_CASES)
-def test_conv_f16_operands_matches_fp16_rounded_reference(case):
-    """Reduced-precision mode (ds_conv_args.wgt_f16): fp16 operands on v_mfma_f32_32x32x16_f16, fp32 accumulation.  The reference
-    is the SAME arithmetic on the CPU: input normalised/activated in fp32, rounded to fp16; weights rounded to fp16; products summed
-    in fp64.  Tolerance 2e-3 of the output scale (a device exp that differs in the last bit can move an operand by one fp16 ulp);
-    the distance to the pure fp32 convolution is reported against the fp16 rounding bound 3e-3."""
-    import ctypes as C
-    from diff_sampler_amd import _lib, ops
-    _need_experiments()
-    B, H, c0, c1, cout, (ec0, ec1), use_norm, act = case
-    lib = _lib.load()
-    sup = lib.ds_conv_f16_supported(B, H, H, c0, c1, ec0, ec1)
-    assert sup >= (2 if use_norm else 1)
-    g = torch.Generator().manual_seed(sum(case[:5]) + 11)
-    x = torch.randn(B, c0 + c1, H, H, generator=g)
-    e = torch.randn(B, ec0 + ec1, H, H, generator=g) if ec0 else None
-    w = torch.randn(cout, c0 + c1, 3, 3, generator=g) / (9 * (c0 + c1)) ** 0.5
-    we = torch.randn(cout, ec0 + ec1, 1, 1, generator=g) / (ec0 + ec1) ** 0.5 if ec0 else None
-    bias = torch.randn(cout, generator=g)
-    cb = torch.randn(B, cout, generator=g)
-    res = torch.randn(B, cout, H, H, generator=g)
-    mu = torch.randn(B, c0 + c1, generator=g) * 0.3
-    ga = 1 + 0.2 * torch.randn(B, c0 + c1, generator=g)
-    be = 0.2 * torch.randn(B, c0 + c1, generator=g)
-    xin = x
-    if use_norm:
-        xin = (x - mu[:, :, None, None]) * ga[:, :, None, None] + be[:, :, None, None]
-        xin = F.silu(xin) if act else xin
-    h16 = lambda t: t.to(torch.float16).to(torch.float64)
-    ref16 = F.conv2d(h16(xin), h16(w), padding=1)
-    ref32 = F.conv2d(xin, w, padding=1)
-    if ec0:
-        ref16 = ref16 + F.conv2d(h16(e), h16(we))
-        ref32 = ref32 + F.conv2d(e, we)
-    tail = (bias[None, :, None, None] + cb[:, :, None, None] + res)
-    ref16 = ((ref16 + tail.double()) * 0.7071).float()
-    ref32 = (ref32 + tail) * 0.7071
-    dev = 'cuda'
-    xn = _nhwc(x).to(dev)
-    x0 = xn[:, :c0].contiguous()
-    x1 = xn[:, c0:].contiguous() if c1 else None
-    en = _nhwc(e).to(dev) if ec0 else None
-    e0 = en[:, :ec0].contiguous() if ec0 else None
-    e1 = en[:, ec0:].contiguous() if ec1 else None
-    wp = ops.pack_conv_weight_f16(w.to(dev), we.to(dev) if ec0 else None)
-    coefs = torch.stack([mu, ga, be], 1).contiguous().to(dev) if use_norm else None
-    old = cout if cout % 4 == 0 else -(-cout // 4) * 4
-    out = torch.full((B * H * H, old), float('nan'), device=dev)
-    biasd, cbd, resd = bias.to(dev), cb.to(dev), _nhwc(res).to(dev)
-    a = _lib.ConvArgs(x0.data_ptr(), x1.data_ptr() if c1 else None, c0, c1, c0, c1, B, H, H, 9, wp.data_ptr(), cout, biasd.data_ptr(),
-                      cbd.data_ptr(), cout, B, resd.data_ptr(), cout, 0.7071, 0, out.data_ptr(), old,
-                      coefs.data_ptr() if use_norm else None, 1 if act else 0,
-                      e0.data_ptr() if ec0 else None, e1.data_ptr() if ec1 else None, ec0, ec1, ec0, ec1)
-    a.wgt_f16 = 1
-    assert lib.ds_conv_kernel_id(C.byref(a)) == 2562          # conv3x3_halo2_kernel<W, fp16 operands>
-    rc = lib.ds_conv2d_nhwc(C.byref(a), _lib.stream_ptr())
-    torch.cuda.synchronize()
-    assert rc == 0, lib.ds_error_string(rc)
-    got = out[:, :cout].cpu()
-    assert _rel(got, _nhwc(ref16)) < 2e-3
-    assert _rel(got, _nhwc(ref32)) < 3e-3
-
 
 def test_conv_f16_unsupported_geometry_fails_loudly():
     import ctypes as C
     from diff_sampler_amd import _lib
     lib = _lib.load()
-    if not lib.ds_build_experiments() & 1:                                   # default build: no fp32-activation fp16 kernel at all
-        assert lib.ds_conv_f16_supported(4, 8, 8, 64, 0, 0, 0) == 0 and lib.ds_conv_f16_supported(1, 16, 16, 64, 64, 64, 0) == 0
-        x = torch.zeros(4 * 64, 64, device='cuda'); w = torch.zeros(128, 64 * 9 // 2, device='cuda'); o = torch.zeros(4 * 64, 64, device='cuda')
-        a = _lib.ConvArgs(x.data_ptr(), None, 64, 0, 64, 0, 4, 8, 8, 9, w.data_ptr(), 64, None, None, 0, 1, None, 0, 1.0, 0, o.data_ptr(), 64)
-        a.wgt_f16 = 1
-        assert lib.ds_conv2d_nhwc(C.byref(a), None) == -3                   # DS_E_SHAPE, no silent fp32 fallback
-        return
-    assert lib.ds_conv_f16_supported(1, 32, 32, 96, 0, 0, 0) == 0          # 96 channels: not a multiple of 64
-    assert lib.ds_conv_f16_supported(3, 8, 8, 64, 0, 0, 0) == 0            # 8x8 needs whole tiles of four images
-    assert lib.ds_conv_f16_supported(1, 4, 4, 64, 0, 0, 0) == 0
-    assert lib.ds_conv_f16_supported(4, 8, 8, 64, 0, 0, 0) == 1 and lib.ds_conv_f16_supported(1, 16, 16, 64, 64, 64, 0) == 2
-    x = torch.zeros(3 * 64, 64, device='cuda'); w = torch.zeros(128, 64 * 9 // 2, device='cuda'); o = torch.zeros(3 * 64, 64, device='cuda')
-    a = _lib.ConvArgs(x.data_ptr(), None, 64, 0, 64, 0, 3, 8, 8, 9, w.data_ptr(), 64, None, None, 0, 1, None, 0, 1.0, 0, o.data_ptr(), 64)
-    a.wgt_f16 = 1
-    assert lib.ds_conv2d_nhwc(C.byref(a), None) == -3                       # DS_E_SHAPE, no silent fp32 fallback
+    assert lib.ds_conv_f16_supported(4, 8, 8, 64, 0, 0, 0) == 0 and lib.ds_conv_f16_supported(1, 16, 16, 64, 64, 64, 0) == 0
+    x = torch.zeros(4 * 64, 64, device='cuda'); w = torch.zeros(128, 64 * 9 // 2, device='cuda'); o = torch.zeros(4 * 64, 64, device='cuda')
+    a = _lib.ConvArgs(x.data_ptr(), None, 64, 0, 64, 0, 4, 8, 8, 9, w.data_ptr(), 64, None, None, 0, 1, None, 0, 1.0, 0, o.data_ptr(), 64)
+    a.wgt_f16 = 1                                                       # fp16 operands on fp32 activations: no kernel
+    assert lib.ds_conv2d_nhwc(C.byref(a), None) == -3                   # DS_E_SHAPE, no silent fp32 fallback
 
 
 SPLIT_CASES = [
@@ -1024,14 +907,12 @@ def test_conv_f16_activations_dma_kernel(case, nw):
     """ds_conv2d_nhwc with in_f16 (csrc/conv3x3_f16dma.hip): the input is an fp16 NHWC tensor, both operands go to LDS by DMA, column tiles
     of 64 / 128 / 192 / 256 channels.  Reference = the same arithmetic on the CPU (fp16 operands, products summed in fp64): 2e-5 of the
     output scale -- only the fp32 accumulation order differs; the GroupNorm column sums the epilogue leaves are checked too.
-    nw = 8: the eight-wave kernel on 256-pixel tiles (kernel id 2566); nw = 4: the four-wave half-slab variant on 128-pixel tiles, two
-    workgroups per CU (csrc/conv3x3_f16dmah.hip, kernel id 2569) -- forced per call through ds_conv_tune.f16dma_nw."""
+    The eight-wave kernel on 256-pixel tiles (kernel id 2566) is the only one: ds_conv_tune.f16dma_nw = 4, which once chose a four-wave
+    variant (docs/HISTORY.md), is ignored on a 3x3 layer -- nw = 4 must route to 2566 and give the same checked result as nw = 8."""
     import ctypes as C
     from diff_sampler_amd import _lib, ops
     B, H, cin, cout, ec0, nb, with_stats = case
     lib = _lib.load()
-    if nw == 4:
-        _need_experiments()
     assert lib.ds_conv_f16dma_supported(B, H, H, cin, ec0, cout) == 1
     g = torch.Generator().manual_seed(sum(case[:5]) + 5)
     x = torch.randn(B, cin, H, H, generator=g).to(torch.float16)
@@ -1060,7 +941,7 @@ def test_conv_f16_activations_dma_kernel(case, nw):
     if with_stats:
         a.stats_out = stats.data_ptr()
     a.tune.f16dma_nb, a.tune.f16dma_nw = nb, nw
-    assert lib.ds_conv_kernel_id(C.byref(a)) == (2566 if nw == 8 else 2569)
+    assert lib.ds_conv_kernel_id(C.byref(a)) == 2566
     rc = lib.ds_conv2d_nhwc(C.byref(a), _lib.stream_ptr())
     torch.cuda.synchronize()
     assert rc == 0, lib.ds_error_string(rc)
@@ -1802,12 +1683,11 @@ def test_fused_attention_reads_fp16_q_k_v(d, heads, sq, skv, mask):
 @pytest.mark.parametrize('d,heads,sq,skv,mask,out16', [(40, 8, 1024, 1024, 3, 1), (40, 4, 4096, 4096, 3, 1), (64, 6, 1024, 1024, 3, 1), (64, 9, 256, 256, 3, 0),
                                                         (40, 8, 300, 77, 1, 0), (32, 3, 130, 130, 2, 0), (64, 2, 64, 200, 0, 1), (40, 2, 257, 515, 3, 1)])
 def test_fused_attention_two_query_blocks_per_wave_equals_the_one_block_kernel(d, heads, sq, skv, mask, out16):
-    """flash_attn_f16x2_kernel (round 6: a wave owns two 32-query blocks, skewed by half a phase; csrc/attention_f16.hip) against
-    flash_attn_f16_kernel (one block per wave) through ds_attn_args.variant = 2 / 1: the same MFMA operands in the same order and the same
-    softmax expressions per query => EQUAL bits, fp16 or fp32 operand tensors, fp16 or fp32 output rows, ragged query / key counts
-    (partial last query block, partial last key tile, a workgroup whose later waves have no queries).  The library's own choice (variant 0)
-    is the one-block kernel: the two-block form measured 5 - 8 % slower (profiles/r6_attn_f16_two_blocks_ab.txt) and is kept as that record;
-    head sizes above 64 refuse variant 2."""
+    """ds_attn_args.variant = 2 / 1 / 0 of ds_attention_f16 (csrc/attention_f16.hip): the header promises that results do not depend on the
+    field => EQUAL bits, fp16 or fp32 operand tensors, fp16 or fp32 output rows, ragged query / key counts (partial last query block,
+    partial last key tile, a workgroup whose later waves have no queries).  Variant 2 once chose a kernel with two query blocks per wave
+    (measured 5 - 8 % slower and removed: profiles/r6_attn_f16_two_blocks_ab.txt, docs/HISTORY.md); flash_attn_f16_kernel now serves all
+    three, and head sizes above 64 still refuse variant 2."""
     import ctypes as C
     from diff_sampler_amd import _lib
     lib = _lib.load()

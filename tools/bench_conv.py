@@ -56,7 +56,7 @@ ap.add_argument('--only', type=int, nargs='*')
 ap.add_argument('--variants', type=int, nargs='*', default=None)
 ap.add_argument('--rounds', type=int, default=5)
 ap.add_argument('--split', action='store_true', help='split-fp16 fp32-emulated kernel (wgt_f16 = 2), 3x3 shapes only')
-ap.add_argument('--f16', action='store_true', help='fp16-operand kernel (ds_conv_args.wgt_f16), 3x3 shapes only')
+ap.add_argument('--f16', action='store_true', help='fp16 operands (ds_conv_args.wgt_f16 = 1); needs --dma16: the fp16 kernels of these shapes read fp16 activations')
 ap.add_argument('--dma16', action='store_true', help='with --f16: fp16 ACTIVATIONS (ds_conv_args.in_f16, csrc/conv3x3_f16dma.hip); single source (c0 + c1 channels), no --norm')
 ap.add_argument('--nb', type=int, default=0, help='with --dma16: force the column-tile width (64 * nb)')
 ap.add_argument('--lda', type=int, default=0, help='with --dma16: override the leading dimension of the fp16 input (timing experiments on access locality; results are then meaningless)')
