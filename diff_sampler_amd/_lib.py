@@ -158,9 +158,19 @@ class StemIm2colArgs(C.Structure):
                 ('h', C.c_int), ('w', C.c_int), ('out', vp), ('kpad', C.c_int)]
 
 
+class TokenEmbedArgs(C.Structure):
+    _fields_ = [('tokens', vp), ('tok_table', vp), ('pos_table', vp), ('out', vp), ('out_ld', C.c_int), ('batch', C.c_int), ('seq', C.c_int),
+                ('width', C.c_int), ('vocab', C.c_int)]
+
+
+class QuickGeluArgs(C.Structure):
+    _fields_ = [('x', vp), ('ldx', C.c_int), ('y', vp), ('ldy', C.c_int), ('rows', C.c_longlong), ('cols', C.c_int)]
+
+
 # ds_plan_add op codes (include/ds_engine.h)
 DS_OP_CONV2D, DS_OP_GEMM, DS_OP_GN_STATS, DS_OP_NORM_ACT, DS_OP_GN_FINALIZE, DS_OP_ATTENTION, DS_OP_ATTENTION_F16, DS_OP_LAYERNORM, \
-    DS_OP_GEGLU, DS_OP_NOISE_EMBED, DS_OP_STEM_IM2COL, DS_OP_LAYERNORM_F16, DS_OP_LAYERNORM_F16IO = range(1, 14)
+    DS_OP_GEGLU, DS_OP_NOISE_EMBED, DS_OP_STEM_IM2COL, DS_OP_LAYERNORM_F16, DS_OP_LAYERNORM_F16IO, DS_OP_TOKEN_EMBED, \
+    DS_OP_ATTENTION_CAUSAL, DS_OP_QUICK_GELU = range(1, 17)
 
 _SIGNATURES = {
     'ds_version': (C.c_int, []),
@@ -186,6 +196,10 @@ _SIGNATURES = {
     'ds_attention_supported': (C.c_int, [C.c_int]),
     'ds_attention_f16': (C.c_int, [C.POINTER(AttnArgs), vp]),
     'ds_attention_f16_supported': (C.c_int, [C.c_int]),
+    'ds_attention_causal': (C.c_int, [C.POINTER(AttnArgs), vp]),
+    'ds_attention_causal_supported': (C.c_int, [C.c_int, C.c_int]),
+    'ds_quick_gelu': (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_longlong, C.c_int, vp]),
+    'ds_token_embed': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     'ds_layernorm_rows': (C.c_int, [vp, C.c_int, vp, vp, C.c_float, vp, C.c_int, C.c_longlong, C.c_int, vp]),
     'ds_layernorm_rows_f16': (C.c_int, [vp, C.c_int, vp, vp, C.c_float, vp, C.c_int, C.c_longlong, C.c_int, vp]),
     'ds_layernorm_rows_f16io': (C.c_int, [vp, C.c_int, vp, vp, C.c_float, vp, C.c_int, C.c_longlong, C.c_int, vp]),

@@ -11,6 +11,7 @@ namespace {
 union ArgBlob {
     ds_conv_args conv; ds_gemm_args gemm; ds_norm_args norm; ds_gn_finalize_args fin; ds_attn_args attn;
     ds_layernorm_args ln; ds_geglu_args geglu; ds_noise_embed_args ne; ds_stem_im2col_args stem;
+    ds_token_embed_args tok; ds_quick_gelu_args qg;
 };
 
 struct Node { int op; ArgBlob a; };
@@ -21,11 +22,13 @@ size_t arg_size(int op) {
         case DS_OP_GEMM: return sizeof(ds_gemm_args);
         case DS_OP_GN_STATS: case DS_OP_NORM_ACT: return sizeof(ds_norm_args);
         case DS_OP_GN_FINALIZE: return sizeof(ds_gn_finalize_args);
-        case DS_OP_ATTENTION: case DS_OP_ATTENTION_F16: return sizeof(ds_attn_args);
+        case DS_OP_ATTENTION: case DS_OP_ATTENTION_F16: case DS_OP_ATTENTION_CAUSAL: return sizeof(ds_attn_args);
         case DS_OP_LAYERNORM: case DS_OP_LAYERNORM_F16: case DS_OP_LAYERNORM_F16IO: return sizeof(ds_layernorm_args);
         case DS_OP_GEGLU: return sizeof(ds_geglu_args);
         case DS_OP_NOISE_EMBED: return sizeof(ds_noise_embed_args);
         case DS_OP_STEM_IM2COL: return sizeof(ds_stem_im2col_args);
+        case DS_OP_TOKEN_EMBED: return sizeof(ds_token_embed_args);
+        case DS_OP_QUICK_GELU: return sizeof(ds_quick_gelu_args);
         default: return 0;
     }
 }
@@ -50,6 +53,10 @@ int issue(const Node& n, void* stream) {
             return ds_noise_embed(e.sigma, e.bs, e.freqs, e.nch, e.swap, e.out, e.out_ld, stream); }
         case DS_OP_STEM_IM2COL: { const ds_stem_im2col_args& s = n.a.stem;
             return ds_stem_im2col(s.x, s.sigma, s.sigma_rows, s.sigma_data, s.n, s.c, s.h, s.w, s.out, s.kpad, stream); }
+        case DS_OP_TOKEN_EMBED: { const ds_token_embed_args& e = n.a.tok;
+            return ds_token_embed(e.tokens, e.tok_table, e.pos_table, e.out, e.out_ld, e.batch, e.seq, e.width, e.vocab, stream); }
+        case DS_OP_ATTENTION_CAUSAL: return ds_attention_causal(&n.a.attn, stream);
+        case DS_OP_QUICK_GELU: { const ds_quick_gelu_args& g = n.a.qg; return ds_quick_gelu(g.x, g.ldx, g.y, g.ldy, g.rows, g.cols, stream); }
         default: return DS_E_ARG;
     }
 }

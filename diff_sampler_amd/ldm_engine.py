@@ -355,12 +355,15 @@ class CFGDenoiser(CFGSchedule):
     host_sigma_ok = True       # solvers._Run: pass sigma as a Python float (c_noise is host math; nothing to copy or sync)
 
     def __init__(self, spec: ldm_arch.LDMUNetSpec, params: Dict[str, torch.Tensor], device='cuda', guidance_rate=None,
-                 guidance_type=None, use_fp16=False, batch_invariant=False, decoder=None, **engine_kw):
+                 guidance_type=None, use_fp16=False, batch_invariant=False, decoder=None, text_encoder=None, **engine_kw):
         """batch_invariant: same seed, same bits at any batch (LDMUNetEngine).
         decoder: optional vae_engine.VAEDecoder -- the first stage that turns this denoiser's latents into images (``net.decoder(z)``, the
-        reference's ``net.model.decode_first_stage``); not used by the denoiser itself."""
+        reference's ``net.model.decode_first_stage``); not used by the denoiser itself.
+        text_encoder: optional clip_engine.ClipTextEncoder -- the conditioning stage (``net.text_encoder(tokens)``, the reference's
+        ``net.model.get_learned_conditioning`` after its tokenizer); not used by the denoiser itself either."""
         self.spec = spec
         self.decoder = decoder
+        self.text_encoder = text_encoder
         self.engine = LDMUNetEngine(spec, params, device, use_fp16=use_fp16, batch_invariant=batch_invariant, **engine_kw)
         self.batch_invariant = bool(batch_invariant)
         self.device = self.engine.device

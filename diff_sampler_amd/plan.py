@@ -222,11 +222,13 @@ def _native_plan(ops):
     lib = _lib.load()
     by_ref = {id(lib.ds_conv2d_nhwc): _lib.DS_OP_CONV2D, id(lib.ds_gemm_nt_batched): _lib.DS_OP_GEMM, id(lib.ds_gn_stats): _lib.DS_OP_GN_STATS,
               id(lib.ds_norm_act): _lib.DS_OP_NORM_ACT, id(lib.ds_gn_finalize): _lib.DS_OP_GN_FINALIZE,
-              id(lib.ds_attention): _lib.DS_OP_ATTENTION, id(lib.ds_attention_f16): _lib.DS_OP_ATTENTION_F16}
+              id(lib.ds_attention): _lib.DS_OP_ATTENTION, id(lib.ds_attention_f16): _lib.DS_OP_ATTENTION_F16,
+              id(lib.ds_attention_causal): _lib.DS_OP_ATTENTION_CAUSAL}
     by_val = {id(lib.ds_layernorm_rows): (_lib.DS_OP_LAYERNORM, _lib.LayerNormArgs), id(lib.ds_geglu): (_lib.DS_OP_GEGLU, _lib.GegluArgs),
               id(lib.ds_noise_embed): (_lib.DS_OP_NOISE_EMBED, _lib.NoiseEmbedArgs), id(lib.ds_stem_im2col): (_lib.DS_OP_STEM_IM2COL, _lib.StemIm2colArgs),
               id(lib.ds_layernorm_rows_f16): (_lib.DS_OP_LAYERNORM_F16, _lib.LayerNormArgs),
-              id(lib.ds_layernorm_rows_f16io): (_lib.DS_OP_LAYERNORM_F16IO, _lib.LayerNormArgs)}
+              id(lib.ds_layernorm_rows_f16io): (_lib.DS_OP_LAYERNORM_F16IO, _lib.LayerNormArgs),
+              id(lib.ds_token_embed): (_lib.DS_OP_TOKEN_EMBED, _lib.TokenEmbedArgs), id(lib.ds_quick_gelu): (_lib.DS_OP_QUICK_GELU, _lib.QuickGeluArgs)}
     h = C.c_void_p()
     _lib.check(lib.ds_plan_create(C.byref(h)), 'ds_plan_create')
     try:
@@ -654,6 +656,21 @@ class Builder:
         if self.invariant and not f16 and d % 128 == 0:
             a.variant = 2           # invariant: the channel-split block at every batch (ds_attention_variant)
         self.add(self.lib.ds_attention_f16 if f16 else self.lib.ds_attention, (C.byref(a),), name, keep=(a,))
+
+    def attention_causal(self, q, k, v, out, name, *, batch, heads, s, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale):
+        """Causal self-attention over `s` tokens (csrc/text_encoder.hip: the CLIP text encoder); fp32 in every mode."""
+        assert all(t.dtype == torch.float32 for t in (q, k, v, out)), name
+        if not self.lib.ds_attention_causal_supported(d, s):
+            raise NotImplementedError(f'{name}: no causal attention kernel for head size {d} over {s} tokens')
+        a = AttnArgs(ptr(q), ptr(k), ptr(v), ptr(out), ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, batch, heads, s, s, d, scale)
+        self.add(self.lib.ds_attention_causal, (C.byref(a),), name, keep=(a,))
+
+    def token_embed(self, tokens, tok_table, pos_table, out, out_ld, batch, seq, width, vocab, name):
+        assert tokens.dtype == torch.int32 and tokens.numel() == batch * seq, name
+        self.add(self.lib.ds_token_embed, (ptr(tokens), ptr(tok_table), ptr(pos_table), ptr(out), out_ld, batch, seq, width, vocab), name)
+
+    def quick_gelu(self, x, ldx, y, ldy, rows, cols, name):
+        self.add(self.lib.ds_quick_gelu, (ptr(x), ldx, ptr(y), ldy, rows, cols), name)
 
     def layernorm(self, x, ldx, gamma, beta, eps, y, ldy, rows, cols, name):
         if x.dtype == torch.float16:          # a tensor of the fp16 residual stream

@@ -231,8 +231,12 @@ SOLVER_FNS = dict(euler='euler_sampler', heun='heun_sampler', dpm='dpm_2_sampler
 
 # ------------------------------------------------------------------------------------------------------------------
 def create_model(dataset_name=None, model_path=None, random_init=False, device=None, seed=0, guidance_type=None, guidance_rate=None,
-                 use_fp16=False, batch_invariant=False, decode_latents=False):
-    """decode_latents (ms_coco): also build the AutoencoderKL decoder (vae_engine.VAEDecoder: the reference's decode_first_stage, sample.py:299)
+                 use_fp16=False, batch_invariant=False, decode_latents=False, text_encoder=False):
+    """text_encoder (ms_coco): also build the CLIP text encoder (clip_engine.ClipTextEncoder: the reference's get_learned_conditioning,
+    sample.py:286-289) and hand it over as ``net.text_encoder`` -- from the checkpoint's ``cond_stage_model.transformer.*`` tensors, or
+    random-init like the U-Net.  fp32 whatever `use_fp16` says: the reference encodes outside autocast.
+
+    decode_latents (ms_coco): also build the AutoencoderKL decoder (vae_engine.VAEDecoder: the reference's decode_first_stage, sample.py:299)
     and hand it over as ``net.decoder`` -- from the checkpoint's ``first_stage_model.decoder.*`` / ``first_stage_model.post_quant_conv.*``
     tensors, or random-init like the U-Net.
 
@@ -254,12 +258,25 @@ def create_model(dataset_name=None, model_path=None, random_init=False, device=N
         assert guidance_type == 'cfg', 'ms_coco samples with classifier-free guidance (sample.py:112)'
         spec = ldm_arch.ldm_unet_spec(**ldm_arch.NAMED_LDM_CONFIGS['sd15'])
         vae_params = None
+        clip_sd = None
         if random_init or model_path is None:
             params = ldm_arch.init_ldm_params(spec, seed=seed)
         else:                                   # SD checkpoint: the U-Net lives under 'model.diffusion_model.' (ddpm.py:1399)
             sd = torch.load(model_path, map_location='cpu')
             sd = sd.get('state_dict', sd)
             params, vae_params = split_sd_checkpoint(sd)
+            if text_encoder:
+                from . import clip_arch
+                clip_sd = clip_arch.split_cond_stage(sd)
+        encoder = None
+        if text_encoder:
+            from .clip_engine import ClipTextEncoder
+            if random_init or model_path is None:
+                encoder = ClipTextEncoder.from_config('sd15', seed=seed, device=device, batch_invariant=bool(batch_invariant))
+            elif not clip_sd:
+                raise ValueError(f'--tokenizer_path: {model_path} holds no cond_stage_model.transformer.* tensors')
+            else:
+                encoder = ClipTextEncoder.from_state_dict(clip_sd, device=device, batch_invariant=bool(batch_invariant))
         decoder = None
         if decode_latents:
             from . import vae_arch
@@ -273,7 +290,7 @@ def create_model(dataset_name=None, model_path=None, random_init=False, device=N
                 vae_params = vae_arch.vae_params_from_state_dict(vspec, vae_params)
             decoder = VAEDecoder(vspec, vae_params, device, use_fp16=bool(use_fp16), batch_invariant=bool(batch_invariant))
         return CFGDenoiser(spec, params, device, guidance_rate=(7.5 if guidance_rate is None else guidance_rate), use_fp16=bool(use_fp16),
-                           batch_invariant=bool(batch_invariant), decoder=decoder), 'ldm'
+                           batch_invariant=bool(batch_invariant), decoder=decoder, text_encoder=encoder), 'ldm'
     if dataset_name not in arch.NAMED_CONFIGS:
         raise ValueError(f'dataset {dataset_name!r}: only the EDM networks are in scope of the HIP engine '
                          f'({sorted(k for k in arch.NAMED_CONFIGS if not k.startswith("tiny"))} and ms_coco); CM / ADM-classifier-guided / LSUN-LDM models run on the reference')
@@ -295,6 +312,36 @@ def split_sd_checkpoint(sd):
     unet = {k[len(pre):]: v.float() for k, v in sd.items() if k.startswith(pre)}
     vae, _ = vae_arch.split_first_stage(sd)
     return unet, {k: v.float() for k, v in vae.items()}
+
+
+def batch_prompts(batch_seeds, prompt=None, prompts=None):
+    """The prompts of one batch (diff-solvers-main/sample.py:282-284): the lines ``batch_seeds[0] .. batch_seeds[-1]`` of the prompt file when
+    there is one, else ``--prompt`` for every image."""
+    B = len(batch_seeds)
+    if prompts is not None:
+        lo, hi = int(batch_seeds[0]), int(batch_seeds[-1])
+        rows = list(prompts[lo:hi + 1])
+        if len(rows) != B:
+            raise ValueError(f'--prompts_path: seeds {lo} .. {hi} need {B} consecutive lines, the file has {len(prompts)}')
+        return rows
+    if prompt is None:
+        raise ValueError('--tokenizer_path needs --prompt or --prompts_path')
+    return [prompt] * B
+
+
+def encode_conditions(encoder, tokenizer, prompts, guidance_rate):
+    """(c [B, 77, width], uc [B, 77, width] or None) for the prompts of one batch: ``c = encoder(tokenize(prompts))``,
+    ``uc = encoder(tokenize([""]))`` expanded to B (sample.py:286-289); None at guidance 1.0.  Identical prompts are encoded once, and the
+    empty prompt shares the encode with them (one launch plan run for all distinct texts)."""
+    texts = list(dict.fromkeys(prompts))
+    want_uc = guidance_rate != 1.0
+    if want_uc and '' not in texts:
+        texts.append('')
+    states = encoder(tokenizer(texts))
+    index = {t: i for i, t in enumerate(texts)}
+    c = states[[index[p] for p in prompts]]
+    uc = states[index['']].unsqueeze(0).expand(len(prompts), -1, -1) if want_uc else None
+    return c, uc
 
 
 class PngSink:
@@ -388,6 +435,8 @@ def run(dataset_name=None, max_batch_size=64, seeds='0-63', grid=False, outdir=N
     stub = bool(solver_kwargs.pop('stub', False))
     batch_invariant = bool(solver_kwargs.pop('batch_invariant', False))       # --batch_invariant: the engines' mode, not a solver setting
     decode_latents = bool(solver_kwargs.pop('decode_latents', False))         # --decode_latents: ms_coco writes decoded PNGs instead of latents
+    tokenizer_path = solver_kwargs.pop('tokenizer_path', None)                # --tokenizer_path: ms_coco encodes the prompts with the CLIP text encoder
+    prompts_path = solver_kwargs.pop('prompts_path', None)
     if stub:
         device = torch.device('cpu')
     else:
@@ -426,11 +475,19 @@ def run(dataset_name=None, max_batch_size=64, seeds='0-63', grid=False, outdir=N
                                                           guidance_type=solver_kwargs.get('guidance_type'),
                                                           guidance_rate=solver_kwargs.get('guidance_rate'),
                                                           use_fp16=solver_kwargs.get('use_fp16', False), batch_invariant=batch_invariant,
-                                                          **(dict(decode_latents=True) if decode_latents else {}))
+                                                          **(dict(decode_latents=True) if decode_latents else {}),
+                                                          **(dict(text_encoder=True) if tokenizer_path and dataset_name == 'ms_coco' else {}))
     ldm = solver_kwargs['model_source'] == 'ldm'
+    tokenizer = prompt_lines = None
+    if ldm and tokenizer_path:
+        from .clip_tokenizer import ClipTokenizer
+        tokenizer = ClipTokenizer(tokenizer_path, context_length=net.text_encoder.spec.positions)
+        if prompts_path:
+            with open(prompts_path, encoding='utf-8') as fh:
+                prompt_lines = fh.read().splitlines()
     cond_table = None
     if ldm and solver_kwargs.get('condition_path'):
-        # text-encoder states computed elsewhere (CLIP is not on the sampling path): {'c': [N, L, 768] indexed by seed, 'uc': [1, L, 768]}
+        # text-encoder states computed elsewhere (the route without --tokenizer_path): {'c': [N, L, 768] indexed by seed, 'uc': [1, L, 768]}
         cond_table = torch.load(solver_kwargs['condition_path'], map_location='cpu')
     if dist is not None and rank == 0:
         dist.barrier()
@@ -515,10 +572,13 @@ def run(dataset_name=None, max_batch_size=64, seeds='0-63', grid=False, outdir=N
             class_labels = torch.eye(net.label_dim, device=device)[rnd.randint(net.label_dim, size=[B], device=device)]
         with torch.no_grad():
             if ldm:
-                if cond_table is not None:
+                if tokenizer is not None:       # prompt -> CLIP states on the engine (sample.py:281-289)
+                    c, uc = encode_conditions(net.text_encoder, tokenizer, batch_prompts(batch_seeds, solver_kwargs.get('prompt'), prompt_lines),
+                                              solver_kwargs['guidance_rate'])
+                elif cond_table is not None:
                     c = cond_table['c'][torch.as_tensor(batch_seeds) % cond_table['c'].shape[0]].to(device)
                     uc = cond_table['uc'].to(device).expand(B, -1, -1)
-                else:       # no text encoder here: seeded N(0,1) states of the CLIP shape (BASELINE config 5)
+                else:       # no --tokenizer_path: seeded N(0,1) states of the CLIP shape (BASELINE config 5)
                     c = rnd.randn([B, 77, net.spec.context_dim], device=device)
                     uc = torch.randn(1, 77, net.spec.context_dim, generator=torch.Generator().manual_seed(0)).to(device).expand(B, -1, -1)
                 if solver_kwargs['guidance_rate'] == 1.0:
@@ -576,6 +636,8 @@ if click is not None:
     @click.option('--use_fp16', help='Whether to use mixed precision', metavar='BOOL', type=bool, default=False)
     @click.option('--batch_invariant', help='Same seed, same bits at any --batch and world size', metavar='BOOL', type=bool, default=False)
     @click.option('--decode_latents', help='ms_coco: decode the sampled latents with the AutoencoderKL decoder and write PNGs', metavar='BOOL', type=bool, default=False)
+    @click.option('--tokenizer_path', help='ms_coco: directory with the CLIP tokenizer files (vocab.json, merges.txt); the prompts are then encoded by the CLIP text encoder on the engine', metavar='DIR', type=str, default=None)
+    @click.option('--prompts_path', help='ms_coco with --tokenizer_path: text file, line i = the prompt of seed i', metavar='PATH', type=str, default=None)
     @click.option('--max_order', help='Max order for solvers', metavar='INT', type=click.IntRange(min=1))
     @click.option('--predict_x0', help='Whether to use data prediction mode', metavar='BOOL', type=bool, default=True)
     @click.option('--lower_order_final', help='Whether to lower the order at final stages', metavar='BOOL', type=bool, default=True)

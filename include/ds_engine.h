@@ -395,6 +395,16 @@ DS_API int ds_attention_variant(const ds_attn_args* a);
 DS_API int ds_attention_f16(const ds_attn_args* a, void* stream);
 DS_API int ds_attention_f16_supported(int d);
 
+/* Causal self-attention for SHORT sequences, fp32 on the exact-fp32 matrix pipe (csrc/text_encoder.hip): the attention of the CLIP text
+ * encoder (transformers CLIPTextModel as ldm/modules/encoders/modules.py:137-159 FrozenCLIPEmbedder runs it: causal mask only, no padding
+ * mask).  out[b, i, h*d : (h+1)*d] = sum_{j <= i} softmax_{j <= i}(scale * q[b,i,h,:] . k[b,j,h,:]) v[b,j,h,:].  Same argument struct and
+ * token-major operands as ds_attention (arbitrary ld* / *_bs: a packed q|k|v projection is consumed in place); sq == skv (else DS_E_ARG),
+ * fp32 tensors only (in_f16 / out_f16: DS_E_ARG), `variant` is ignored.  The whole K and V of one (image, head) stay in LDS:
+ * ds_attention_causal_supported(d, sq) -- d == 64 and 1 <= sq <= 128 -- else DS_E_SHAPE.  Masked scores are excluded (weight exactly 0; row 0
+ * attends to itself only); a row's scores are summed in an order that depends on the row alone, so results do not depend on the batch. */
+DS_API int ds_attention_causal(const ds_attn_args* a, void* stream);
+DS_API int ds_attention_causal_supported(int d, int sq);
+
 /* LayerNorm over the last dimension (ldm/modules/attention.py:206-208): y[r, :] = (x[r, :] - mean) / sqrt(var + eps)
  * * gamma + beta, cols % 4 == 0, cols <= 2048. */
 DS_API int ds_layernorm_rows(const float* x, int ldx, const float* gamma, const float* beta, float eps, float* y, int ldy,
@@ -410,6 +420,16 @@ DS_API int ds_layernorm_rows_f16io(const void* x16, int ldx, const float* gamma,
 
 /* GEGLU gate (ldm/modules/attention.py:45-52): y[r, c] = x[r, c] * gelu(x[r, inner + c]) with the exact (erf) GELU. */
 DS_API int ds_geglu(const float* x, int ldx, float* y, int ldy, long long rows, int inner, void* stream);
+
+/* quick_gelu, the activation of the CLIP text encoder's MLP (transformers activations.py QuickGELUActivation): y[r, c] = x[r, c] *
+ * sigmoid(1.702 x[r, c]) for c < cols; cols, ldx, ldy % 4 == 0; in place allowed (y == x, ldy == ldx). */
+DS_API int ds_quick_gelu(const float* x, int ldx, float* y, int ldy, long long rows, int cols, void* stream);
+
+/* Token + position embedding of the CLIP text encoder (transformers CLIPTextEmbeddings): out[(b * seq + s) * out_ld + c] =
+ * tok_table[tokens[b * seq + s]][c] + pos_table[s][c], c < width.  tokens: int32 [batch * seq]; tables fp32 [vocab][width] / [seq][width];
+ * width, out_ld % 4 == 0.  Ids are clamped into [0, vocab) by the kernel (it never reads outside the table); a host validates them first. */
+DS_API int ds_token_embed(const int* tokens, const float* tok_table, const float* pos_table, float* out, int out_ld, int batch, int seq,
+                   int width, int vocab, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Noise embedding front end (networks_edm.py:185-198, :314-315, :488-491).
@@ -593,6 +613,9 @@ typedef struct ds_noise_embed_args { const float* sigma; int bs; const float* fr
                                    } ds_noise_embed_args;                                              /* ds_noise_embed */
 typedef struct ds_stem_im2col_args { const float* x; const float* sigma; int sigma_rows; float sigma_data; int n, c, h, w;
                                      float* out; int kpad; } ds_stem_im2col_args;                      /* ds_stem_im2col */
+typedef struct ds_token_embed_args { const int* tokens; const float* tok_table; const float* pos_table; float* out; int out_ld;
+                                     int batch, seq, width, vocab; } ds_token_embed_args;              /* ds_token_embed */
+typedef struct ds_quick_gelu_args { const float* x; int ldx; float* y; int ldy; long long rows; int cols; } ds_quick_gelu_args;   /* ds_quick_gelu */
 
 enum { DS_OP_CONV2D = 1,        /* ds_conv_args        -> ds_conv2d_nhwc      */
        DS_OP_GEMM = 2,          /* ds_gemm_args        -> ds_gemm_nt_batched  */
@@ -606,7 +629,10 @@ enum { DS_OP_CONV2D = 1,        /* ds_conv_args        -> ds_conv2d_nhwc      */
        DS_OP_NOISE_EMBED = 10,  /* ds_noise_embed_args -> ds_noise_embed      */
        DS_OP_STEM_IM2COL = 11,  /* ds_stem_im2col_args -> ds_stem_im2col      */
        DS_OP_LAYERNORM_F16 = 12, /* ds_layernorm_args  -> ds_layernorm_rows_f16 (y = fp16 rows) */
-       DS_OP_LAYERNORM_F16IO = 13 /* ds_layernorm_args -> ds_layernorm_rows_f16io (x and y = fp16 rows) */ };
+       DS_OP_LAYERNORM_F16IO = 13, /* ds_layernorm_args -> ds_layernorm_rows_f16io (x and y = fp16 rows) */
+       DS_OP_TOKEN_EMBED = 14,  /* ds_token_embed_args -> ds_token_embed      */
+       DS_OP_ATTENTION_CAUSAL = 15, /* ds_attn_args    -> ds_attention_causal */
+       DS_OP_QUICK_GELU = 16    /* ds_quick_gelu_args  -> ds_quick_gelu       */ };
 
 typedef struct ds_plan ds_plan;
 DS_API int ds_plan_create(ds_plan** out);
