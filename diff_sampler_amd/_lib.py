@@ -78,7 +78,8 @@ class ConvArgs(C.Structure):
                 ('e0', vp), ('e1', vp), ('ec0', C.c_int), ('ec1', C.c_int), ('eld0', C.c_int), ('eld1', C.c_int),
                 ('stride', C.c_int), ('workspace', vp), ('workspace_floats', C.c_longlong),
                 ('out_nchw', C.c_int), ('stats_out', vp), ('wgt_f16', C.c_int), ('wgt_shift', C.c_int), ('in_f16', C.c_int), ('out_f16', C.c_int), ('res_f16', C.c_int), ('tune', ConvTune),
-                ('update', vp)]          # const ds_update_args*: the solver update fused into the network head (ABI 3)
+                ('update', vp),          # const ds_update_args*: the solver update fused into the network head (ABI 3)
+                ('in_up2', C.c_int)]     # 1: conv3x3 of the nearest-x2 upsampled input on the low-res rows, `wgt` = ops.pack_conv_weight_up2 (ABI 6, appended)
 
 
 class ConvRouteInfo(C.Structure):

@@ -100,8 +100,18 @@ constexpr int VAR_TILE_OPTS = VAR_LEAN | VAR_NTEPI;
 // NT = 32-column MFMA tiles per wave: 2 = 64 x 64 per wave (the normal shape), 4 = 64 x 128 per wave, i.e. a 256-pixel x 256-channel
 // tile for the 8-wave shape: the halo of a slab is staged (normalised, SiLU'd) once for 256 output channels instead of twice, a K step
 // reads 6 fragments for 32 MFMAs instead of 4 for 16, and a tap has 128 MFMAs per wave between barriers (128 accumulator registers).
-template <int WM, bool GLDS, int WN, int VAR = 0, int NT = 2>
+// UP = 1 (ds_conv_args.in_up2): the layer is conv3x3(nearest_x2(x)) and the kernel runs on the LOW-RES image x (p.H, p.W, p.HW, p.M are
+// its geometry).  Per output phase (py, px) = (row & 1, col & 1) the nine taps collapse onto a 2 x 2 low-res neighbourhood whose weights
+// were summed at load time (ops.pack_conv_weight_up2): out[2y+py, 2x+px] = sum_{a,b} W[py][px][a][b] . x[y+py-1+a, x+px-1+b].  A
+// workgroup is one (M tile, column tile, phase); the halo, its loader and the LDS image are those of the ordinary layer, a slab has
+// FOUR taps at the halo offsets of its phase, the weight matrix of the phase is p.b + phase * nrows_b * ldb, and the epilogue writes
+// tile row (img, y, x) to output row (img, 2y+py, 2x+px).  The four phases of an M tile are neighbours in the workgroup order and
+// share an XCD (decode_tile with 4 x ntiles column slots), so the halo comes from HBM once.  No fused normalisation, no appended
+// 1x1 slabs, no split-K (the launcher refuses them).
+template <int WM, bool GLDS, int WN, int VAR = 0, int NT = 2, int UP = 0>
 __global__ void __launch_bounds__(64 * WM * WN, WN == 4 ? 2 : WN) conv3x3_halo_kernel(const KParams p) {
+    static_assert(!UP || (GLDS && !(VAR & VAR_PIPE)), "upsampled-input mode: LDS-DMA weights, the plain tap loop");
+    constexpr int NTAP = UP ? 4 : 9;       // taps per 3x3 slab
     static_assert(NT != 1 || (WM == 2 && WN == 4 && GLDS && VAR == 0), "half-size wave tiles: 128 x 128 tile on 8 waves, LDS-DMA weights");
     static_assert(WN != 4 || NT == 1, "four wave columns: 32-column wave tiles only");
     static_assert(NT == 1 || NT == 2 || ((NT == 4 || NT == 3) && WM == 4 && WN == 2 && GLDS && (VAR & ~(VAR_TILE_OPTS | VAR_NO_NORM | VAR_NO_HALO | VAR_NO_DMA | VAR_NO_EPI)) == 0), "wide-N tiles: 8-wave LDS-DMA shape only");
@@ -116,15 +126,27 @@ __global__ void __launch_bounds__(64 * WM * WN, WN == 4 ? 2 : WN) conv3x3_halo_k
     constexpr int BROWS = BNT * 8 / T;     // weight float4 per thread per tap (4 or 2)
     constexpr int BLD = GLDS ? 32 : LDSK;  // floats per weight row in LDS
     constexpr int NS_MAX = (NT >= 3) ? 7 : ns_max(WN);      // wide-N tiles: one image per tile, at most 7 slots per thread (64-column images)
-    constexpr int B_FLOATS = 2 * BNT * LDSK;
+    constexpr int B_FLOATS = 2 * BNT * (UP ? BLD : LDSK);   // (UP: the unpadded LDS-DMA image exactly -- four 8x8 images per 256 x 256 tile fit)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Bs = smem;                               // [2][BNT][LDSK]
     float* Ah = smem + B_FLOATS;                    // [NP][LDSK]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave / WN, wc = wave % WN;
-    int mt, nt;
-    if (!decode_tile(blockIdx.x, p.mtiles, p.ntiles, mt, nt, blockIdx.y)) return;
+    int mt, nt, phase = 0;
+    if constexpr (UP) {
+        int slot;
+        if (!decode_tile(blockIdx.x, p.mtiles, p.ntiles * 4, mt, slot)) return;
+        phase = slot / p.ntiles;
+        nt = slot - phase * p.ntiles;
+    } else {
+        if (!decode_tile(blockIdx.x, p.mtiles, p.ntiles, mt, nt, blockIdx.y)) return;
+    }
+    const int py = phase >> 1, px = phase & 1;
+    auto wgt_base = [&]() -> const float* {           // UP: this phase's folded weight matrix
+        if constexpr (UP) return p.b + (size_t)phase * p.nrows_b * p.ldb;
+        else return p.b;
+    };
     const int m0 = mt * TBM, n0 = p.n_begin + nt * BNT;
     const int ld_row = tid >> 3, ld_col = (tid & 7) * 4;
     const float* zero = g_zero_page_halo;
@@ -252,7 +274,7 @@ __global__ void __launch_bounds__(64 * WM * WN, WN == 4 ? 2 : WN) conv3x3_halo_k
             }
         }
     };
-    auto b_addr = [&](int kt, int i) -> const float* { return b_ok[i] ? p.b + b_off[i] + kt * BK : zero; };
+    auto b_addr = [&](int kt, int i) -> const float* { return b_ok[i] ? wgt_base() + b_off[i] + kt * BK : zero; };
     auto b_store = [&](int buf) {
         float* bs = Bs + buf * BNT * LDSK + ld_row * LDSK + ld_col;
         DS_RACE_SKEW(wave);
@@ -276,7 +298,7 @@ __global__ void __launch_bounds__(64 * WM * WN, WN == 4 ? 2 : WN) conv3x3_halo_k
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const unsigned b_voff = (unsigned)((ld_row * p.ldb + (((tid & 7) ^ ((ld_row >> 1) & 7)) * 4)) * (int)sizeof(float));
     auto b_dma_lean = [&](int kt, int buf) {
-        const char* tap = reinterpret_cast<const char*>(p.b + (size_t)n0 * p.ldb + (size_t)kt * BK);
+        const char* tap = reinterpret_cast<const char*>(wgt_base() + (size_t)n0 * p.ldb + (size_t)kt * BK);
         DS_RACE_SKEW(wave_u);
 #pragma unroll
         for (int i = 0; i < BROWS; ++i) {
@@ -301,7 +323,7 @@ __global__ void __launch_bounds__(64 * WM * WN, WN == 4 ? 2 : WN) conv3x3_halo_k
     // split-K: this block contracts slabs [c_begin, NCH) only (splits == 1: everything)
     const int c_begin = (int)((long long)blockIdx.y * NCH_all / p.splits);
     const int NCH = (int)((long long)(blockIdx.y + 1) * NCH_all / p.splits);
-    auto kt_of = [&](int chunk) { return chunk < nchunks ? chunk * 9 : nchunks * 9 + (chunk - nchunks); };
+    auto kt_of = [&](int chunk) { return chunk < nchunks ? chunk * NTAP : nchunks * NTAP + (chunk - nchunks); };
     const int kt0 = kt_of(c_begin);
     const int KT = kt_of(NCH);
 
@@ -411,11 +433,12 @@ __global__ void __launch_bounds__(64 * WM * WN, WN == 4 ? 2 : WN) conv3x3_halo_k
         __syncthreads();
     } else {
     for (int chunk = c_begin; chunk < NCH; ++chunk) {
-        const int ntaps = chunk < nchunks ? 9 : 1;
+        const int ntaps = chunk < nchunks ? NTAP : 1;
         for (int t9 = 0; t9 < ntaps; ++t9, ++kt) {
             const int tap = ntaps == 9 ? t9 : 4;
             const int ty = tap / 3;
-            const int toff = ((ty - 1) * p.WP + (tap - ty * 3 - 1)) * LDSK;
+            // UP: tap t9 = a * 2 + b of the phase's 2 x 2 neighbourhood, low-res offset (py - 1 + a, px - 1 + b)
+            const int toff = UP ? ((py - 1 + (t9 >> 1)) * p.WP + (px - 1 + (t9 & 1))) * LDSK : ((ty - 1) * p.WP + (tap - ty * 3 - 1)) * LDSK;
             const int cur = kt & 1;
             const int nxt = min(kt + 1, KT - 1);            // past the end: re-stage the last tile (branch-free body)
             const float* as0 = Ah + a_foff[0] + toff;
@@ -494,6 +517,18 @@ __global__ void __launch_bounds__(64 * WM * WN, WN == 4 ? 2 : WN) conv3x3_halo_k
             }
         return;
     }
+    if constexpr (UP) {                              // never split; tile rows go to the output rows of this workgroup's phase
+        if constexpr (NT == 1) {
+            epilogue32<HALF, true>(p, acc, smem + wave * 32 * EPI_LD, lane, m0 + wr * 64, n0 + wc * 32, p.out, phase);
+        } else {
+            epilogue<0, HALF, NTEPI, true>(p, acc, smem + wave * (HALF ? 32 : 64) * EPI_LD, lane, m0 + wr * 64, n0 + wc * 32 * NT, p.out, phase);
+            if constexpr (NT == 4)
+                epilogue<0, HALF, NTEPI, true>(p, acc_hi, smem + wave * (HALF ? 32 : 64) * EPI_LD, lane, m0 + wr * 64, n0 + wc * 32 * NT + 64, p.out, phase);
+            if constexpr (NT == 3)
+                epilogue32<HALF, true>(p, acc_hi, smem + wave * 32 * EPI_LD, lane, m0 + wr * 64, n0 + wc * 32 * NT + 64, p.out, phase);
+        }
+        return;
+    }
     if constexpr (NT == 1) {                         // 64 x 32 wave tiles (also the raw partial tile of a split)
         if (p.splits > 1) {
             const KParams q = split_params(p, blockIdx.y);
@@ -540,27 +575,36 @@ inline bool use_tail64(const KParams& p) { return p.t_mode != 4; }
 // tile lies in one image (16-, 32- or 64-column images: at most 7 halo slots per thread -- the kernel sits at 256 VGPRs), there is
 // no split-K, and the tiles still give every CU a workgroup.  Measured +4.1 ... +4.5 % on the CIFAR-10 / FFHQ 32x32 and 16x16 layers (129 -> 136 TFLOP/s
 // network average, profiles/r2_conv_wide_n.txt).  p.t_variant 7 switches it off (A/B runs), 6 forces it regardless of the tile count.
-bool wide_n_tiles(const KParams& p, const Geo& g) {
+// Row tiles of `tile` pixels a layer's fill rules count.  up2 (the upsampled-input mode, p.M = low-res pixels): the tiles of the OUTPUT, the
+// quantity the same layer has in the ordinary mode -- the launch has ceil(M / tile) x 4 phases of them, the same number except in a ragged
+// last tile -- so that a layer changes tile shape at the same batch in both modes.
+inline long long fill_tiles(const KParams& p, int tile, bool up2) {
+    return up2 ? (4LL * p.M + tile - 1) / tile : (long long)((p.M + tile - 1) / tile);
+}
+
+// up2: no fused normalisation, hence no per-image coefficient planes -- a tile may hold several images (the 8 -> 16 layer: four 8x8 images
+// per tile).
+bool wide_n_tiles(const KParams& p, const Geo& g, bool up2 = false) {
     const int v = p.t_variant & 31;                    // bits 5.. select options of the 256 x 256 tile itself
 #ifdef DS_CONV_ABLATIONS
     if (p.t_variant & 0x10000) { if (p.splits != 1 || p.N < 256 || g.NP * 8 > 7 * 512 || g.nimg != 1) return false; return true; }
 #endif
     if (v != 0 && v != 6) return false;
-    if (p.splits != 1 || p.N < 256 || g.NP * 8 > 7 * 512 || g.nimg != 1 || p.nrows_b < (p.N / 256) * 256) return false;
-    const long long blocks = (long long)((p.M + 255) / 256) * (p.N / 256);       // the 256-column tiles (a remainder keeps 128 / 64-column tiles)
+    if (p.splits != 1 || p.N < 256 || g.NP * 8 > 7 * 512 || (g.nimg != 1 && !up2) || p.nrows_b < (p.N / 256) * 256) return false;
+    const long long blocks = fill_tiles(p, 256, up2) * (p.N / 256);       // the 256-column tiles (a remainder keeps 128 / 64-column tiles)
     return v == 6 || blocks >= 256;
 }
 
-bool wide192_tiles(const KParams& p, const Geo& g) {
+bool wide192_tiles(const KParams& p, const Geo& g, bool up2 = false) {
     if ((p.t_variant & 31) != 0 || (p.t_variant & 8192)) return false;
     if (p.splits != 1 || p.N % 192 || p.N % 256 == 0 || g.NP * 8 > 7 * 512 || g.nimg != 1 || p.nrows_b < p.N || !p.vec_ok || p.out_planar) return false;
-    return (p.t_variant & 16384) || (long long)((p.M + 255) / 256) * (p.N / 192) >= 256;          // the tiles still cover the 256 CUs (bit 14: forced, tests)
+    return (p.t_variant & 16384) || fill_tiles(p, 256, up2) * (p.N / 192) >= 256;          // the tiles still cover the 256 CUs (bit 14: forced, tests)
 }
 
-template <int WM, bool GLDS, int WN, int VAR = 0, int NT = 2>
+template <int WM, bool GLDS, int WN, int VAR = 0, int NT = 2, int UP = 0>
 int launch_one(KParams p, const Geo& g, int n_begin, int ntiles, hipStream_t stream) {
     constexpr int TBM = 64 * WM;
-    constexpr int B_BYTES = 2 * 32 * NT * WN * LDSK * (int)sizeof(float);
+    constexpr int B_BYTES = 2 * 32 * NT * WN * (UP ? 32 : LDSK) * (int)sizeof(float);
     p.TH = g.TH; p.nimg = g.nimg; p.HP = g.TH + 2; p.WP = p.W + 2; p.NP = g.NP;
     p.mtiles = (p.M + TBM - 1) / TBM;
     p.ntiles = ntiles;
@@ -573,8 +617,9 @@ int launch_one(KParams p, const Geo& g, int n_begin, int ntiles, hipStream_t str
     if (p.coef_lds) smem += coef_bytes;
     const int epi = 4 * 64 * EPI_LD * (int)sizeof(float);       // = 8 x 32 x EPI_LD for the 8-wave shape
     if (smem < epi) smem = epi;
-    DS_ENSURE_DYN_LDS((&conv3x3_halo_kernel<WM, GLDS, WN, VAR, NT>), 128 * 1024);
-    hipLaunchKernelGGL((conv3x3_halo_kernel<WM, GLDS, WN, VAR, NT>), dim3(grid_1d(p.mtiles, p.ntiles), p.splits), dim3(64 * WM * WN), smem, stream, p);
+    if (smem > 128 * 1024) return DS_E_SHAPE;
+    DS_ENSURE_DYN_LDS((&conv3x3_halo_kernel<WM, GLDS, WN, VAR, NT, UP>), 128 * 1024);
+    hipLaunchKernelGGL((conv3x3_halo_kernel<WM, GLDS, WN, VAR, NT, UP>), dim3(grid_1d(p.mtiles, p.ntiles * (UP ? 4 : 1)), p.splits), dim3(64 * WM * WN), smem, stream, p);
     DS_CHECK_LAUNCH();
     return DS_OK;
 }
@@ -582,11 +627,11 @@ int launch_one(KParams p, const Geo& g, int n_begin, int ntiles, hipStream_t str
 // Half-size wave tiles (conv3x3_halo_kernel<2, true, 4, 0, 1>) for the `wide` full 128-column tiles of a layer on 128-pixel tiles: taken
 // where the whole launch is at most one workgroup per CU (with more, two 4-wave workgroups share a CU and every SIMD has its two waves
 // anyway), the float4 epilogue is legal and every one of those tiles is complete.  Variant bit 11: off (A/B runs).
-bool half_wave_tiles(const KParams& p, int n_begin, int wide) {
+bool half_wave_tiles(const KParams& p, int n_begin, int wide, bool up2 = false) {
     if ((p.t_variant & 31) != 0 || (p.t_variant & 2048) || !use_glds(p) || wide < 1) return false;
     if (!p.vec_ok || p.out_planar || p.act == DS_ACT_GEGLU || n_begin + wide * BN > p.N || p.nrows_b < n_begin + wide * BN) return false;
     if (p.splits > 1 && !p.vec_part) return false;
-    if ((long long)((p.M + 127) / 128) * wide * p.splits > 256) return false;
+    if (fill_tiles(p, 128, up2) * wide * p.splits > 256) return false;
     return geometry(p, 128, 4).ok;
 }
 
@@ -596,6 +641,30 @@ bool half_wave_tiles(const KParams& p, int n_begin, int wide) {
 template <int WM, bool GLDS>
 int launch_wm(KParams& p, const ConvRoute& r, hipStream_t stream) {
     const int n256 = r.n256, wide = r.n128;
+    if (r.up2) {
+        // the upsampled-input mode: the default kernel of each tile shape, one launch per column range, every tile whole, no split-K
+        if constexpr (GLDS) {
+            if (p.splits != 1 || r.tail64) return DS_E_SHAPE;
+            int rc = DS_OK;
+            if constexpr (WM == 4) {
+                const Geo g4 = geometry(p, 256, 2);
+                if (r.cols192) return launch_one<4, true, 2, VAR_TILE_OPTS, 3, 1>(p, g4, 0, p.N / 192, stream);
+                if (n256) rc = launch_one<4, true, 2, VAR_TILE_OPTS, 4, 1>(p, g4, 0, n256 / 256, stream);
+                if (rc) return rc;
+            }
+            if (wide > 0) {
+                if (r.half_wave) {
+                    if constexpr (WM == 2) rc = launch_one<2, true, 4, 0, 1, 1>(p, geometry(p, 128, 4), n256, wide, stream);
+                    else rc = DS_E_ARG;
+                } else {
+                    rc = launch_one<WM, true, 2, VAR_LEAN | VAR_NTEPI, 2, 1>(p, geometry(p, 64 * WM, 2), n256, wide, stream);
+                }
+            }
+            return rc;
+        } else {
+            return DS_E_ARG;
+        }
+    }
     if constexpr (WM == 4 && GLDS) {
         const Geo g4 = geometry(p, 256, 2);
         if (r.cols192) {
@@ -684,29 +753,33 @@ void conv3x3_halo_route(const KParams& layer, ConvRoute& r) {
     const Geo g128 = geometry(p, 128), g256 = geometry(p, 256);
     r.kernel_id = 0; r.tile = 0; r.splits = 1;
     if (!g128.ok) return;
+    const bool up2 = r.up2;
+    if (up2) p.t_splits = 1;                            // the four phases already multiply the workgroups: never split-K
+    const int ntap = up2 ? 4 : 9;
     const int nt = (p.N + BN - 1) / BN;
     const int units = (p.c0 + p.c1 + p.ec0 + p.ec1) / BK;
     const long long mn = (long long)p.M * p.N, cap = p.part ? p.part_cap : 0;
     double c128 = 0.0, c256 = 0.0;
     r.tile = 128;
-    r.splits = choose_splits((long long)((p.M + 127) / 128) * nt, false, units, 9, cap, mn, &c128, p.t_splits);
-    const long long blocks256 = (long long)((p.M + 255) / 256) * nt;
+    r.splits = choose_splits(fill_tiles(p, 128, up2) * nt, false, units, ntap, cap, mn, &c128, p.t_splits);
+    const long long blocks256 = fill_tiles(p, 256, up2) * nt;
     // the 8-wave shape only where its tiles alone cover the 256 CUs twice (below that the model is optimistic about it)
     if (g256.ok && tile_override(p) != 128 && (blocks256 >= 512 || tile_override(p) == 256)) {
-        const int s256 = choose_splits(blocks256, true, units, 9, cap, mn, &c256, p.t_splits);
+        const int s256 = choose_splits(blocks256, true, units, ntap, cap, mn, &c256, p.t_splits);
         if (tile_override(p) == 256 || 0.97 * c256 < c128) { r.tile = 256; r.splits = s256; }
     }
     if (((p.t_variant & 31) == 6 || (p.t_variant & 16384)) && r.tile == 256) r.splits = 1;      // forced wide tiles (tests at small sizes): no split-K
     p.splits = r.splits;
     const int WM = r.tile / 64;
     if (r.tile == 256 && use_glds(p)) {
-        if (wide192_tiles(p, g256)) { r.cols192 = true; r.kernel_id = 2568; return; }
-        if (wide_n_tiles(p, g256)) r.n256 = (p.N / 256) * 256;
+        if (wide192_tiles(p, g256, up2)) { r.cols192 = true; r.kernel_id = 2568; return; }
+        if (wide_n_tiles(p, g256, up2)) r.n256 = (p.N / 256) * 256;
     }
     const int nrest = p.N - r.n256, full = nrest / BN, rem = nrest - full * BN;
     r.tail64 = rem > 0 && rem <= 64 && geometry(p, 64 * WM, 1).ok && use_tail64(p);
     r.n128 = r.tail64 ? full : (nrest + BN - 1) / BN;
-    r.half_wave = WM == 2 && use_glds(p) && half_wave_tiles(p, r.n256, r.n128);
+    r.half_wave = WM == 2 && use_glds(p) && half_wave_tiles(p, r.n256, r.n128, up2);
+    if (up2 && (rem != 0 || !use_glds(p))) return;       // whole 128-column LDS-DMA tiles only: refused (kernel id 0)
     r.kernel_id = r.n256 ? 2565 : r.half_wave ? 1284 : r.tile;
 }
 

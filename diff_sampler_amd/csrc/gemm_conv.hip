@@ -479,21 +479,31 @@ static int route_conv(const ds_conv_args* a, KParams& p, ConvRoute& r) {
     if ((a->ld0 & 3) || (a->c1 && (a->ld1 & 3))) return DS_E_ALIGN;
     if (!ds_aligned16(a->x0) || (a->c1 && !ds_aligned16(a->x1)) || !ds_aligned16(a->wgt)) return DS_E_ALIGN;
     if (a->n <= 0 || a->h <= 0 || a->w <= 0 || a->cout <= 0) return DS_E_ARG;
-    const long long M = (long long)a->n * a->h * a->w;
-    if (M > 0x7fffffffLL - BM) return DS_E_SHAPE;
+    // in_up2 (appended to ABI 6): conv3x3 of the nearest-x2 upsampled input, computed on the low-res rows as four 2 x 2 phase convolutions
+    // (conv3x3_halo.hip, UP).  fp32 only, stride 1, no fused normalisation, no appended 1x1 slabs, no residual; h, w = the (even) OUTPUT size.
+    const bool up2 = a->in_up2 != 0;
+    if (up2) {
+        if (a->in_up2 != 1 || a->taps != 9 || a->stride > 1 || a->wgt_f16 || a->in_f16 || a->out_f16 || a->res_f16 || a->wgt_shift) return DS_E_ARG;
+        if (a->norm_coefs || a->e0 || a->e1 || a->ec0 || a->ec1 || a->res || a->out_nchw || a->act == DS_ACT_GEGLU) return DS_E_ARG;
+        if (a->update && (a->update->x_out || a->update->m_out)) return DS_E_ARG;
+        if ((a->h & 1) || (a->w & 1)) return DS_E_SHAPE;
+    }
+    const int geo_h = up2 ? a->h / 2 : a->h, geo_w = up2 ? a->w / 2 : a->w;       // the geometry the kernel tiles: the low-res image's under in_up2
+    const long long M = (long long)a->n * geo_h * geo_w;
+    if ((long long)a->n * a->h * a->w > 0x7fffffffLL - BM) return DS_E_SHAPE;
     set_tune(p, a);
     p.a0 = a->x0; p.a1 = a->x1; p.c0 = a->c0; p.c1 = a->c1; p.lda0 = a->ld0; p.lda1 = a->ld1;
-    p.H = a->h; p.W = a->w; p.HW = a->h * a->w; p.taps = a->taps;
+    p.H = geo_h; p.W = geo_w; p.HW = geo_h * geo_w; p.taps = a->taps;
     const int stride = a->stride ? a->stride : 1;
     if (stride != 1 && (stride != 2 || a->taps != 9 || a->norm_coefs || a->ec0)) return DS_E_ARG;
-    p.stride = stride; p.IH = a->h * stride; p.IW = a->w * stride;
+    p.stride = stride; p.IH = geo_h * stride; p.IW = geo_w * stride;
     if (a->ec0 < 0 || a->ec1 < 0 || a->ec0 % 32 || a->ec1 % 32 || (a->ec1 && !a->ec0)) return DS_E_SHAPE;
     if (a->ec0) {
         if (a->taps != 9 || !a->e0 || (a->ec1 && !a->e1)) return DS_E_ARG;
         if ((a->eld0 & 3) || (a->ec1 && (a->eld1 & 3)) || !ds_aligned16(a->e0) || (a->ec1 && !ds_aligned16(a->e1))) return DS_E_ALIGN;
     }
     if (a->norm_coefs && (a->taps != 9 || !ds_aligned16(a->norm_coefs))) return DS_E_ARG;
-    p.M = (int)M; p.N = a->cout; p.K = a->taps * (a->c0 + a->c1) + a->ec0 + a->ec1;
+    p.M = (int)M; p.N = a->cout; p.K = (up2 ? 4 : a->taps) * (a->c0 + a->c1) + a->ec0 + a->ec1;       // in_up2: four folded taps per phase matrix
     p.b = a->wgt; p.ldb = p.K; p.nrows_b = ((a->cout + BN - 1) / BN) * BN;   // weights are row-padded
     p.norm = a->norm_coefs; p.norm_act = a->norm_act;
     p.e0 = a->e0; p.e1 = a->e1; p.ec0 = a->ec0; p.ec1 = a->ec1; p.elda0 = a->eld0; p.elda1 = a->eld1;
@@ -585,6 +595,20 @@ static int route_conv(const ds_conv_args* a, KParams& p, ConvRoute& r) {
         if (!conv3x3_halo2_applicable(p, r.n128)) return DS_E_SHAPE;
         r.kernel_id = 2563;
         return DS_OK;
+    }
+    if (up2) {
+        // the default kernel of each LDS-DMA tile shape only (tune: a forced M tile, the 256 x 256 / 256 x 192 tiles forced or off, bit 11)
+        const int v5 = p.t_variant & 31;
+        if ((p.t_mode != 0 && p.t_mode != 128 && p.t_mode != 256) || (v5 != 0 && v5 != 6 && v5 != 7) || (p.t_variant & ~(31 | 2048 | 8192 | 16384))) return DS_E_ARG;
+        if (!p.vec_ok || (p.N & 63)) return DS_E_SHAPE;
+        if (p.stats && (p.HW & 63)) return DS_E_SHAPE;     // an image's column-sum blocks: HW / 64 per phase
+        if (!conv3x3_halo_supported(p)) return DS_E_SHAPE;
+        if (inv) p.t_variant |= 2048 | 8192;
+        p.part = nullptr; p.part_cap = 0;
+        r.up2 = true;
+        conv3x3_halo_route(p, r);
+        p.splits = r.splits = 1;
+        return r.kernel_id ? DS_OK : DS_E_SHAPE;           // (a channel count that leaves a partial 128-column tile)
     }
     const bool generic = p.t_mode == 1;                    // tune.mode 1: the generic gather kernel (A/B runs, cross-checks)
     // network heads (cout <= 4): VALU kernel instead of a 64- / 128-column matrix tile (tune.mode != 0 keeps the matrix kernels: 8 = just that)

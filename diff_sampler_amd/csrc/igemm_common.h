@@ -63,9 +63,23 @@ struct KParams {
 // 256 x 256 conv tile; as a run-time option for every other kernel of the family (fp32 / fp16 GEMMs, fp16 convolutions; outputs of at
 // least 32 MiB) it changed nothing on the CIFAR-10, ImageNet-64 fp16 and SD-1.5 fp16 benches (profiles/r2_conv_tile_options.txt), so
 // only that kernel instantiates it.
-template <int MODE, bool HALF = false, bool NTS = false>
+// UP2 (conv3x3_halo_kernel<.., UP = 1>, the upsampled-input 3x3): the tile's rows are pixels (img, y, x) of the LOW-RES image (p.H, p.W,
+// p.HW, p.M) and go to row (img, 2y + py, 2x + px) of the 2H x 2W output, `phase` = py * 2 + px; the per-image bias is indexed by the
+// low-res row as before, and the column sums of the wave's 64 rows land in block (img * 4 + phase) * (HW / 64) + (block in the low-res
+// image) -- an image's 4 HW / 64 blocks stay contiguous, which is all ds_gn_finalize assumes (the launcher requires HW % 64 == 0).
+__device__ __forceinline__ size_t up2_out_row(const KParams& p, int row, int phase) {
+    const int img = row / p.HW, rem = row - img * p.HW;
+    const int y = rem / p.W, x = rem - y * p.W;
+    return ((size_t)img * 2 * p.H + 2 * y + (phase >> 1)) * (2 * p.W) + 2 * x + (phase & 1);
+}
+__device__ __forceinline__ size_t up2_stats_block(const KParams& p, int wm0, int phase) {
+    return (size_t)(wm0 >> 6) + (size_t)((wm0 / p.HW) * 3 + phase) * (p.HW >> 6);
+}
+
+template <int MODE, bool HALF = false, bool NTS = false, bool UP2 = false>
 __device__ __forceinline__ void epilogue(const KParams& p, const f32x16 (&acc)[2][2], float* stage, int lane, int wm0, int wn0,
-                                         float* o_base) {
+                                         float* o_base, int phase = 0) {
+    static_assert(!UP2 || MODE == 0, "upsampled-input mode: convolutions only");
     // HALF: the staging area holds 32 x EPI_LD floats per wave (8-wave blocks) and the two 32-row halves go one after
     // the other; otherwise 64 x EPI_LD and the whole tile is staged at once.
     const bool full_cols = (wn0 + 64 <= p.N);
@@ -126,8 +140,9 @@ __device__ __forceinline__ void epilogue(const KParams& p, const f32x16 (&acc)[2
 #pragma unroll
                     for (int q = 0; q < 4; ++q) v[q] = ds_silu(v[q]);
                 }
-                if (NTS) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(o_base + (size_t)row * p.ldo + col));
-                else *reinterpret_cast<f32x4*>(o_base + (size_t)row * p.ldo + col) = v;
+                const size_t orow = UP2 ? up2_out_row(p, row, phase) : (size_t)row;
+                if (NTS) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(o_base + orow * p.ldo + col));
+                else *reinterpret_cast<f32x4*>(o_base + orow * p.ldo + col) = v;
                 st_s += v; st_q += v * v;
             }
         };
@@ -157,7 +172,7 @@ __device__ __forceinline__ void epilogue(const KParams& p, const f32x16 (&acc)[2
                 st_q[q] += __shfl_xor(st_q[q], 16); st_q[q] += __shfl_xor(st_q[q], 32);
             }
             if (lane < 16) {
-                float* sp = p.stats + (size_t)(wm0 >> 6) * 2 * p.N + col;
+                float* sp = p.stats + (UP2 ? up2_stats_block(p, wm0, phase) : (size_t)(wm0 >> 6)) * 2 * p.N + col;
                 *reinterpret_cast<f32x4*>(sp) = st_s;
                 *reinterpret_cast<f32x4*>(sp + p.N) = st_q;
             }
@@ -199,8 +214,9 @@ __device__ __forceinline__ void epilogue(const KParams& p, const f32x16 (&acc)[2
 // re-laid for 32 columns -- 8 lanes x float4 cover a row segment, lane >> 3 picks one of 8 rows per pass, 4 passes per 32-row group.
 // The launcher only takes this kernel where the vector path is legal (p.vec_ok, whole 32-column tiles) and there is no GEGLU gate.
 //   out = act((acc * acc_scale + colbias + cbias[img] + res) * scale), column sums / sums of squares of the wave's 64 rows to p.stats
-template <bool HALF>
-__device__ __forceinline__ void epilogue32(const KParams& p, const f32x16 (&acc)[2][2], float* stage, int lane, int wm0, int wn0, float* o_base) {
+template <bool HALF, bool UP2 = false>
+__device__ __forceinline__ void epilogue32(const KParams& p, const f32x16 (&acc)[2][2], float* stage, int lane, int wm0, int wn0, float* o_base,
+                                           int phase = 0) {
     static_assert(HALF, "8-wave tiles: 32 staging rows per wave, the two 32-row groups one after the other");
     const int c4 = (lane & 7) * 4;
     const int col = wn0 + c4;
@@ -243,7 +259,8 @@ __device__ __forceinline__ void epilogue32(const KParams& p, const f32x16 (&acc)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = ds_silu(v[q]);
             }
-            *reinterpret_cast<f32x4*>(o_base + (size_t)row * p.ldo + col) = v;
+            const size_t orow = UP2 ? up2_out_row(p, row, phase) : (size_t)row;
+            *reinterpret_cast<f32x4*>(o_base + orow * p.ldo + col) = v;
             st_s += v; st_q += v * v;
         }
     }
@@ -255,7 +272,7 @@ __device__ __forceinline__ void epilogue32(const KParams& p, const f32x16 (&acc)
             st_q[q] += __shfl_xor(st_q[q], 8); st_q[q] += __shfl_xor(st_q[q], 16); st_q[q] += __shfl_xor(st_q[q], 32);
         }
         if (lane < 8) {
-            float* sp = p.stats + (size_t)(wm0 >> 6) * 2 * p.N + col;
+            float* sp = p.stats + (UP2 ? up2_stats_block(p, wm0, phase) : (size_t)(wm0 >> 6)) * 2 * p.N + col;
             *reinterpret_cast<f32x4*>(sp) = st_s;
             *reinterpret_cast<f32x4*>(sp + p.N) = st_q;
         }
@@ -618,6 +635,9 @@ struct ConvRoute {
     // tile count of the split-fp16 halo kernel (kernel id 2563).
     int tile, n256, n128;
     bool cols192, tail64, half_wave;
+    // ds_conv_args.in_up2, set by route_conv BEFORE conv3x3_halo_route: the KParams geometry is the low-res image's, a layer has four phases
+    // (four times the workgroups, 4 taps per slab), never split-K, whole 128- / 192- / 256-column tiles only (kernel id 0 = refused)
+    bool up2;
     // fp16-activation 3x3 kernel: column tiling, groups of (first column, tiles, width in 64-channel units), widest first
     int ngroups;
     int groups[4][3];

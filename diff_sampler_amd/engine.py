@@ -29,14 +29,18 @@ import torch
 
 from . import _lib, arch
 from ._lib import DS_ACT_SILU, DS_RESAMPLE_NONE, DS_RESAMPLE_DOWN, DS_RESAMPLE_UP
-from .ops import pack_conv_weight, pack_conv_weight_f16, pack_conv_weight_split, pack_linear_weight, pack_stem_weight
+from .ops import pack_conv_weight, pack_conv_weight_f16, pack_conv_weight_split, pack_conv_weight_up2, pack_linear_weight, pack_stem_weight
 from .plan import FUSE_NORM16_DEFAULT, Builder, Plan as _Plan, fuse_norm16_here, fuse_norm16_value, ptr as _ptr
 
 
 class UNetEngine:
     def __init__(self, spec: arch.UNetSpec, params: Dict[str, torch.Tensor], device='cuda', use_fp16=False, split_fp16=False,
-                 batch_invariant=False):
-        """batch_invariant: every plan takes the batch-invariant route: an image's output bits depend on its own
+                 batch_invariant=False, up_phase=True):
+        """up_phase (exact fp32 mode only): conv0 of an up block, conv3x3(nearest_x2(silu(norm0(x)))), runs on the LOW-RES activated tensor as
+        four 2x2 phase convolutions with weights folded at load time (ds_conv_args.in_up2: 4 taps per output pixel instead of 9, and the
+        upsampled tensor is never written) wherever the library takes the layer; False = the upsampling pass and the 9-tap convolution
+        (A/B runs, tests/test_hip_upconv.py).
+        batch_invariant: every plan takes the batch-invariant route: an image's output bits depend on its own
         inputs, the weights and the mode only -- not on the batch size, the other images or the sigma form.
         split_fp16: fp32 EMULATED on the fp16 matrix pipe in the 3x3 convolutions -- every operand as fp16 hi + lo, three MFMA
         products per multiplication, fp32 accumulation (ds_conv_args.wgt_f16 == 2); 2**-22 relative per product, i.e. inside every
@@ -52,6 +56,7 @@ class UNetEngine:
         self.use_fp16 = bool(use_fp16)
         self.split_fp16 = bool(split_fp16) and not self.use_fp16
         self.batch_invariant = bool(batch_invariant)
+        self.up_phase = bool(up_phase) and not self.use_fp16 and not self.split_fp16
         # fp16 mode: GroupNorm apply + SiLU inside the fp16-activation convolution's LDS halo instead of a ds_norm_act pass (plan(): fz0 / fz1;
         # bit-identical results).  An attribute, not an argument, so that A/B runs flip it per engine: DS_FUSE_NORM16 sets the default.
         self.fuse_norm16 = fuse_norm16_value(os.environ.get('DS_FUSE_NORM16', FUSE_NORM16_DEFAULT))
@@ -104,6 +109,8 @@ class UNetEngine:
                 w[f'{b.name}.{leaf}.g'] = g(f'{p}.{leaf}.weight'); w[f'{b.name}.{leaf}.b'] = g(f'{p}.{leaf}.bias')
             w[f'{b.name}.conv0.w'] = pack_conv_weight(g(f'{p}.conv0.weight')); w[f'{b.name}.conv0.b'] = g(f'{p}.conv0.bias')
             w[f'{b.name}.conv1.w'] = pack_conv_weight(g(f'{p}.conv1.weight')); w[f'{b.name}.conv1.b'] = g(f'{p}.conv1.bias')
+            if self.up_phase and b.up and b.cin % 32 == 0:
+                w[f'{b.name}.conv0.wup'] = pack_conv_weight_up2(g(f'{p}.conv0.weight'))      # the four folded phase matrices, once per build
             if self.conv_mode == 1 and b.cin % 64 == 0 and b.cout % 64 == 0:
                 w[f'{b.name}.conv0.w16'] = (pack_conv_weight_f16(g(f'{p}.conv0.weight')), 0)
                 w[f'{b.name}.conv1.w16'] = (pack_conv_weight_f16(g(f'{p}.conv1.weight'), g(f'{p}.skip.weight') if b.skip_conv else None), 0)
@@ -334,7 +341,15 @@ class UNetEngine:
         if w16_0 is not None and bd.f16_level(n, Ho, Ho, cin, 0, 0, 0) == 1:
             fuse = False        # fp16 operands without the fused normalisation (8x8: four images per tile): normalise in a pass
         conv0 = dict(bias=w[f'{nm}.conv0.b'], stats=True, w16=w16_0, **cb)      # (+ per-image embedding for the non-adaptive variant)
-        if fuse and rs == DS_RESAMPLE_NONE:
+        wup = w.get(f'{nm}.conv0.wup') if b.up and w16_0 is None else None
+        if wup is not None and bd.up2_ok(ws.act, cin, cin, n, Ho, Ho, wup, cout, ws.hbuf, cout, **conv0):
+            # up block: the pass activates at the input resolution and the convolution reads it through the x2 upsampling (four 2x2 phase
+            # convolutions on the low-res rows); the launches are those of the other route, the upsampled tensor is never written
+            bd.norm('stats', x0, c0, c0, n, Hin, Hin, nm + '.norm0.stats', groups=G_in, eps=b.eps, **src)
+            bd.norm('apply', x0, c0, c0, n, Hin, Hin, nm + '.norm0', groups=G_in, eps=b.eps, gamma=w[f'{nm}.norm0.g'], beta=w[f'{nm}.norm0.b'],
+                    act=DS_ACT_SILU, resample=DS_RESAMPLE_NONE, out=ws.act, out_ld=cin, **src)
+            bd.conv(ws.act, cin, cin, n, Ho, Ho, wup, cout, ws.hbuf, cout, 9, nm + '.conv0', in_up2=True, **conv0)
+        elif fuse and rs == DS_RESAMPLE_NONE:
             bd.norm('stats', x0, c0, c0, n, Hin, Hin, nm + '.norm0.stats', groups=G_in, eps=b.eps, gamma=w[f'{nm}.norm0.g'],
                     beta=w[f'{nm}.norm0.b'], coefs=ncoef, **src)
             bd.conv(x0, c0, c0, n, Ho, Ho, w[f'{nm}.conv0.w'], cout, ws.hbuf, cout, 9, nm + '.conv0', norm_coefs=ncoef, norm_act=DS_ACT_SILU,
@@ -438,10 +453,11 @@ class EDMDenoiser:
     edm_raw_output = True      # solvers._Run: ds_solver_update applies the EDM preconditioning to the raw output itself
 
     def __init__(self, spec: arch.UNetSpec, params: Dict[str, torch.Tensor], device='cuda', use_fp16=False, split_fp16=False,
-                 batch_invariant=False):
-        """batch_invariant: same seed, same bits at any batch (UNetEngine)."""
+                 batch_invariant=False, up_phase=True):
+        """batch_invariant: same seed, same bits at any batch (UNetEngine).  up_phase: UNetEngine."""
         self.spec = spec
-        self.engine = UNetEngine(spec, params, device, use_fp16=use_fp16, split_fp16=split_fp16, batch_invariant=batch_invariant)
+        self.engine = UNetEngine(spec, params, device, use_fp16=use_fp16, split_fp16=split_fp16, batch_invariant=batch_invariant,
+                                 up_phase=up_phase)
         self.batch_invariant = bool(batch_invariant)
         self.device = self.engine.device
         self.img_resolution = spec.img_resolution
@@ -455,11 +471,12 @@ class EDMDenoiser:
         self.bottleneck_name = None      # set by the AMED path: 'enc.8x8_block3' / 'enc.8x8_block2'
 
     @classmethod
-    def from_config(cls, name_or_kwargs, seed=0, mode='signal', device='cuda', use_fp16=False, split_fp16=False, batch_invariant=False):
+    def from_config(cls, name_or_kwargs, seed=0, mode='signal', device='cuda', use_fp16=False, split_fp16=False, batch_invariant=False,
+                    up_phase=True):
         kw = arch.NAMED_CONFIGS[name_or_kwargs] if isinstance(name_or_kwargs, str) else name_or_kwargs
         spec = arch.edm_precond_spec(**kw)
         return cls(spec, arch.init_params(spec, seed=seed, mode=mode), device, use_fp16=use_fp16, split_fp16=split_fp16,
-                   batch_invariant=batch_invariant)
+                   batch_invariant=batch_invariant, up_phase=up_phase)
 
     @classmethod
     def from_reference_module(cls, net, device='cuda', use_fp16=None, batch_invariant=False):

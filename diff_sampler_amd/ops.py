@@ -40,6 +40,37 @@ def pack_conv_weight(w: torch.Tensor, row_pad: int = 128, k_pad: int = 32) -> to
     return out.contiguous()
 
 
+def fold_conv_weight_up2(w: torch.Tensor) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] -> [4, Cout, Cin, 2, 2]: the four 2x2 phase kernels of ``conv3x3(nearest_x2(x), pad 1)`` on the low-res image.
+
+    Output pixel (2y + py, 2x + px) reads upsampled rows 2y + py - 1 + ky, i.e. low-res rows y + floor((py - 1 + ky) / 2): for py = 0 kernel
+    row 0 lands on offset -1 and rows {1, 2} on offset 0; for py = 1 rows {0, 1} land on offset 0 and row 2 on +1 (columns alike with px).
+    Phase p = py * 2 + px, tap (a, b) multiplies low-res pixel (y + py - 1 + a, x + px - 1 + b); weights that share a pixel are summed (at
+    most four, in the dtype of ``w``)."""
+    assert w.dim() == 4 and w.shape[2:] == (3, 3)
+    rows = (((0,), (1, 2)), ((0, 1), (2,)))          # rows[py][a] = kernel rows that land on low-res offset py - 1 + a
+    out = w.new_zeros(4, w.shape[0], w.shape[1], 2, 2)
+    for py in range(2):
+        for px in range(2):
+            for a in range(2):
+                for b in range(2):
+                    out[py * 2 + px, :, :, a, b] = sum(w[:, :, ky, kx] for ky in rows[py][a] for kx in rows[px][b])
+    return out
+
+
+def pack_conv_weight_up2(w: torch.Tensor, row_pad: int = 128, k_pad: int = 32) -> torch.Tensor:
+    """Weights of ds_conv_args.in_up2: [Cout, Cin, 3, 3] -> [4, Cout_pad, 4 Cin], the folded phase kernels (fold_conv_weight_up2) each packed
+    like pack_conv_weight with four taps: K = (chunk*4 + a*2 + b)*32 + cc, rows zero-padded to a multiple of the N tile."""
+    cout, cin = w.shape[:2]
+    assert cin % k_pad == 0
+    f = fold_conv_weight_up2(w.to(torch.float32))                                            # [4, cout, cin, 2, 2]
+    m = f.permute(0, 1, 3, 4, 2).reshape(4, cout, 4, cin // k_pad, k_pad).permute(0, 1, 3, 2, 4).reshape(4, cout, 4 * cin)
+    rows = -(-cout // row_pad) * row_pad
+    out = torch.zeros(4, rows, 4 * cin, dtype=torch.float32, device=w.device)
+    out[:, :cout] = m
+    return out.contiguous()
+
+
 def pack_conv_weight_f16(w: torch.Tensor, extra: Optional[torch.Tensor] = None, row_pad: int = 128) -> torch.Tensor:
     """fp16 weights of the reduced-precision 3x3 convolution (ds_conv_args.wgt_f16): [Cout, Cin, 3, 3] (+ optional 1x1 skip
     projection [Cout, Ce, 1, 1] appended along K) -> [Cout_pad, K] halfs, K = (slab*9 + tap)*64 + cc with c = slab*64 + cc,

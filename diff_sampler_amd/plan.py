@@ -16,7 +16,7 @@ from typing import Dict, List
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, ConvArgs, GemmArgs, GnFinalizeArgs, NormArgs, DS_ACT_NONE, DS_ACT_SILU, DS_RESAMPLE_NONE, DS_RESAMPLE_UP
+from ._lib import AttnArgs, ConvArgs, ConvRouteInfo, GemmArgs, GnFinalizeArgs, NormArgs, DS_ACT_NONE, DS_ACT_SILU, DS_RESAMPLE_NONE, DS_RESAMPLE_UP
 
 
 SPLITK_WORKSPACE_FLOATS = 64 << 20      # 256 MiB per plan
@@ -415,7 +415,8 @@ class Builder:
 
     def conv(self, x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, taps, name, x1=None, c1=0, ld1=0, bias=None, cbias=None,
              cbias_ld=0, cbias_rows=1, res=None, res_ld=0, scale=1.0, act=DS_ACT_NONE, norm_coefs=None, norm_act=DS_ACT_NONE,
-             e0=None, ec0=0, e1=None, ec1=0, stride=1, stats=False, w16=None, out_nchw=0, in_f16=False, out_f16=False, emb=False):
+             e0=None, ec0=0, e1=None, ec1=0, stride=1, stats=False, w16=None, out_nchw=0, in_f16=False, out_f16=False, emb=False,
+             in_up2=False):
         """stats=True: the epilogue also leaves the output's per-(64-row block, channel) sums for the consumer's GroupNorm
         (honoured when cout % 64 == 0; otherwise the consumer falls back to a ds_gn_stats pass).
         w16: fp16 weights of the same layer (ops.pack_conv_weight_f16); used -- with the fp16-operand kernel -- when the
@@ -423,7 +424,11 @@ class Builder:
         in_f16: x0 (and e0) are fp16 NHWC tensors (leading dimensions in halfs) written by ``norm(..., out_f16=True)``: the
         fp16-activation kernel (csrc/conv3x3_f16dma.hip); needs w16.
         emb: a projection of the embedding path (one row per image or one shared row): in the invariant mode the row kernel at every row
-        count (ds_conv_tune.invariant bit 1), so that both sigma forms and every batch give the same embedding rows."""
+        count (ds_conv_tune.invariant bit 1), so that both sigma forms and every batch give the same embedding rows.
+        in_up2: the layer is conv3x3(nearest_x2(x0)) on the low-res rows x0 ([n][h/2][w/2]; h, w = the output size) with `wgt` =
+        ops.pack_conv_weight_up2 (ds_conv_args.in_up2; fp32 only -- the caller asked up2_ok())."""
+        if in_up2:
+            assert w16 is None and not in_f16 and norm_coefs is None and not ec0 and res is None and stride == 1 and taps == 9, name
         if taps == 1 and x0.dtype == torch.float16:
             # 1x1 / Linear on an fp16 tensor (LayerNorm / GroupNorm pass / attention / GEGLU output in fp16 mode): csrc/gemm_f16dma.hip
             assert x1 is None and not ec0 and norm_coefs is None and not out_nchw and stride == 1
@@ -453,6 +458,7 @@ class Builder:
         a.out_nchw = out_nchw               # network output written channel-planar (NCHW) by the epilogue
         a.wgt_f16, a.wgt_shift = (self.conv_mode, shift) if f16 else (0, 0)
         a.in_f16 = 1 if in_f16 else 0
+        a.in_up2 = 1 if in_up2 else 0
         if self.invariant:
             a.tune.invariant = 3 if emb else 1
         if out_f16 or out.dtype == torch.float16:          # fp16 output rows: conv0 outputs, projection operands, the fp16 residual stream
@@ -468,6 +474,20 @@ class Builder:
             self.stats_of[out.data_ptr()] = (sb, cout)
         self._autotune(a, (x0, e0 if in_f16 else None, x1 if in_f16 else None, e1 if in_f16 else None, norm_coefs if in_f16 else None))
         self.add(self.lib.ds_conv2d_nhwc, (C.byref(a),), name, keep=(a,))
+
+    def up2_ok(self, x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, bias=None, cbias=None, cbias_ld=0, cbias_rows=1, stats=False, **_):
+        """Does the library take this layer as an upsampled-input convolution (ds_conv_args.in_up2)?  Asked of ds_conv_route (host logic
+        only) with the arguments conv(..., in_up2=True) would pass.  On the batch-invariant route the answer depends on the layer alone (the
+        256 x 192 tiles, the one shape whose use follows the tile count, are off there)."""
+        a = ConvArgs(ptr(x0), None, c0, 0, ld0, 0, n, h, w, 9, ptr(wgt), cout, ptr(bias), ptr(cbias), cbias_ld, cbias_rows, None, 0,
+                     1.0, DS_ACT_NONE, ptr(out), out_ld)
+        a.in_up2 = 1
+        if stats and cout % 64 == 0 and out_ld == cout:
+            a.stats_out = ptr(out)              # (any 16-byte-aligned address: the probe launches nothing)
+        if self.invariant:
+            a.tune.invariant = 1
+        info = ConvRouteInfo()
+        return self.lib.ds_conv_route(C.byref(a), C.byref(info)) == 0
 
     @staticmethod
     def _tune_key(a, stride):

@@ -197,6 +197,20 @@ typedef struct ds_conv_args {
      * pointer, so a host re-fills the same struct before each run (x_out == m_out == NULL = no fusion for this run).
      * Replaces the separate update launch of the linear solvers (solvers.py:76-81, :156-168, :245-258, :344-352, :574-585). */
     const struct ds_update_args* update;
+    /* ABI 6, appended; 0 = as before.  1: THE INPUT IS UPSAMPLED x2 (nearest neighbour) ON THE FLY -- the layer is
+     * conv3x3(nearest_x2(x), pad 1), the `UNetBlock(up=True)` conv0 of the EDM networks with resample_filter [1, 1] (networks_edm.py:160) --
+     * and is computed on the low-res rows: h, w are the OUTPUT size (both even), x0 / x1 are [n][h/2][w/2] rows, and `wgt` holds FOUR folded
+     * phase matrices [phase = py*2 + px][cout_pad][4 (c0+c1)], K = (chunk*4 + a*2 + b)*32 + cc, with
+     *   W[py][px][a][b] = sum of w[ky][kx] over ky in rowset(py, a), kx in rowset(px, b); rowset(0, .) = {0}, {1,2}; rowset(1, .) = {0,1}, {2}
+     *   out[2y+py, 2x+px] = sum_{a,b} W[py][px][a][b] . x[y+py-1+a, x+px-1+b]      (zero padding of the low-res image)
+     * (ops.pack_conv_weight_up2) -- exact in real arithmetic, 4 taps per output pixel instead of 9, and the upsampled tensor is never
+     * written.  taps stays 9 and stride 0 / 1.  fp32 weights and activations only; no norm_coefs, no e0 / e1, no res, no out_nchw, no
+     * split-K; bias, cbias, out_scale, act NONE / SILU and stats_out are honoured (stats_out needs (h/2)(w/2) % 64 == 0; an image's h w / 64
+     * blocks stay contiguous, phase-major inside the image: 64 rows of one phase each -- all ds_gn_finalize assumes).  cout must be a multiple
+     * of 128 (or of 192 where the layer runs on the 256 x 192 tiles: every tile of the launch is whole) and the low-res image one the LDS-halo
+     * kernel takes, else DS_E_SHAPE; any other combination DS_E_ARG -- from ds_conv_kernel_id / ds_conv_route as well.  The kernel id is that
+     * of the tile shape it runs on (2565 / 256 / 128 / 1284 / 2568). */
+    int in_up2;
 } ds_conv_args;
 
 DS_API int ds_conv2d_nhwc(const ds_conv_args* a, void* stream);

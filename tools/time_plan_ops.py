@@ -58,14 +58,14 @@ def signature(op):
     if op.fn is conv_fn:
         m = a.n * a.h * a.w
         s = a.stride if a.stride else 1
-        k = a.taps * (a.c0 + a.c1) + a.ec0 + a.ec1
+        k = a.taps * (a.c0 + a.c1) + a.ec0 + a.ec1           # algorithmic (9-tap) FLOPs also for an upsampled-input layer (in_up2: 4 taps executed)
         cout = a.cout
         eb = 2 if a.in_f16 else 4
         ob = 2 if a.out_f16 else 4
         n_eff = cout // 2 if a.act == 2 else cout
         by = m * s * s * (a.c0 + a.c1) * eb + m * (a.ec0 + a.ec1) * eb + m * n_eff * ob + (m * n_eff * (2 if a.res_f16 else 4) if a.res else 0) + k * cout * 2
         lab = f'conv{"3x3" if a.taps == 9 else "1x1"} n={a.n} {a.h}x{a.w} {a.c0}+{a.c1}(+{a.ec0}+{a.ec1})->{cout}' \
-              f'{" s2" if s == 2 else ""}{" geglu" if a.act == 2 else ""}{" norm" if a.norm_coefs else ""}{" res" if a.res else ""}{" f16" if a.in_f16 else ""}'
+              f'{" s2" if s == 2 else ""}{" geglu" if a.act == 2 else ""}{" norm" if a.norm_coefs else ""}{" res" if a.res else ""}{" f16" if a.in_f16 else ""}{" up2" if a.in_up2 else ""}'
         return lab, 2.0 * m * k * cout, by
     if op.fn is norm_fn:
         m = a.n * a.h * a.w
