@@ -168,10 +168,18 @@ class QuickGeluArgs(C.Structure):
     _fields_ = [('x', vp), ('ldx', C.c_int), ('y', vp), ('ldy', C.c_int), ('rows', C.c_longlong), ('cols', C.c_int)]
 
 
+class ChannelMeanF16Args(C.Structure):
+    _fields_ = [('x', vp), ('ld', C.c_int), ('c', C.c_int), ('rows', C.c_longlong), ('out', vp)]
+
+
+class CfgSigmaRowsArgs(C.Structure):
+    _fields_ = [('sigma', vp), ('n', C.c_int), ('log_alpha', vp), ('m', C.c_int), ('copies', C.c_int), ('sigma_out', vp), ('c_noise_out', vp)]
+
+
 # ds_plan_add op codes (include/ds_engine.h)
 DS_OP_CONV2D, DS_OP_GEMM, DS_OP_GN_STATS, DS_OP_NORM_ACT, DS_OP_GN_FINALIZE, DS_OP_ATTENTION, DS_OP_ATTENTION_F16, DS_OP_LAYERNORM, \
     DS_OP_GEGLU, DS_OP_NOISE_EMBED, DS_OP_STEM_IM2COL, DS_OP_LAYERNORM_F16, DS_OP_LAYERNORM_F16IO, DS_OP_TOKEN_EMBED, \
-    DS_OP_ATTENTION_CAUSAL, DS_OP_QUICK_GELU = range(1, 17)
+    DS_OP_ATTENTION_CAUSAL, DS_OP_QUICK_GELU, DS_OP_CHANNEL_MEAN_F16, DS_OP_CFG_SIGMA_ROWS = range(1, 19)
 
 _SIGNATURES = {
     'ds_version': (C.c_int, []),
@@ -269,6 +277,19 @@ def check(code, what=''):
     if code != 0:
         msg = load().ds_error_string(code)
         raise DsError(f'{what or "libdsamd call"} failed with code {code}: {msg.decode() if msg else "?"}')
+
+
+def run_op(op, args, what):
+    """One launch that exists only as a plan operation (DS_OP_CHANNEL_MEAN_F16, DS_OP_CFG_SIGMA_ROWS): recorded into a one-entry ds_plan,
+    run on the current stream, and the plan dropped again -- host bookkeeping only, the plan owns no device memory."""
+    lib = load()
+    h = vp()
+    check(lib.ds_plan_create(C.byref(h)), 'ds_plan_create')
+    try:
+        check(lib.ds_plan_add(h, op, C.byref(args), C.sizeof(args)), f'ds_plan_add({what})')
+        check(lib.ds_plan_run(h, stream_ptr()), what)
+    finally:
+        lib.ds_plan_destroy(h)
 
 
 def stream_ptr():

@@ -533,6 +533,29 @@ __global__ void channel_mean_kernel(const float* __restrict__ x, int ld, int c, 
     if (lane == 0) out[row] = s / (float)c;
 }
 
+// The same mean over fp16 rows (a tap on the fp16 residual stream): widened on load, fp32 accumulation, one wave per row.  VEC: 16-byte
+// loads (c % 8 == 0, ld % 8 == 0, 16-byte aligned base -- the launcher checks), else one half per lane and trip.
+template <bool VEC>
+__global__ void channel_mean_f16_kernel(const _Float16* __restrict__ x, int ld, int c, long long rows, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const _Float16* xr = x + row * ld;
+    float s = 0.f;
+    if (VEC) {
+        for (int i = lane * 8; i < c; i += 512) {
+            const n16_h8 v = *reinterpret_cast<const n16_h8*>(xr + i);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s += (float)v[j];
+        }
+    } else {
+        for (int i = lane; i < c; i += 64) s += (float)xr[i];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) out[row] = s / (float)c;
+}
+
 // --------------------------------------------------------------------------------------------------------------
 // LayerNorm over the channel dimension of token rows: one wave per row, the row lives in registers (<= 8 float4 per
 // lane), two-pass mean / variance like ATen's row-wise moments.
@@ -868,6 +891,20 @@ extern "C" int ds_channel_mean(const float* x, int ld, int c, long long rows, fl
     (void)hipGetLastError();   // drop stale errors of unrelated runtime calls
     if (!x || !out || rows <= 0 || c <= 0) return DS_E_ARG;
     hipLaunchKernelGGL(channel_mean_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, ld, c, rows, out);
+    DS_CHECK_LAUNCH();
+    return DS_OK;
+}
+
+int ds_channel_mean_f16(const void* x, int ld, int c, long long rows, float* out, void* stream) {
+    (void)hipGetLastError();   // drop stale errors of unrelated runtime calls
+    if (!x || !out || rows <= 0 || c <= 0 || ld < c) return DS_E_ARG;
+    if (reinterpret_cast<uintptr_t>(x) & 1u) return DS_E_ALIGN;
+    const _Float16* x16 = reinterpret_cast<const _Float16*>(x);
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (!(c & 7) && !(ld & 7) && ds_aligned16(x))
+        hipLaunchKernelGGL(channel_mean_f16_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x16, ld, c, rows, out);
+    else
+        hipLaunchKernelGGL(channel_mean_f16_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x16, ld, c, rows, out);
     DS_CHECK_LAUNCH();
     return DS_OK;
 }

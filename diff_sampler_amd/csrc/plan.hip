@@ -11,7 +11,7 @@ namespace {
 union ArgBlob {
     ds_conv_args conv; ds_gemm_args gemm; ds_norm_args norm; ds_gn_finalize_args fin; ds_attn_args attn;
     ds_layernorm_args ln; ds_geglu_args geglu; ds_noise_embed_args ne; ds_stem_im2col_args stem;
-    ds_token_embed_args tok; ds_quick_gelu_args qg;
+    ds_token_embed_args tok; ds_quick_gelu_args qg; ds_channel_mean_f16_args cm16; ds_cfg_sigma_rows_args csr;
 };
 
 struct Node { int op; ArgBlob a; };
@@ -29,6 +29,8 @@ size_t arg_size(int op) {
         case DS_OP_STEM_IM2COL: return sizeof(ds_stem_im2col_args);
         case DS_OP_TOKEN_EMBED: return sizeof(ds_token_embed_args);
         case DS_OP_QUICK_GELU: return sizeof(ds_quick_gelu_args);
+        case DS_OP_CHANNEL_MEAN_F16: return sizeof(ds_channel_mean_f16_args);
+        case DS_OP_CFG_SIGMA_ROWS: return sizeof(ds_cfg_sigma_rows_args);
         default: return 0;
     }
 }
@@ -57,6 +59,9 @@ int issue(const Node& n, void* stream) {
             return ds_token_embed(e.tokens, e.tok_table, e.pos_table, e.out, e.out_ld, e.batch, e.seq, e.width, e.vocab, stream); }
         case DS_OP_ATTENTION_CAUSAL: return ds_attention_causal(&n.a.attn, stream);
         case DS_OP_QUICK_GELU: { const ds_quick_gelu_args& g = n.a.qg; return ds_quick_gelu(g.x, g.ldx, g.y, g.ldy, g.rows, g.cols, stream); }
+        case DS_OP_CHANNEL_MEAN_F16: { const ds_channel_mean_f16_args& m = n.a.cm16; return ds_channel_mean_f16(m.x, m.ld, m.c, m.rows, m.out, stream); }
+        case DS_OP_CFG_SIGMA_ROWS: { const ds_cfg_sigma_rows_args& r = n.a.csr;
+            return ds_cfg_sigma_rows(r.sigma, r.n, r.log_alpha, r.m, r.copies, r.sigma_out, r.c_noise_out, stream); }
         default: return DS_E_ARG;
     }
 }

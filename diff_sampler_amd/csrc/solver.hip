@@ -499,6 +499,33 @@ __global__ void __launch_bounds__(256) cfg_denoise_kernel(const float* __restric
     }
 }
 
+// CFGPrecond's sigma -> c_noise for a device vector of per-sample sigmas (networks_edm.py:677, :713-759): log_alpha = -1/2 log(1 + sigma^2)
+// (what logaddexp(0, 2 ln sigma) evaluates), t = the piecewise-linear inverse of the log_alpha table (t_k = (k + 1) / m, the table falls with
+// k; beyond either end the outermost segment is extended), c_noise = m t - 1.  One thread per sample; the table is searched as its ascending
+// (flipped) view like torch.searchsorted on the host path.  The handful of scalar operations run in fp64, so the fp32 result carries the
+// table's rounding and its own only.  `copies` = 2 writes both halves of a classifier-free 2n-row evaluation.
+__global__ void cfg_sigma_rows_kernel(const float* __restrict__ sigma, int n, const float* __restrict__ la, int m, int copies,
+                                      float* __restrict__ sigma_out, float* __restrict__ cn_out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n) return;
+    const float s = sigma[b];
+    const double x = -0.5 * log1p((double)s * (double)s);
+    int lo = 0, hi = m;                                      // first j of the ascending view xp[j] = la[m - 1 - j] with xp[j] >= x
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((double)la[m - 1 - mid] < x) lo = mid + 1; else hi = mid;
+    }
+    const int i = min(max(lo, 1), m - 1) - 1;                // segment [i, i + 1] of the ascending view, 0 <= i <= m - 2
+    const double x0 = la[m - 1 - i], x1 = la[m - 2 - i];
+    const double y0 = (double)(m - i) / m, y1 = (double)(m - i - 1) / m;
+    const double t = y0 + (x - x0) * (y1 - y0) / (x1 - x0);
+    const float cn = (float)((double)m * t - 1.0);
+    for (int k = 0; k < copies; ++k) {
+        sigma_out[(size_t)k * n + b] = s;
+        cn_out[(size_t)k * n + b] = cn;
+    }
+}
+
 }  // namespace
 
 extern "C" int ds_solver_update(const ds_update_args* a, void* stream) {
@@ -586,6 +613,16 @@ extern "C" int ds_cfg_denoise(const float* x, const float* f, int f_ld, const fl
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(cfg_denoise_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, f, f_ld, sigma, sigma_rows, guidance,
                        doubled, n, c, h * w, out);
+    DS_CHECK_LAUNCH();
+    return DS_OK;
+}
+
+int ds_cfg_sigma_rows(const float* sigma, int n, const float* log_alpha, int m, int copies, float* sigma_out, float* c_noise_out,
+                                 void* stream) {
+    (void)hipGetLastError();
+    if (!sigma || !log_alpha || !sigma_out || !c_noise_out || n <= 0 || m < 2 || (copies != 1 && copies != 2)) return DS_E_ARG;
+    hipLaunchKernelGGL(cfg_sigma_rows_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, sigma, n, log_alpha, m, copies,
+                       sigma_out, c_noise_out);
     DS_CHECK_LAUNCH();
     return DS_OK;
 }

@@ -128,6 +128,9 @@ NAMED_LDM_CONFIGS = {
                      num_res_blocks=2, channel_mult=(1, 2, 4, 4), num_heads=4, context_dim=96),
     'tiny_ldm_1res': dict(img_resolution=16, in_channels=4, out_channels=4, model_channels=32, attention_resolutions=(2, 1),
                           num_res_blocks=1, channel_mult=(1, 2, 2), num_heads=2, context_dim=64),
+    # AMED test size: the middle block is [N, 128, 8, 8] -- the 8x8 tap the AMED predictor's 64-wide input needs (amed-solver-main/solvers_amed.py:24)
+    'tiny_ldm_amed': dict(img_resolution=32, in_channels=4, out_channels=4, model_channels=64, attention_resolutions=(4, 2, 1),
+                          num_res_blocks=1, channel_mult=(1, 2, 2), num_heads=2, context_dim=64),
 }
 
 

@@ -373,6 +373,8 @@ class CFGDenoiser(CFGSchedule):
         CFGSchedule.__init__(self, spec)                                    # host tables (networks_edm.py:654-658)
         self.use_fp16 = bool(use_fp16)      # the reference's autocast mode (sample.py:296); fixed at construction
         self.cache_context = True           # cross-attention K / V projections once per context tensor, not once per evaluation
+        self._last = None                   # (plan, B, doubled) of the last evaluation (block_output, bottleneck_mean)
+        self._log_alpha_dev = None          # the log_alpha table on the device (DS_OP_CFG_SIGMA_ROWS), uploaded on first use
 
     @classmethod
     def from_config(cls, name_or_kwargs, seed=0, device='cuda', **kw):
@@ -394,8 +396,11 @@ class CFGDenoiser(CFGSchedule):
             P.ctx_capture_key = None
 
     # -- evaluation ----------------------------------------------------------------------------------------------------------
-    def raw(self, x, sigma, condition=None, unconditional_condition=None):
-        """Runs the plan; returns (F rows NHWC [N*H*W, 4], plan, doubled)."""
+    def raw(self, x, sigma, condition=None, unconditional_condition=None, device_sigma=False):
+        """Runs the plan; returns (F rows NHWC [N*H*W, 4], plan, doubled).
+        device_sigma: `sigma` is an fp32 device tensor [B] and stays there -- sigma and c_noise rows of both halves are written by one
+        DS_OP_CFG_SIGMA_ROWS launch instead of the host interpolation of ``sigma_inv`` (a D2H copy, CPU math and an H2D copy per evaluation:
+        the AMED samplers evaluate at per-sample device sigmas in every step).  Off (the default) keeps the host path and its bits."""
         lib = self.engine.lib
         st = _lib.stream_ptr()
         B = x.shape[0]
@@ -404,6 +409,11 @@ class CFGDenoiser(CFGSchedule):
             raise ValueError('CFGDenoiser needs `condition` (text-encoder states [B, L, context_dim])')
         N = 2 * B if doubled else B
         host_scalar = isinstance(sigma, (int, float)) or (isinstance(sigma, torch.Tensor) and sigma.numel() == 1)
+        if device_sigma:
+            if not (isinstance(sigma, torch.Tensor) and sigma.is_cuda and sigma.dtype == torch.float32 and sigma.numel() == B
+                    and sigma.is_contiguous()):
+                raise ValueError('device_sigma=True takes a contiguous fp32 device tensor of B sigmas')
+            host_scalar = False
         emb_rows = 1 if host_scalar else N
         cond = condition if condition is not None else torch.zeros(B, 1, self.spec.context_dim, device=self.device)
         L = cond.shape[1]
@@ -413,7 +423,11 @@ class CFGDenoiser(CFGSchedule):
         per = x[0].numel()
         for half in range(2 if doubled else 1):
             _lib.check(lib.ds_copy_rows(ptr(x), per, ptr(bufs['x'][half * B:]), per, B, per, st), 'copy x')
-        if host_scalar:
+        if device_sigma:
+            if self._log_alpha_dev is None:
+                self._log_alpha_dev = self.log_alpha_array.to(device=self.device, dtype=torch.float32).contiguous()
+            ops.cfg_sigma_rows(sigma, B, self._log_alpha_dev, 2 if doubled else 1, bufs['sigma'], bufs['c_noise'])
+        elif host_scalar:
             s = float(sigma)
             cn = float(self.M * self.sigma_inv(torch.tensor(s, dtype=torch.float32)) - 1.)
             _lib.check(lib.ds_fill(ptr(bufs['sigma']), s, 1, st), 'fill sigma')
@@ -460,12 +474,51 @@ class CFGDenoiser(CFGSchedule):
             plan.ctx.run(st)
             plan.ctx_key = None if capturing else key
         plan.run(st)
+        self._last = (plan, B, doubled)
         return bufs['out'], plan, doubled
 
-    def __call__(self, x, sigma, condition=None, unconditional_condition=None, force_fp32=False, **kwargs):
+    def __call__(self, x, sigma, condition=None, unconditional_condition=None, force_fp32=False, device_sigma=False, **kwargs):
         B, Cc, H, W = x.shape
-        f, plan, doubled = self.raw(x, sigma, condition, unconditional_condition)
+        f, plan, doubled = self.raw(x, sigma, condition, unconditional_condition, device_sigma=device_sigma)
         out = torch.empty(B, Cc, H, W, dtype=torch.float32, device=self.device)
         rows = plan.bufs['sigma'].numel()
         ops.cfg_denoise(plan.bufs['x'], f, 4, plan.bufs['sigma'], 1 if rows == 1 else B, self.guidance_rate, doubled, B, Cc, H, W, out)
+        return out
+
+    # -- the AMED tap: the reference hooks net.model.model.diffusion_model.middle_block (amed-solver-main/solvers_amed.py:11-12) -----------
+    bottleneck_name = 'middle_block.2'
+
+    def tap_shape(self, name=None):
+        """(channels, resolution) of block `name`'s output (default: the AMED tap), from the spec: known before any launch."""
+        name = self.bottleneck_name if name is None else name
+        for b in self.spec.blocks:
+            for l in b.layers:
+                if l.key == name:
+                    return l.cout, l.res_out
+        raise KeyError(name)
+
+    def block_output(self, name):
+        """Output of layer ``name`` ('middle_block.2', 'input_blocks.1.0', ...) of the LAST evaluation as the NCHW fp32 tensor
+        ``[N, C, h, w]`` a forward hook on that module of the reference would see -- all N images: under classifier-free guidance N = 2B,
+        unconditional half first (networks_edm.py:687-689).  A copy: the plan's own buffer is overwritten by the next evaluation."""
+        plan, B, doubled = self._last
+        N = 2 * B if doubled else B
+        t = plan.bufs[name].float()          # fp16 residual stream (fp16 mode): widened for the caller
+        hw = t.shape[0] // N
+        h = int(round(hw ** 0.5))
+        assert h * h == hw, (name, tuple(t.shape), N)
+        return t.reshape(N, h, h, t.shape[1]).permute(0, 3, 1, 2).contiguous()
+
+    def bottleneck_mean(self, plan, B, doubled):
+        """Channel mean of the AMED tap, [B, h, w] fp32 (solvers_amed.py:23-28): of the conditional half -- rows [B h w, 2 B h w) of the
+        plan's NHWC buffer -- when the evaluation was doubled, of the whole batch otherwise.  Reads the rows in place, fp32 or fp16."""
+        t = plan.bufs[self.bottleneck_name]
+        N = 2 * B if doubled else B
+        c = t.shape[1]
+        hw = t.shape[0] // N
+        h = int(round(hw ** 0.5))
+        assert h * h == hw and t.shape[0] == N * hw and t.stride(0) == c, (tuple(t.shape), N)
+        rows = t[B * hw:] if doubled else t
+        out = torch.empty(B, h, h, dtype=torch.float32, device=self.device)
+        (ops.channel_mean_f16 if t.dtype == torch.float16 else ops.channel_mean)(rows, c, c, B * hw, out)
         return out

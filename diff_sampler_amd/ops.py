@@ -238,6 +238,20 @@ def channel_mean(x, ld, c, rows, out):
     _lib.check(_lib.load().ds_channel_mean(_p(x), ld, c, rows, _p(out), _lib.stream_ptr()), 'ds_channel_mean')
 
 
+def channel_mean_f16(x, ld, c, rows, out):
+    """x: fp16 rows [rows][ld] (ld in halfs); out: fp32 [rows].  A tensor view selects the rows (its data_ptr is what is passed)."""
+    assert x.dtype == torch.float16 and out.dtype == torch.float32
+    _lib.run_op(_lib.DS_OP_CHANNEL_MEAN_F16, _lib.ChannelMeanF16Args(_p(x), ld, c, rows, _p(out)), 'DS_OP_CHANNEL_MEAN_F16')
+
+
+def cfg_sigma_rows(sigma, n, log_alpha, copies, sigma_out, c_noise_out):
+    """sigma: fp32 device [n]; log_alpha: fp32 device table [M]; sigma_out / c_noise_out: fp32 device [copies * n]."""
+    assert sigma.dtype == log_alpha.dtype == sigma_out.dtype == c_noise_out.dtype == torch.float32
+    assert sigma.numel() >= n and sigma_out.numel() >= copies * n and c_noise_out.numel() >= copies * n
+    _lib.run_op(_lib.DS_OP_CFG_SIGMA_ROWS, _lib.CfgSigmaRowsArgs(_p(sigma), n, _p(log_alpha), log_alpha.numel(), copies, _p(sigma_out),
+                                                                 _p(c_noise_out)), 'DS_OP_CFG_SIGMA_ROWS')
+
+
 def copy_rows(src, src_ld, dst, dst_ld, rows, cols):
     _lib.check(_lib.load().ds_copy_rows(_p(src), src_ld, _p(dst), dst_ld, rows, cols, _lib.stream_ptr()), 'ds_copy_rows')
 

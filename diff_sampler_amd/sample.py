@@ -9,6 +9,8 @@ diff-solvers-main/sample.py:125-320.  One CLI serves the three variants of the r
     setting (sampler_stu, num_steps, afs, max_order, predict_x0, lower_order_final, schedule_type/rho, guidance, dataset_name)
     is read back from it, exactly as the reference does; ``--predictor_path random:<seed> --random_init True`` builds a seeded
     predictor from the CLI's own options instead (there are no trained predictors in this environment).
+    ``dataset_name='ms_coco'`` (AMED-Plugin on DPM-Solver++(2M), launch.sh:55-62, :75-77) runs on the SD-1.5 U-Net under
+    classifier-free guidance and composes with ``--decode_latents`` / ``--tokenizer_path`` / ``--use_fp16``.
 Differences, all host-side:
   * the network object is an ``engine.EDMDenoiser`` (built from the unpickled EDM network when a pickle is given, or
     from the stated architecture with ``--random_init`` -- no pretrained weights exist in this environment);

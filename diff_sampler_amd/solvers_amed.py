@@ -7,7 +7,10 @@ tensors ``r, scale_dir, scale_time, t_mid``.  Here the bottleneck is an explicit
 of both stages are one kernel each (``ds_amed_coefs``) and each stage's update is the same fused ``ds_solver_update``
 launch the other samplers use, reading its scalars per sample from the coefficient rows.
 
-Scope: inference (``train=False``) with an ``EDMDenoiser`` net -- the configuration of BASELINE config 4.
+Scope: inference (``train=False``) with an ``EDMDenoiser`` net -- the configuration of BASELINE config 4 -- or with the latent-diffusion
+``ldm_engine.CFGDenoiser`` under classifier-free guidance (amed-solver-main/launch.sh:55-62, :75-77: AMED-Plugin on DPM-Solver++(2M) for
+Stable Diffusion).  There the tap is the middle block's conditional half (solvers_amed.py:11-12, :23-25), the evaluations return D (the
+non-fused form of ``_Run``) and every evaluation takes its sigmas from a device vector (``DS_OP_CFG_SIGMA_ROWS``): no host round trip per step.
 """
 from __future__ import annotations
 
@@ -22,6 +25,7 @@ from .solver_utils import get_schedule, dynamic_thresholding_fn
 from .solvers import _Run, _Ring, get_denoised  # noqa: F401  (get_denoised re-exported like the reference)
 
 MODE = dict(amed=0, euler=1, ipndm=2, dpm=3, dpmpp=4)
+DEVICE_SIGMA = True        # latent-diffusion nets: sigma / c_noise rows by DS_OP_CFG_SIGMA_ROWS (False: CFGSchedule.sigma_inv on the host, for A/B runs)
 
 
 class AMEDPredictor:
@@ -94,12 +98,29 @@ class _TapHandle:
         self.tap.active = False
 
 
+def _is_cfg_net(net):
+    """A latent-diffusion denoiser of the engine (ldm_engine.CFGDenoiser): ``guidance_type`` like the reference's CFGPrecond, plus the tap."""
+    return hasattr(net, 'guidance_type') and hasattr(net, 'bottleneck_mean')
+
+
+def _not_doubled(net):
+    return ValueError(f'AMED on a classifier-free denoiser reads the CONDITIONAL half of a doubled evaluation (solvers_amed.py:23-25), and this '
+                      f'evaluation is not doubled: guidance_rate = {getattr(net, "guidance_rate", None)!r} (1 disables guidance) or no '
+                      f'unconditional_condition was given')
+
+
 def init_hook(net, class_labels=None):
     """``unet_enc_out, hook = init_hook(net, class_labels)`` (solvers_amed.py:7-18): the U-Net bottleneck tap -- ``enc['8x8_block2']`` for
-    class-conditional EDM nets, ``enc['8x8_block3']`` otherwise.  LDM / 256-pixel ADM nets (``middle_block``) are outside the engine's
-    AMED scope and raise."""
+    class-conditional EDM nets, ``enc['8x8_block3']`` otherwise, and the middle block (``middle_block.2``, the output of
+    ``net.model.model.diffusion_model.middle_block``) for the latent-diffusion ``ldm_engine.CFGDenoiser``: there ``unet_enc_out[-1]`` is
+    ``[2B, C, h, w]`` under classifier-free guidance, unconditional half first, as the reference's hook sees it.  ``guidance_type='uncond'``
+    LDMs and 256-pixel ADM / CM nets are outside the engine's AMED scope and raise."""
+    if _is_cfg_net(net) and net.guidance_type == 'classifier-free':
+        tap = _BottleneckTap(net, net.bottleneck_name)
+        return tap, _TapHandle(tap)
     if hasattr(net, 'guidance_type') or getattr(net, 'img_resolution', 0) == 256 or not hasattr(net, 'block_output'):
-        raise NotImplementedError('init_hook: the engine exposes the AMED bottleneck of EDM nets (engine.EDMDenoiser) only')
+        raise NotImplementedError('init_hook: the engine exposes the AMED bottleneck of EDM nets (engine.EDMDenoiser) and of the '
+                                  'classifier-free latent-diffusion denoiser (ldm_engine.CFGDenoiser) only')
     tap = _BottleneckTap(net, 'enc.8x8_block2' if class_labels is not None else 'enc.8x8_block3')
     return tap, _TapHandle(tap)
 
@@ -109,17 +130,29 @@ def get_amed_prediction(AMED_predictor, t_cur, t_next, net, unet_enc_out, use_af
     under AFS, :27) through the predictor kernel; an absent head yields ones (:43,48,53-54)."""
     pred = _as_predictor(AMED_predictor, net.device if hasattr(net, 'device') else 'cuda')
     dev = pred.device
+    cfg = getattr(net, 'guidance_type', None) == 'classifier-free'      # the predictor sees the conditional half (solvers_amed.py:23-25)
     if use_afs:
         bott = torch.zeros(batch_size, 8, 8, dtype=torch.float32, device=dev)
     elif isinstance(unet_enc_out, _BottleneckTap):                      # the plan's own NHWC buffer: no copy
         if not unet_enc_out.active:
             raise RuntimeError('the hook was removed')
-        bott = net.bottleneck_mean(net._last[0], batch_size, class_cond=unet_enc_out.name.endswith('block2'))
+        if _is_cfg_net(net):
+            plan, _, doubled = net._last
+            if cfg and not doubled:
+                raise _not_doubled(net)
+            bott = net.bottleneck_mean(plan, batch_size, doubled)
+        else:
+            bott = net.bottleneck_mean(net._last[0], batch_size, class_cond=unet_enc_out.name.endswith('block2'))
     else:                                                               # any list of [B, C, 8, 8] tensors, as the reference's hook fills
         t = unet_enc_out[-1].to(dev, torch.float32)
+        if cfg:                                                         # [2B, C, h, w]: unet_enc[batch_size:]
+            t = t[batch_size:]
+            if t.shape[0] != batch_size:
+                raise _not_doubled(net)
+        h, w = t.shape[2], t.shape[3]
         nhwc = t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]).contiguous()
-        bott = torch.empty(batch_size, 8, 8, dtype=torch.float32, device=dev)
-        ops.channel_mean(nhwc, t.shape[1], t.shape[1], batch_size * 64, bott)
+        bott = torch.empty(batch_size, h, w, dtype=torch.float32, device=dev)
+        ops.channel_mean(nhwc, t.shape[1], t.shape[1], batch_size * h * w, bott)
     out = torch.empty(batch_size, 4, dtype=torch.float32, device=dev)
     pred.predict(bott, float(t_cur), float(t_next), out)
     col = lambda j: out[:, j].reshape(-1, 1, 1, 1).clone()
@@ -137,11 +170,25 @@ def _amed_loop(mode, net, latents, class_labels, condition, unconditional_condit
                lower_order_final=True):
     if train:
         raise NotImplementedError('the training branches of solvers_amed are out of scope of the HIP engine (SURVEY.md section 2, row 7)')
+    cfg_net = _is_cfg_net(net)
+    if cfg_net:
+        # latent diffusion: everything that can be refused is refused before the first launch
+        if net.guidance_type != 'classifier-free':
+            raise NotImplementedError("AMED on guidance_type='uncond' latent-diffusion nets is out of scope of the HIP engine")
+        doubled = net.guidance_rate != 1. and unconditional_condition is not None
+        if not doubled:
+            raise _not_doubled(net)
+        predictor = _as_predictor(predictor, latents.device)
+        _, tap_res = net.tap_shape()
+        if tap_res * tap_res != predictor.w['enc_layer0.weight'].shape[1]:
+            raise ValueError(f"the AMED tap of this net is {tap_res}x{tap_res} = {tap_res * tap_res} values per image, the predictor's "
+                             f"enc_layer0 takes {predictor.w['enc_layer0.weight'].shape[1]}")
     t_steps = get_schedule(num_steps, sigma_min, sigma_max, device=latents.device, schedule_type=schedule_type, schedule_rho=schedule_rho, net=net)
     run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, False)
     run.fuse_head = False               # the bottleneck is read between an evaluation and its update: evaluations run on their own
-    if not run.fused:
-        raise RuntimeError('AMED samplers need the bottleneck tap of engine.EDMDenoiser (the reference hooks net.model.enc[...])')
+    if not run.fused and not cfg_net:
+        raise RuntimeError('AMED samplers need the bottleneck tap of engine.EDMDenoiser or ldm_engine.CFGDenoiser (the reference hooks '
+                           'net.model.enc[...] / ...diffusion_model.middle_block)')
     predictor = _as_predictor(predictor, latents.device)
     lib = _lib.load()
     dev, B = latents.device, run.B
@@ -150,6 +197,7 @@ def _amed_loop(mode, net, latents, class_labels, condition, unconditional_condit
     pred = torch.empty(B, 4, **f32)
     c1, c2 = torch.empty(B, 8, **f32), torch.empty(B, 8, **f32)
     sigma2 = torch.empty(B, **f32)
+    sigma1 = torch.empty(B, **f32) if cfg_net else None
     thist = torch.zeros(B, 4, **f32)
     zeros_b = None
     in_dim = predictor.w['enc_layer0.weight'].shape[1]
@@ -162,6 +210,17 @@ def _amed_loop(mode, net, latents, class_labels, condition, unconditional_condit
         a = AmedCoefArgs(C.c_void_p(pred.data_ptr()), ts_cur, ts_next, m, stage, order, int(predict_x0),
                          C.c_void_p(thist.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(sigma2.data_ptr()) if stage == 1 else None, B)
         _lib.check(lib.ds_amed_coefs(C.byref(a), _lib.stream_ptr()), 'ds_amed_coefs')
+
+    def evaluate(xe, sig):
+        """One evaluation at (xe, sig): sig a Python float (stage 1) or the device vector of stage 2.  A latent-diffusion net returns D (the
+        non-fused form of _Run) and takes both as a device vector of B sigmas: its c_noise rows are then written on the device."""
+        if not cfg_net:
+            return run.evaluate(xe, sig)
+        if not isinstance(sig, torch.Tensor):
+            ops.fill(sigma1, sig)
+            sig = sigma1
+        run._f = net(xe, sig, condition=run.cond, unconditional_condition=run.ucond, device_sigma=DEVICE_SIGMA)
+        run._raw = False
 
     def pp_order(step_cur):
         if lower_order_final:
@@ -193,8 +252,11 @@ def _amed_loop(mode, net, latents, class_labels, condition, unconditional_condit
                 zeros_b = torch.zeros(B, in_dim, **f32)
             bott = zeros_b                                             # solvers_amed.py:27
         else:
-            run.evaluate(x, ts_cur)
-            bott = net.bottleneck_mean(run._plan, B, class_cond=(class_labels is not None))
+            evaluate(x, ts_cur)
+            if cfg_net:
+                bott = net.bottleneck_mean(net._last[0], B, net._last[2])      # the conditional half (solvers_amed.py:23-25)
+            else:
+                bott = net.bottleneck_mean(run._plan, B, class_cond=(class_labels is not None))
         predictor.predict(bott, ts_cur, ts_next, pred)
         if mode == 'ipndm':
             o1 = min(max_order, len(ring) + 1)
@@ -210,7 +272,7 @@ def _amed_loop(mode, net, latents, class_labels, condition, unconditional_condit
             coefs(1, 1, c1)
             run.update(xe=x, xb=x, t=1.0, sigma=1.0, cx=0.0, cm=0.0, x_out=xt, m_out=d1, afs=use_afs, coefs=c1)
         # ---- stage 2: evaluation at (x~, scale_time * t_mid), step to t_next ------------------------------------------
-        run.evaluate(xt, sigma2)
+        evaluate(xt, sigma2)
         xn = run.new() if return_inters else x
         if mode == 'amed':
             coefs(2, 1, c2)

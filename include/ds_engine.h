@@ -630,6 +630,19 @@ typedef struct ds_stem_im2col_args { const float* x; const float* sigma; int sig
 typedef struct ds_token_embed_args { const int* tokens; const float* tok_table; const float* pos_table; float* out; int out_ld;
                                      int batch, seq, width, vocab; } ds_token_embed_args;              /* ds_token_embed */
 typedef struct ds_quick_gelu_args { const float* x; int ldx; float* y; int ldy; long long rows; int cols; } ds_quick_gelu_args;   /* ds_quick_gelu */
+/* The two launches of the AMED samplers on the latent-diffusion denoiser; they have no entry point of their own and run as plan operations.
+ * ds_channel_mean_f16_args: ds_channel_mean over fp16 rows (a tap that lives on the fp16 residual stream): x = fp16 [rows][ld], ld in halfs,
+ * fp32 accumulation, out[r] = one fp32 mean per row.  A sub-range of the rows (the conditional half of a classifier-free 2B-image
+ * evaluation, solvers_amed.py:23-25) is selected by offsetting x.
+ * ds_cfg_sigma_rows_args: CFGPrecond's noise-level inputs for per-sample sigmas that live on the DEVICE (networks_edm.py:677, :713-759; the
+ * AMED second evaluation at scale_time * t_mid): for b < n and k < copies
+ *     sigma_out[k n + b] = sigma[b],   c_noise_out[k n + b] = m * t(sigma[b]) - 1
+ * with t = the piecewise-linear inverse of log_alpha[0 .. m) (the table of 0.5 log alphas_cumprod at t_k = (k + 1) / m, strictly falling) at
+ * -0.5 log(1 + sigma^2), the outermost segments extended beyond both ends.  copies = 1 or 2 (both halves of a classifier-free evaluation);
+ * m >= 2.  sigma_out may be sigma itself.  No host round trip: the host path (ldm_engine.CFGSchedule.sigma_inv) copies sigma to the CPU. */
+typedef struct ds_channel_mean_f16_args { const void* x; int ld; int c; long long rows; float* out; } ds_channel_mean_f16_args;
+typedef struct ds_cfg_sigma_rows_args { const float* sigma; int n; const float* log_alpha; int m; int copies; float* sigma_out;
+                                        float* c_noise_out; } ds_cfg_sigma_rows_args;
 
 enum { DS_OP_CONV2D = 1,        /* ds_conv_args        -> ds_conv2d_nhwc      */
        DS_OP_GEMM = 2,          /* ds_gemm_args        -> ds_gemm_nt_batched  */
@@ -646,7 +659,9 @@ enum { DS_OP_CONV2D = 1,        /* ds_conv_args        -> ds_conv2d_nhwc      */
        DS_OP_LAYERNORM_F16IO = 13, /* ds_layernorm_args -> ds_layernorm_rows_f16io (x and y = fp16 rows) */
        DS_OP_TOKEN_EMBED = 14,  /* ds_token_embed_args -> ds_token_embed      */
        DS_OP_ATTENTION_CAUSAL = 15, /* ds_attn_args    -> ds_attention_causal */
-       DS_OP_QUICK_GELU = 16    /* ds_quick_gelu_args  -> ds_quick_gelu       */ };
+       DS_OP_QUICK_GELU = 16,   /* ds_quick_gelu_args  -> ds_quick_gelu       */
+       DS_OP_CHANNEL_MEAN_F16 = 17, /* ds_channel_mean_f16_args -> channel mean of fp16 rows (norm_act.hip) */
+       DS_OP_CFG_SIGMA_ROWS = 18    /* ds_cfg_sigma_rows_args -> sigma and c_noise rows from device sigmas (solver.hip) */ };
 
 typedef struct ds_plan ds_plan;
 DS_API int ds_plan_create(ds_plan** out);
