@@ -81,10 +81,23 @@ class ConvArgs(C.Structure):
                 ('update', vp),          # const ds_update_args*: the solver update fused into the network head (ABI 3)
                 ('in_up2', C.c_int)]     # 1: conv3x3 of the nearest-x2 upsampled input on the low-res rows, `wgt` = ops.pack_conv_weight_up2 (ABI 6, appended)
 
+    # `int wino` of ds_conv_args (1: the Winograd F(2x2, 3x3) form of an exact-fp32 3x3 layer, `wgt` = ops.pack_conv_weight_wino; ABI 6, appended
+    # after in_up2).  The C struct is 8-byte aligned (pointers) and in_up2 sits on an 8-byte boundary, so the new int takes the four bytes that
+    # were tail padding: sizeof is unchanged and `_fields_` still ends with in_up2 (tests/test_upconv_cpu.py pins that); the member is mirrored
+    # here as a property on those bytes (a zero-initialised ctypes struct has them zero: wino = 0, as before).
+    def _wino_cell(self):
+        return C.c_int.from_address(C.addressof(self) + ConvArgs.in_up2.offset + C.sizeof(C.c_int))
+
+    wino = property(lambda self: self._wino_cell().value, lambda self, v: setattr(self._wino_cell(), 'value', int(v)))
+
+
+assert C.sizeof(ConvArgs) == ConvArgs.in_up2.offset + 2 * C.sizeof(C.c_int), 'ds_conv_args.wino must fit the tail padding behind in_up2'
+
 
 class ConvRouteInfo(C.Structure):
     # ds_conv_route (ABI 5): kernel id, split-K factor and the fp16-activation 3x3 kernel's column-tile widths (64-channel units)
-    _fields_ = [('kernel_id', C.c_int), ('splits', C.c_int), ('f16_groups', C.c_int), ('f16_widths', C.c_int * 4)]
+    _fields_ = [('kernel_id', C.c_int), ('splits', C.c_int), ('f16_groups', C.c_int), ('f16_widths', C.c_int * 4),
+                ('wino', C.c_int)]       # 1: the launch runs the Winograd form (appended to ABI 6)
 
 
 class GemmArgs(C.Structure):

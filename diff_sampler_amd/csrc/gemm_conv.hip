@@ -488,6 +488,18 @@ static int route_conv(const ds_conv_args* a, KParams& p, ConvRoute& r) {
         if (a->update && (a->update->x_out || a->update->m_out)) return DS_E_ARG;
         if ((a->h & 1) || (a->w & 1)) return DS_E_SHAPE;
     }
+    // wino (appended to ABI 6): the Winograd form F(2x2, 3x3) of an exact-fp32 stride-1 3x3 layer (conv3x3_wino.hip), `wgt` = the transformed weights.
+    // Only where the direct form would run on the 256 x 256 tiles without split-K (decided below, after conv3x3_halo_route); never on the
+    // batch-invariant route, whose promise is the canonical (slab, tap, channel) chain.
+    const bool wino = a->wino != 0;
+    if (wino) {
+        if (a->wino != 1 || up2 || a->taps != 9 || a->stride > 1 || a->wgt_f16 || a->in_f16 || a->out_f16 || a->res_f16 || a->wgt_shift) return DS_E_ARG;
+        if ((a->tune.invariant & 1) || a->out_nchw || a->act == DS_ACT_GEGLU) return DS_E_ARG;
+        if (a->update && (a->update->x_out || a->update->m_out)) return DS_E_ARG;
+        if (a->tune.mode != 0 && a->tune.mode != 256) return DS_E_ARG;              // a forced generic / 128-pixel / register-staged route
+        if ((a->tune.variant & 31) == 7 || (a->tune.variant & 256)) return DS_E_ARG; // the 256 x 128 tiles forced / the plain 256 x 256 tile (A/B switches of the direct form)
+        if ((a->h & 1) || (a->w & 1) || (a->cout & 255)) return DS_E_SHAPE;
+    }
     const int geo_h = up2 ? a->h / 2 : a->h, geo_w = up2 ? a->w / 2 : a->w;       // the geometry the kernel tiles: the low-res image's under in_up2
     const long long M = (long long)a->n * geo_h * geo_w;
     if ((long long)a->n * a->h * a->w > 0x7fffffffLL - BM) return DS_E_SHAPE;
@@ -625,8 +637,14 @@ static int route_conv(const ds_conv_args* a, KParams& p, ConvRoute& r) {
         if (inv) p.t_variant |= 2048 | 8192;
         conv3x3_halo_route(p, r);
         p.splits = r.splits;
+        if (wino) {
+            // exactly the launches of kernel id 2565 without split-K, every column on the 256-column tiles
+            if (r.kernel_id != 2565 || r.splits != 1 || r.n256 != p.N || r.cols192 || !conv3x3_wino_applicable(p)) return DS_E_SHAPE;
+            r.wino = true;
+        }
         return DS_OK;
     }
+    if (wino) return DS_E_SHAPE;
     if (p.norm) return DS_E_SHAPE;           // fused input normalisation exists only in the halo kernel
     const bool emb_rows = inv && (a->tune.invariant & 2) && p.t_mode == 0 && p.t_variant == 0;
     if (emb_rows && gemv_rows_applicable(p, true)) r.kernel_id = 2573;                 // invariant embedding projection: the row kernel at any row count
@@ -647,6 +665,7 @@ extern "C" int ds_conv2d_nhwc(const ds_conv_args* a, void* stream) {
     const int rc = route_conv(a, p, r);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
+    if (r.wino) return launch_conv3x3_wino(p, s);
     switch (r.kernel_id) {
         case 0: return launch<0>(p, 1, s);
         case 2561: return launch_gemm_dma8(p, s);
@@ -680,6 +699,7 @@ extern "C" int ds_conv_route(const ds_conv_args* a, ds_conv_route_info* info) {
     info->splits = r.splits;
     info->f16_groups = r.ngroups;
     for (int i = 0; i < r.ngroups; ++i) info->f16_widths[i] = r.groups[i][2];
+    info->wino = r.wino ? 1 : 0;
     return DS_OK;
 }
 

@@ -638,6 +638,9 @@ struct ConvRoute {
     // ds_conv_args.in_up2, set by route_conv BEFORE conv3x3_halo_route: the KParams geometry is the low-res image's, a layer has four phases
     // (four times the workgroups, 4 taps per slab), never split-K, whole 128- / 192- / 256-column tiles only (kernel id 0 = refused)
     bool up2;
+    // ds_conv_args.wino: the launch runs the Winograd form (conv3x3_wino.hip) of the layer the fields above describe -- taken only where they
+    // say 256 x 256 tiles for every column and no split-K; the kernel id stays 2565
+    bool wino;
     // fp16-activation 3x3 kernel: column tiling, groups of (first column, tiles, width in 64-channel units), widest first
     int ngroups;
     int groups[4][3];
@@ -647,6 +650,10 @@ struct ConvRoute {
 bool conv3x3_halo_supported(const KParams& p);
 void conv3x3_halo_route(const KParams& p, ConvRoute& r);    // tile, split-K factor, column ranges, kernel id
 int launch_conv3x3_halo(KParams& p, const ConvRoute& r, hipStream_t stream);
+
+// conv3x3_wino.hip: Winograd F(2x2, 3x3) form of the layers of the 256 x 256 tiles (weights = ops.pack_conv_weight_wino)
+bool conv3x3_wino_applicable(const KParams& p);
+int launch_conv3x3_wino(KParams& p, hipStream_t stream);
 
 // conv3x3_halo2.hip: second-generation 256 x 128 tile (static tap schedule, double halo buffer), split fp16 hi/lo operands
 bool conv3x3_halo2_applicable(const KParams& p, int wide);

@@ -29,14 +29,19 @@ import torch
 
 from . import _lib, arch
 from ._lib import DS_ACT_SILU, DS_RESAMPLE_NONE, DS_RESAMPLE_DOWN, DS_RESAMPLE_UP
-from .ops import pack_conv_weight, pack_conv_weight_f16, pack_conv_weight_split, pack_conv_weight_up2, pack_linear_weight, pack_stem_weight
+from .ops import pack_conv_weight, pack_conv_weight_f16, pack_conv_weight_split, pack_conv_weight_up2, pack_conv_weight_wino, pack_linear_weight, pack_stem_weight
 from .plan import FUSE_NORM16_DEFAULT, Builder, Plan as _Plan, fuse_norm16_here, fuse_norm16_value, ptr as _ptr
 
 
 class UNetEngine:
     def __init__(self, spec: arch.UNetSpec, params: Dict[str, torch.Tensor], device='cuda', use_fp16=False, split_fp16=False,
-                 batch_invariant=False, up_phase=True):
-        """up_phase (exact fp32 mode only): conv0 of an up block, conv3x3(nearest_x2(silu(norm0(x)))), runs on the LOW-RES activated tensor as
+                 batch_invariant=False, up_phase=True, winograd=True):
+        """winograd (exact fp32 mode only, never with batch_invariant): the stride-1 3x3 layers the library would run on its 256 x 256 tiles
+        run in the Winograd form F(2x2, 3x3) instead (ds_conv_args.wino, csrc/conv3x3_wino.hip: 2.25 x fewer fp32 multiply-adds, weights
+        transformed once per build; the same launches, the same kernel ids) wherever the library takes the layer; layers it refuses -- and
+        every layer with False -- are emitted as the direct form, bit for bit.  Results differ from the direct form in rounding only (~1e-6
+        of a layer's output absmax; the per-evaluation bound of DESIGN.md section 2 is unchanged).
+        up_phase (exact fp32 mode only): conv0 of an up block, conv3x3(nearest_x2(silu(norm0(x)))), runs on the LOW-RES activated tensor as
         four 2x2 phase convolutions with weights folded at load time (ds_conv_args.in_up2: 4 taps per output pixel instead of 9, and the
         upsampled tensor is never written) wherever the library takes the layer; False = the upsampling pass and the 9-tap convolution
         (A/B runs, tests/test_hip_upconv.py).
@@ -57,6 +62,7 @@ class UNetEngine:
         self.split_fp16 = bool(split_fp16) and not self.use_fp16
         self.batch_invariant = bool(batch_invariant)
         self.up_phase = bool(up_phase) and not self.use_fp16 and not self.split_fp16
+        self.winograd = bool(winograd) and not self.use_fp16 and not self.split_fp16 and not self.batch_invariant
         # fp16 mode: GroupNorm apply + SiLU inside the fp16-activation convolution's LDS halo instead of a ds_norm_act pass (plan(): fz0 / fz1;
         # bit-identical results).  An attribute, not an argument, so that A/B runs flip it per engine: DS_FUSE_NORM16 sets the default.
         self.fuse_norm16 = fuse_norm16_value(os.environ.get('DS_FUSE_NORM16', FUSE_NORM16_DEFAULT))
@@ -111,6 +117,10 @@ class UNetEngine:
             w[f'{b.name}.conv1.w'] = pack_conv_weight(g(f'{p}.conv1.weight')); w[f'{b.name}.conv1.b'] = g(f'{p}.conv1.bias')
             if self.up_phase and b.up and b.cin % 32 == 0:
                 w[f'{b.name}.conv0.wup'] = pack_conv_weight_up2(g(f'{p}.conv0.weight'))      # the four folded phase matrices, once per build
+            if self.winograd and b.cin % 32 == 0 and b.cout % 256 == 0:
+                # Winograd-transformed weights, once per build (a fused skip projection's 1x1 columns follow them untransformed)
+                w[f'{b.name}.conv0.wwino'] = pack_conv_weight_wino(g(f'{p}.conv0.weight'))
+                w[f'{b.name}.conv1.wwino'] = pack_conv_weight_wino(g(f'{p}.conv1.weight'), g(f'{p}.skip.weight') if b.skip_conv else None)
             if self.conv_mode == 1 and b.cin % 64 == 0 and b.cout % 64 == 0:
                 w[f'{b.name}.conv0.w16'] = (pack_conv_weight_f16(g(f'{p}.conv0.weight')), 0)
                 w[f'{b.name}.conv1.w16'] = (pack_conv_weight_f16(g(f'{p}.conv1.weight'), g(f'{p}.skip.weight') if b.skip_conv else None), 0)
@@ -185,8 +195,9 @@ class UNetEngine:
                 block = self._block16 if self._dma16(bd, B, b) else self._block32
                 c1_in, c1_w, c1_kw = block(bd, ws, b, x0, c0, x1, c1)
                 out = self._block_out(bd, ws, b, f16_out)
-                bd.conv(c1_in, cout, cout, B, Ho, Ho, c1_w, cout, out, cout, 9, nm + '.conv1', scale=b.skip_scale, stats=True,
-                        w16=w.get(f'{nm}.conv1.w16'), **c1_kw)
+                c1_kw = dict(scale=b.skip_scale, stats=True, w16=w.get(f'{nm}.conv1.w16'), **c1_kw)
+                c1_w = self._wino_pick(bd, c1_in, cout, cout, B, Ho, c1_w, w.get(f'{nm}.conv1.wwino'), cout, out, c1_kw)
+                bd.conv(c1_in, cout, cout, B, Ho, Ho, c1_w, cout, out, cout, 9, nm + '.conv1', **c1_kw)
                 if b.heads:
                     out = self._attention(bd, ws, b, out, f16_out)
             x_cur = (out, cout)
@@ -327,6 +338,14 @@ class UNetEngine:
             kw.update(res=s0, res_ld=cout)
         return c1_in, w[f'{nm}.conv1.w'], dict(kw, bias=w[f'{nm}.conv1.b'])
 
+    def _wino_pick(self, bd, x0, c0, ld0, n, side, wgt, wwino, cout, out, kw):
+        """Weights of a 3x3 launch bd.conv(x0, ..., **kw): the Winograd-transformed ones -- and kw['wino'] = True -- where this engine has
+        them and the library takes the layer in that form (Builder.wino_ok), else `wgt` and kw untouched."""
+        if wwino is not None and kw.get('w16') is None and bd.wino_ok(x0, c0, ld0, n, side, side, wwino, cout, out, cout, **kw):
+            kw['wino'] = True
+            return wwino
+        return wgt
+
     def _block32(self, bd, ws, b, x0, c0, x1, c1):
         """norm0 .. norm1 and the skip path of a block on fp32 activations; returns (input, weights, keywords) of its conv1.  GroupNorm +
         SiLU ride in the 3x3 convolution's halo loader where the LDS-halo kernel takes the shape, else they are a pass (always for a
@@ -352,13 +371,16 @@ class UNetEngine:
         elif fuse and rs == DS_RESAMPLE_NONE:
             bd.norm('stats', x0, c0, c0, n, Hin, Hin, nm + '.norm0.stats', groups=G_in, eps=b.eps, gamma=w[f'{nm}.norm0.g'],
                     beta=w[f'{nm}.norm0.b'], coefs=ncoef, **src)
-            bd.conv(x0, c0, c0, n, Ho, Ho, w[f'{nm}.conv0.w'], cout, ws.hbuf, cout, 9, nm + '.conv0', norm_coefs=ncoef, norm_act=DS_ACT_SILU,
-                    **src, **conv0)
+            kw0 = dict(norm_coefs=ncoef, norm_act=DS_ACT_SILU, **src, **conv0)
+            w0 = self._wino_pick(bd, x0, c0, c0, n, Ho, w[f'{nm}.conv0.w'], w.get(f'{nm}.conv0.wwino'), cout, ws.hbuf, kw0)
+            bd.conv(x0, c0, c0, n, Ho, Ho, w0, cout, ws.hbuf, cout, 9, nm + '.conv0', **kw0)
         else:
             bd.norm('stats', x0, c0, c0, n, Hin, Hin, nm + '.norm0.stats', groups=G_in, eps=b.eps, **src)
             bd.norm('apply', x0, c0, c0, n, Hin, Hin, nm + '.norm0', groups=G_in, eps=b.eps, gamma=w[f'{nm}.norm0.g'], beta=w[f'{nm}.norm0.b'],
                     act=DS_ACT_SILU, resample=rs, out=ws.act, out_ld=cin, **src)
-            bd.conv(ws.act, cin, cin, n, Ho, Ho, w[f'{nm}.conv0.w'], cout, ws.hbuf, cout, 9, nm + '.conv0', **conv0)
+            kw0 = dict(conv0)
+            w0 = self._wino_pick(bd, ws.act, cin, cin, n, Ho, w[f'{nm}.conv0.w'], w.get(f'{nm}.conv0.wwino'), cout, ws.hbuf, kw0)
+            bd.conv(ws.act, cin, cin, n, Ho, Ho, w0, cout, ws.hbuf, cout, 9, nm + '.conv0', **kw0)
         # norm1 (+adaptive scale/shift) + silu
         if fuse:
             bd.norm('stats', ws.hbuf, cout, cout, n, Ho, Ho, nm + '.norm1.stats', groups=G_out, eps=b.eps, gamma=w[f'{nm}.norm1.g'],
@@ -453,11 +475,11 @@ class EDMDenoiser:
     edm_raw_output = True      # solvers._Run: ds_solver_update applies the EDM preconditioning to the raw output itself
 
     def __init__(self, spec: arch.UNetSpec, params: Dict[str, torch.Tensor], device='cuda', use_fp16=False, split_fp16=False,
-                 batch_invariant=False, up_phase=True):
-        """batch_invariant: same seed, same bits at any batch (UNetEngine).  up_phase: UNetEngine."""
+                 batch_invariant=False, up_phase=True, winograd=True):
+        """batch_invariant: same seed, same bits at any batch (UNetEngine).  up_phase, winograd: UNetEngine."""
         self.spec = spec
         self.engine = UNetEngine(spec, params, device, use_fp16=use_fp16, split_fp16=split_fp16, batch_invariant=batch_invariant,
-                                 up_phase=up_phase)
+                                 up_phase=up_phase, winograd=winograd)
         self.batch_invariant = bool(batch_invariant)
         self.device = self.engine.device
         self.img_resolution = spec.img_resolution
@@ -472,11 +494,11 @@ class EDMDenoiser:
 
     @classmethod
     def from_config(cls, name_or_kwargs, seed=0, mode='signal', device='cuda', use_fp16=False, split_fp16=False, batch_invariant=False,
-                    up_phase=True):
+                    up_phase=True, winograd=True):
         kw = arch.NAMED_CONFIGS[name_or_kwargs] if isinstance(name_or_kwargs, str) else name_or_kwargs
         spec = arch.edm_precond_spec(**kw)
         return cls(spec, arch.init_params(spec, seed=seed, mode=mode), device, use_fp16=use_fp16, split_fp16=split_fp16,
-                   batch_invariant=batch_invariant, up_phase=up_phase)
+                   batch_invariant=batch_invariant, up_phase=up_phase, winograd=winograd)
 
     @classmethod
     def from_reference_module(cls, net, device='cuda', use_fp16=None, batch_invariant=False):

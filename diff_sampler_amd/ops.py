@@ -71,6 +71,38 @@ def pack_conv_weight_up2(w: torch.Tensor, row_pad: int = 128, k_pad: int = 32) -
     return out.contiguous()
 
 
+WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))        # F(2x2, 3x3): U = G g G^T
+WINO_BT = ((1.0, 0.0, -1.0, 0.0), (0.0, 1.0, 1.0, 0.0), (0.0, -1.0, 1.0, 0.0), (0.0, 1.0, 0.0, -1.0))      # V = B^T d B
+WINO_AT = ((1.0, 1.0, 1.0, 0.0), (0.0, 1.0, -1.0, -1.0))                               # Y = A^T M A
+
+
+def pack_conv_weight_wino(w: torch.Tensor, extra: Optional[torch.Tensor] = None, row_pad: int = 64, k_pad: int = 8) -> torch.Tensor:
+    """Weights of ds_conv_args.wino (csrc/conv3x3_wino.hip): [Cout, Cin, 3, 3] -> the Winograd F(2x2, 3x3) transform U = G g G^T of every
+    (cout, cin) kernel, computed in fp64 and rounded once to fp32, laid out as the kernel's LDS image so that a slab is one linear 32 KiB
+    copy: [Cout_pad / 64][Cin / 8][16 positions i*4 + j][2 channel quads][64 rows][4 channels], rows zero-padded to a multiple of 64.
+    extra: the 1x1 skip projection [Cout, Ce, 1, 1] fused into the layer (ds_conv_args.e0 / e1, Ce % 32 == 0): its columns stay untransformed
+    and follow the U images as [Cout_pad / 64][Ce / 32][4 channel groups][2 quads][64 rows][4]; the result is then one flat tensor."""
+    cout, cin, kh, kw = w.shape
+    assert kh == 3 and kw == 3 and cin % k_pad == 0 and row_pad == 64 and k_pad == 8
+    G = torch.tensor(WINO_G, dtype=torch.float64, device=w.device)
+    u = torch.einsum('ik,ockl,jl->ijoc', G, w.to(torch.float64), G)                    # [4, 4, cout, cin]
+    rows = -(-cout // row_pad) * row_pad
+    full = torch.zeros(4, 4, rows, cin, dtype=torch.float64, device=w.device)
+    full[:, :, :cout] = u
+    # (i, j, nt, row, s, kh, e) -> (nt, s, i, j, kh, row, e)
+    m = full.reshape(4, 4, rows // 64, 64, cin // 8, 2, 4).permute(2, 4, 0, 1, 5, 3, 6)
+    u32 = m.to(torch.float32).contiguous().reshape(rows // 64, cin // 8, 16, 2, 64, 4)
+    if extra is None:
+        return u32
+    ce = extra.shape[1]
+    assert extra.shape[0] == cout and extra.shape[2:] == (1, 1) and ce % 32 == 0
+    e = torch.zeros(rows, ce, dtype=torch.float32, device=w.device)
+    e[:cout] = extra.reshape(cout, ce).to(torch.float32)
+    # (nt, row, slab, group, kh, e) -> (nt, slab, group, kh, row, e)
+    e = e.reshape(rows // 64, 64, ce // 32, 4, 2, 4).permute(0, 2, 3, 4, 1, 5).contiguous()
+    return torch.cat([u32.reshape(-1), e.reshape(-1)])
+
+
 def pack_conv_weight_f16(w: torch.Tensor, extra: Optional[torch.Tensor] = None, row_pad: int = 128) -> torch.Tensor:
     """fp16 weights of the reduced-precision 3x3 convolution (ds_conv_args.wgt_f16): [Cout, Cin, 3, 3] (+ optional 1x1 skip
     projection [Cout, Ce, 1, 1] appended along K) -> [Cout_pad, K] halfs, K = (slab*9 + tap)*64 + cc with c = slab*64 + cc,

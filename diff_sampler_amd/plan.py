@@ -416,7 +416,7 @@ class Builder:
     def conv(self, x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, taps, name, x1=None, c1=0, ld1=0, bias=None, cbias=None,
              cbias_ld=0, cbias_rows=1, res=None, res_ld=0, scale=1.0, act=DS_ACT_NONE, norm_coefs=None, norm_act=DS_ACT_NONE,
              e0=None, ec0=0, e1=None, ec1=0, stride=1, stats=False, w16=None, out_nchw=0, in_f16=False, out_f16=False, emb=False,
-             in_up2=False):
+             in_up2=False, wino=False):
         """stats=True: the epilogue also leaves the output's per-(64-row block, channel) sums for the consumer's GroupNorm
         (honoured when cout % 64 == 0; otherwise the consumer falls back to a ds_gn_stats pass).
         w16: fp16 weights of the same layer (ops.pack_conv_weight_f16); used -- with the fp16-operand kernel -- when the
@@ -426,7 +426,11 @@ class Builder:
         emb: a projection of the embedding path (one row per image or one shared row): in the invariant mode the row kernel at every row
         count (ds_conv_tune.invariant bit 1), so that both sigma forms and every batch give the same embedding rows.
         in_up2: the layer is conv3x3(nearest_x2(x0)) on the low-res rows x0 ([n][h/2][w/2]; h, w = the output size) with `wgt` =
-        ops.pack_conv_weight_up2 (ds_conv_args.in_up2; fp32 only -- the caller asked up2_ok())."""
+        ops.pack_conv_weight_up2 (ds_conv_args.in_up2; fp32 only -- the caller asked up2_ok()).
+        wino: the Winograd form of the layer, `wgt` = ops.pack_conv_weight_wino (ds_conv_args.wino; exact fp32 only -- the caller asked
+        wino_ok())."""
+        if wino:
+            assert w16 is None and not in_f16 and not in_up2 and stride == 1 and taps == 9 and not self.invariant, name
         if in_up2:
             assert w16 is None and not in_f16 and norm_coefs is None and not ec0 and res is None and stride == 1 and taps == 9, name
         if taps == 1 and x0.dtype == torch.float16:
@@ -459,6 +463,7 @@ class Builder:
         a.wgt_f16, a.wgt_shift = (self.conv_mode, shift) if f16 else (0, 0)
         a.in_f16 = 1 if in_f16 else 0
         a.in_up2 = 1 if in_up2 else 0
+        a.wino = 1 if wino else 0
         if self.invariant:
             a.tune.invariant = 3 if emb else 1
         if out_f16 or out.dtype == torch.float16:          # fp16 output rows: conv0 outputs, projection operands, the fp16 residual stream
@@ -488,6 +493,23 @@ class Builder:
             a.tune.invariant = 1
         info = ConvRouteInfo()
         return self.lib.ds_conv_route(C.byref(a), C.byref(info)) == 0
+
+    def wino_ok(self, x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, x1=None, c1=0, ld1=0, bias=None, cbias=None, cbias_ld=0, cbias_rows=1,
+                res=None, res_ld=0, scale=1.0, act=DS_ACT_NONE, norm_coefs=None, norm_act=DS_ACT_NONE, e0=None, ec0=0, e1=None, ec1=0, stats=False, **_):
+        """Does the library take this layer in the Winograd form (ds_conv_args.wino)?  Asked of ds_conv_route (host logic only) with the
+        arguments conv(..., wino=True) would pass: yes exactly where the direct form would run on the 256 x 256 tiles without split-K."""
+        if self.invariant or self.conv_mode:
+            return False
+        a = ConvArgs(ptr(x0), ptr(x1), c0, c1, ld0, ld1, n, h, w, 9, ptr(wgt), cout, ptr(bias), ptr(cbias), cbias_ld, cbias_rows, ptr(res), res_ld,
+                     scale, act, ptr(out), out_ld, ptr(norm_coefs), norm_act, ptr(e0), ptr(e1), ec0, ec1, ec0, ec1)
+        a.wino = 1
+        if self.ws is None:
+            self.ws = self.new(SPLITK_WORKSPACE_FLOATS)
+        a.workspace, a.workspace_floats = ptr(self.ws), self.ws.numel()      # as conv() offers it: the split-K decision is part of the answer
+        if stats and cout % 64 == 0 and out_ld == cout:
+            a.stats_out = ptr(out)              # (any 16-byte-aligned address: the probe launches nothing)
+        info = ConvRouteInfo()
+        return self.lib.ds_conv_route(C.byref(a), C.byref(info)) == 0 and info.wino == 1
 
     @staticmethod
     def _tune_key(a, stride):

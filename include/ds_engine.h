@@ -211,6 +211,16 @@ typedef struct ds_conv_args {
      * kernel takes, else DS_E_SHAPE; any other combination DS_E_ARG -- from ds_conv_kernel_id / ds_conv_route as well.  The kernel id is that
      * of the tile shape it runs on (2565 / 256 / 128 / 1284 / 2568). */
     int in_up2;
+    /* ABI 6, appended; 0 = as before.  1: THE WINOGRAD FORM F(2x2, 3x3) of a stride-1 3x3 layer in exact fp32 (csrc/conv3x3_wino.hip): `wgt` holds
+     * the transformed weights U = G g G^T of ops.pack_conv_weight_wino, [cout / 64][(c0+c1) / 8][16 positions][2 channel quads][64 rows][4],
+     * followed -- when ec0 != 0 -- by the untransformed 1x1 columns [cout / 64][(ec0+ec1) / 32][4 groups][2 quads][64 rows][4];
+     * 16 multiplies per (cin, cout) pair and 2 x 2 output patch instead of 36, still on the fp32 MFMA.  norm_coefs, x1, e0 / e1, bias, cbias, out_scale,
+     * res, act NONE / SILU and stats_out are honoured with the semantics of the direct form (an image's h w / 64 column-sum blocks stay
+     * contiguous; a block is 64 pixels of two patch rows).  Taken ONLY where the direct form would run on the 256 x 256 tiles (kernel id 2565,
+     * no split-K); the reported kernel id stays 2565 and ds_conv_route_info.wino is 1.  Refused: tune.invariant, in_up2, fp16 / split flags,
+     * stride 2, out_nchw, a forced generic / 128 / register-staged route (DS_E_ARG); odd h or w, a cout that is not a multiple of 256,
+     * or a layer the 256 x 256 tiles do not take (DS_E_SHAPE) -- from ds_conv_kernel_id / ds_conv_route as well. */
+    int wino;
 } ds_conv_args;
 
 DS_API int ds_conv2d_nhwc(const ds_conv_args* a, void* stream);
@@ -241,6 +251,7 @@ typedef struct ds_conv_route_info {
     int splits;          /* split-K factor: partial planes in ds_conv_args.workspace, reduced by a second launch (1 = none) */
     int f16_groups;
     int f16_widths[4];
+    int wino;            /* 1: the launch runs the Winograd form (ds_conv_args.wino; appended to ABI 6) */
 } ds_conv_route_info;
 DS_API int ds_conv_route(const ds_conv_args* a, ds_conv_route_info* info);
 

@@ -70,6 +70,7 @@ ap.add_argument('--f16io', action='store_true', help='with --dma16: fp16 output 
 ap.add_argument('--extra', action='store_true', help='append the fused 1x1 skip projection (ec0 = c0 + c1 raw columns) as conv1 of a block with a skip conv has it')
 ap.add_argument('--ws', action='store_true', help='give the launcher a split-K workspace (256 MiB), as the engine plans do (the persistent schedule needs it)')
 ap.add_argument('--splits', type=int, default=0, help='ds_conv_tune.splits (with --ws): force the split-K factor, 1 = never split')
+ap.add_argument('--wino', action='store_true', help='exact fp32 3x3 shapes: ask for the Winograd F(2x2, 3x3) form (ds_conv_args.wino); a shape the route refuses runs the direct form (wino=0 in its row)')
 ap.add_argument('--norm', action='store_true', help='fused GroupNorm affine + SiLU in the halo loader, as the network uses it')
 args = ap.parse_args()
 STRIDE2 = args.shapes == 'sd15down'
@@ -147,6 +148,17 @@ for si, (res, c0, c1, cout, taps) in enumerate(SHAPES):
     if args.ws:
         scratch = torch.empty(64 << 20, device=dev)
         a.workspace, a.workspace_floats = scratch.data_ptr(), scratch.numel()
+    wino = 0
+    if args.wino and taps == 9 and not (args.f16 or args.split or STRIDE2):
+        ww = ops.pack_conv_weight_wino(w, we if args.extra else None)
+        direct = a.wgt
+        a.wgt, a.wino = ww.data_ptr(), 1
+        info = _lib.ConvRouteInfo()
+        if lib.ds_conv_route(C.byref(a), C.byref(info)) == 0 and info.wino:
+            wino = 1
+        else:
+            a.wgt, a.wino = direct, 0
+    k_exec = 2.25 if wino else 1.0                    # executed multiply-adds of the 3x3 columns = algorithmic / 2.25 on a Winograd launch
     st = _lib.stream_ptr()
     if args.variants:
         import statistics
@@ -164,7 +176,7 @@ for si, (res, c0, c1, cout, taps) in enumerate(SHAPES):
                 if rnd:
                     times[v].append(e0.elapsed_time(e1) / args.iters)
         a.tune.variant = 0
-        print(f'[{si}] {res}x{res} {c0}+{c1}->{cout} taps={taps} M={M} norm={int(args.norm)}: ' +
+        print(f'[{si}] {res}x{res} {c0}+{c1}->{cout} taps={taps} M={M} norm={int(args.norm)} wino={wino}: ' +
               '  '.join(f'v{v}: {statistics.median(t):.3f} ms {fl / statistics.median(t) / 1e9:6.1f} TF (min {fl / min(t) / 1e9:6.1f})' for v, t in times.items()), flush=True)
         continue
     rc = fn(C.byref(a), st); assert rc == 0, rc
@@ -177,7 +189,7 @@ for si, (res, c0, c1, cout, taps) in enumerate(SHAPES):
     ms = e0.elapsed_time(e1) / args.iters
     fl = 2.0 * M * taps * (c0 + c1) * cout
     tot_fl += fl; tot_t += ms
-    msg = f'[{si}] {res}x{res} {c0}+{c1}->{cout} taps={taps} M={M}: {ms:8.3f} ms  {fl/ms/1e9:7.1f} TFLOP/s'
+    msg = f'[{si}] {res}x{res} {c0}+{c1}->{cout} taps={taps} M={M} wino={wino}: {ms:8.3f} ms  {fl/ms/1e9:7.1f} TFLOP/s  (executed {fl/k_exec/ms/1e9:7.1f})'
     if args.dma16:        # the launch's algorithmic HBM bytes: fp16 activations in, output and residual rows out / in
         byt = MI * (c0 + c1) * 2 + M * cout * (2 if a.out_f16 else 4) + (M * cout * (2 if a.res_f16 else 4) if a.res else 0)
         msg += f'  {byt / ms / 1e6:6.0f} GB/s'

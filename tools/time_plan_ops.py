@@ -24,6 +24,7 @@ ap.add_argument('--reps', type=int, default=5)
 ap.add_argument('--fp32', action='store_true')
 ap.add_argument('--top', type=int, default=45)
 ap.add_argument('--json', default='')
+ap.add_argument('--no-winograd', action='store_true', help='exact fp32: the direct form of every 3x3 layer (UNetEngine winograd=False)')
 args = ap.parse_args()
 lib = _lib.load()
 dev = torch.device('cuda')
@@ -37,7 +38,7 @@ if args.config == 'sd15':
     run = lambda: net(x, 3.0, condition=c, unconditional_condition=uc)
 else:
     from diff_sampler_amd.engine import EDMDenoiser
-    net = EDMDenoiser.from_config(args.config, seed=0, use_fp16=f16)
+    net = EDMDenoiser.from_config(args.config, seed=0, use_fp16=f16, winograd=not args.no_winograd)
     R = net.img_resolution
     x = torch.randn(args.batch, 3, R, R, generator=g).to(dev) * 3
     lab = torch.eye(net.label_dim)[torch.randint(net.label_dim, (args.batch,), generator=g)].to(dev) if net.label_dim else None
@@ -53,7 +54,8 @@ attn_fns = (lib.ds_attention, lib.ds_attention_f16)
 
 
 def signature(op):
-    """(label, flops, bytes) of a launch from its argument struct."""
+    """(label, flops, bytes, executed-FLOP divisor) of a launch from its argument struct.  A Winograd launch (ds_conv_args.wino) executes
+    16 multiplies per 2 x 2 patch and (cin, cout) pair of its 3x3 columns instead of 36: divisor 2.25 on that part."""
     a = op.keep[0] if op.keep else None
     if op.fn is conv_fn:
         m = a.n * a.h * a.w
@@ -65,19 +67,20 @@ def signature(op):
         n_eff = cout // 2 if a.act == 2 else cout
         by = m * s * s * (a.c0 + a.c1) * eb + m * (a.ec0 + a.ec1) * eb + m * n_eff * ob + (m * n_eff * (2 if a.res_f16 else 4) if a.res else 0) + k * cout * 2
         lab = f'conv{"3x3" if a.taps == 9 else "1x1"} n={a.n} {a.h}x{a.w} {a.c0}+{a.c1}(+{a.ec0}+{a.ec1})->{cout}' \
-              f'{" s2" if s == 2 else ""}{" geglu" if a.act == 2 else ""}{" norm" if a.norm_coefs else ""}{" res" if a.res else ""}{" f16" if a.in_f16 else ""}{" up2" if a.in_up2 else ""}'
-        return lab, 2.0 * m * k * cout, by
+              f'{" s2" if s == 2 else ""}{" geglu" if a.act == 2 else ""}{" norm" if a.norm_coefs else ""}{" res" if a.res else ""}{" f16" if a.in_f16 else ""}{" up2" if a.in_up2 else ""}{" wino" if a.wino else ""}'
+        k_exec = (a.taps * (a.c0 + a.c1) / 2.25 if a.wino else (4 if a.in_up2 else a.taps) * (a.c0 + a.c1)) + a.ec0 + a.ec1
+        return lab, 2.0 * m * k * cout, by, k / k_exec
     if op.fn is norm_fn:
         m = a.n * a.h * a.w
         cc = a.c0 + a.c1
         by = m * cc * ((2 if a.in_f16 else 4) + (2 if a.out_f16 else 4)) + (m * cc * 2 if a.raw_out else 0)
-        return f'norm n={a.n} {a.h}x{a.w} c={a.c0}+{a.c1} rs={a.resample}{" fin" if a.stats0 else ""}{" raw" if a.raw_out else ""}{" f16" if a.in_f16 else ""}', 0.0, by
+        return f'norm n={a.n} {a.h}x{a.w} c={a.c0}+{a.c1} rs={a.resample}{" fin" if a.stats0 else ""}{" raw" if a.raw_out else ""}{" f16" if a.in_f16 else ""}', 0.0, by, 1.0
     if op.fn is fin_fn:
-        return f'gn_finalize n={a.n} hw={a.hw} c={a.c0}+{a.c1}', 0.0, 0
+        return f'gn_finalize n={a.n} hw={a.hw} c={a.c0}+{a.c1}', 0.0, 0, 1.0
     if op.fn in attn_fns:
         fl = 4.0 * a.batch * a.heads * a.sq * a.skv * a.d
-        return f'attn b={a.batch} h={a.heads} sq={a.sq} skv={a.skv} d={a.d}{" f16" if op.fn is lib.ds_attention_f16 else ""}', fl, 0
-    return op.name.split('.')[-1] if '.' in op.name else op.name, 0.0, 0
+        return f'attn b={a.batch} h={a.heads} sq={a.sq} skv={a.skv} d={a.d}{" f16" if op.fn is lib.ds_attention_f16 else ""}', fl, 0, 1.0
+    return op.name.split('.')[-1] if '.' in op.name else op.name, 0.0, 0, 1.0
 
 
 sigs = [signature(op) for op in ops]
@@ -104,20 +107,20 @@ torch.cuda.synchronize()
 whole = e0.elapsed_time(e1) * 1e3 / args.reps
 
 groups = collections.OrderedDict()
-for (lab, fl, by), t in zip(sigs, tot):
-    gq = groups.setdefault(lab, dict(n=0, us=0.0, flops=fl, bytes=by))
+for (lab, fl, by, div), t in zip(sigs, tot):
+    gq = groups.setdefault(lab, dict(n=0, us=0.0, flops=fl, bytes=by, exec_div=div))
     gq['n'] += 1
     gq['us'] += t
 rows = sorted(groups.items(), key=lambda kv: -kv[1]['us'])
 ssum = sum(tot)
 print(f'# {args.config} batch {args.batch} {"fp16" if f16 else "fp32"}: {len(ops)} launches per evaluation, sum of event pairs {ssum/1e3:.2f} ms, '
       f'plan.run {whole/1e3:.2f} ms per evaluation')
-print(f'{"layer":78s} {"n":>3s} {"us each":>8s} {"us all":>8s} {"share":>6s} {"TF":>7s} {"GB/s":>7s}')
+print(f'{"layer":78s} {"n":>3s} {"us each":>8s} {"us all":>8s} {"share":>6s} {"TF":>7s} {"TF exec":>7s} {"GB/s":>7s}')
 for lab, gq in rows[:args.top]:
     each = gq['us'] / gq['n']
     tf = gq['flops'] / each / 1e6 if gq['flops'] else 0.0
     gbs = gq['bytes'] / each / 1e3 if gq['bytes'] else 0.0
-    print(f'{lab[:78]:78s} {gq["n"]:3d} {each:8.1f} {gq["us"]:8.1f} {gq["us"]/ssum:6.3f} {tf:7.0f} {gbs:7.0f}')
+    print(f'{lab[:78]:78s} {gq["n"]:3d} {each:8.1f} {gq["us"]:8.1f} {gq["us"]/ssum:6.3f} {tf:7.0f} {tf / gq["exec_div"]:7.0f} {gbs:7.0f}')
 if args.json:
     with open(args.json, 'w') as fh:
         json.dump(dict(config=args.config, batch=args.batch, fp16=f16, launches=len(ops), sum_us=ssum, plan_run_us=whole,
