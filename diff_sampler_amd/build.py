@@ -164,5 +164,49 @@ def build_lib(force=False, verbose=True):
     return build_libs(('',), force=force, verbose=verbose)[0]
 
 
+# The SECOND library: csrc/metrics/*.hip -> csrc/metrics/libdsmetrics.so (evaluation metrics; ABI in csrc/metrics/ds_metrics.h, binding in
+# _metrics_lib.py).  The globs above are not recursive: nothing under metrics/ is in sources(), headers(), a stress variant or a source hash,
+# so a change there invalidates no tile table and no profile tie.  Its translation units may include ../ds_common.h (read-only).
+METRICS_DIR = os.path.join(CSRC, 'metrics')
+METRICS_LIB = os.path.join(METRICS_DIR, 'libdsmetrics.so')
+METRICS_OBJ = os.path.join(METRICS_DIR, 'obj')
+METRICS_STAMP = os.path.join(METRICS_DIR, '.build_flags')
+
+
+def metrics_sources():
+    return sorted(glob.glob(os.path.join(METRICS_DIR, '*.hip')))
+
+
+def metrics_needs_build():
+    if not os.path.exists(METRICS_LIB) or not _stamp_ok(METRICS_STAMP, _flags_stamp()):
+        return True
+    t = os.path.getmtime(METRICS_LIB)
+    return any(os.path.getmtime(d) > t for d in metrics_sources() + glob.glob(os.path.join(METRICS_DIR, '*.h')) + headers())
+
+
+def build_metrics_lib(force=False, verbose=True):
+    if not (force or metrics_needs_build()):
+        return METRICS_LIB
+    hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
+    if not os.path.exists(hipcc):
+        raise RuntimeError('hipcc not found: libdsmetrics.so cannot be built on this machine')
+
+    def run(cmd):
+        if verbose:
+            print(' '.join(cmd), flush=True)
+        subprocess.check_call(cmd)
+
+    os.makedirs(METRICS_OBJ, exist_ok=True)
+    objs = []
+    for src in metrics_sources():                               # every object again: the library is one or two small translation units
+        objs.append(os.path.join(METRICS_OBJ, os.path.basename(src)[:-4] + '.o'))
+        run([hipcc, f'--offload-arch={ARCH}'] + BASE_FLAGS + EXTRA_FLAGS + ['-c', src, '-o', objs[-1]])
+    run([hipcc, f'--offload-arch={ARCH}', '-shared', '-o', METRICS_LIB] + objs)          # visibility and PIC are compile-time (BASE_FLAGS)
+    with open(METRICS_STAMP, 'w') as fh:
+        fh.write(_flags_stamp())
+    return METRICS_LIB
+
+
 if __name__ == '__main__':
     build_libs(('',) + (tuple(VARIANTS) if '--variants' in sys.argv else ()), force='--force' in sys.argv)
+    build_metrics_lib(force='--force' in sys.argv)
