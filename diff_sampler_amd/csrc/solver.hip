@@ -202,6 +202,9 @@ __global__ void __launch_bounds__(256) quantize_kernel(const float* __restrict__
         const int img = (int)(pix / HW);
         const int p = (int)(pix - (long long)img * HW);
         for (int ch = 0; ch < c; ++ch) {
+            // product and sum rounded on their own, like ATen: a fused multiply-add lands just below an integer that the reference reaches
+            // (x near -1: the product's rounding exceeds the sum's ulp), and the truncation below then gives one level less
+#pragma clang fp contract(off)
             float v = x[((size_t)img * c + ch) * HW + p] * 127.5f + 128.0f;
             v = fminf(fmaxf(v, 0.0f), 255.0f);
             out[pix * c + ch] = (uint8_t)v;        // truncation, like .to(torch.uint8) (sample.py:311)
@@ -584,9 +587,10 @@ extern "C" int ds_dpmpp_x0_step(const ds_update_args* a, float p, void* stream) 
     if (a->n <= 0 || a->c <= 0 || a->h <= 0 || a->w <= 0) return DS_E_ARG;
     if (a->raw && !a->afs && a->f_ld != 0) return DS_E_ARG;                  // the raw network output must be channel-planar here
     if (a->coefs && a->coef_rows != 1 && a->coef_rows != a->n) return DS_E_ARG;
+    if (a->hist[2]) return DS_E_ARG;                                         // x' combines m0 with hist[0] and hist[1] only (DPM-Solver++ order <= 3)
     const long long per = (long long)a->c * a->h * a->w;
     bool al = ds_aligned16(a->xe) && ds_aligned16(a->xb) && (a->afs || ds_aligned16(a->f)) && (!a->x_out || ds_aligned16(a->x_out)) &&
-              (!a->m_out || ds_aligned16(a->m_out)) && !a->hist[2];
+              (!a->m_out || ds_aligned16(a->m_out));
     for (int i = 0; i < 2; ++i) if (a->hist[i] && !ds_aligned16(a->hist[i])) al = false;
     if (a->variant == 0 && al && ds_dpmpp_x0_step_in_registers(per)) {
         const dim3 grid(a->n);

@@ -511,7 +511,7 @@ DS_API int ds_solver_update(const ds_update_args* a, void* stream);
  *   m0 = clamp(D, -s, s) / s,  s = max(quantile_p(|D|), 1)      (dynamic thresholding; the same radix select as ds_dynamic_threshold)
  *   x' = hcoefs[0] * xb + hcoefs[1] * m0 + hcoefs[2] * hist[0] + hcoefs[3] * hist[1]
  * m_out receives m0 (the solver's history entry), x_out receives x'.  Replaces the three launches D pass -> threshold -> combination.
- * c * h * w <= ~38 000 elements per sample (LDS); f_ld must be 0 (channel-planar F).
+ * c * h * w <= 38 144 elements per sample (LDS, else DS_E_SHAPE); f_ld must be 0 (channel-planar F); hist[2] must be NULL (DS_E_ARG).
  * Samples of 3x32x32, 3x64x64, 4x64x64 (and 3x16x16) values with 16-B aligned tensors and at most two history tensors run on the
  * register-resident kernel (every operand touched once: 3-4 R + 2 W passes, HBM-bound from a few thousand images per launch);
  * ds_dpmpp_x0_step_in_registers(c*h*w) tells which, ds_update_args.variant = 1 forces the LDS kernel.
@@ -538,7 +538,8 @@ DS_API int ds_cfg_denoise(const float* x, const float* f, int f_ld, const float*
 /* y = a * x (latents * t_steps[0], solvers.py:68). */
 DS_API int ds_scale(const float* x, float a, float* y, long long count, void* stream);
 
-/* images uint8 NHWC <- clip(x * 127.5 + 128, 0, 255), x NCHW (sample.py:311). */
+/* images uint8 NHWC <- clip(x * 127.5 + 128, 0, 255), x NCHW (sample.py:311); product and sum each rounded to fp32 (no fused
+ * multiply-add), then truncated: the same level as ATen for every input. */
 DS_API int ds_quantize_u8_nhwc(const float* x, uint8_t* out, int n, int c, int h, int w, void* stream);
 
 /* dst[0..count) = value. */

@@ -1,5 +1,6 @@
 """GPU: GITS schedule search (cost matrix from trajectory moments, DP, AFS slot search) against the real reference's
-outputs on the same seeded warm-up latents (tests/golden/gits.npz, made by oracle/gen_golden.py --part gits)."""
+outputs on the same seeded warm-up latents (tests/golden/gits.npz, made by oracle/gen_golden.py --part gits), and the cost
+kernels themselves (moments, closed-form 'dev' cost, 'l1' / 'l2' pair kernel) against fp64 restatements of the definition."""
 import os
 import sys
 
@@ -80,3 +81,99 @@ def test_get_dp_list_on_a_latent_diffusion_denoiser_matches_reference():
     # without the test hooks the search draws its own conditions (seeded N(0,1) CLIP-shaped states for an engine net) and still returns a path
     dp2 = gits_utils.get_dp_list(net, torch.device('cuda'), **kwargs)
     assert dp2[0] == 0 and dp2[-1] == kwargs['num_steps_tea'] - 1 and len(dp2) == kwargs['num_steps']
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The cost kernels against the cost's definition (tests/_kernel_refs.py: fp64 on the CPU, synthetic trajectories, no network).  The
+# dp_list tests above see the cost matrix only through the argmin path of the dynamic programme.
+
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import _kernel_refs as R  # noqa: E402
+
+_TRAJ = {}
+
+
+def _traj(shape):
+    """(traj, eps, t) of one synthetic trajectory on the CPU and (traj, eps) on the device, made once per shape."""
+    if shape not in _TRAJ:
+        traj, eps, t = R.degenerate_trajectory() if shape == 'degenerate' else R.synthetic_trajectory(*shape)
+        _TRAJ[shape] = (traj, eps, t, traj.cuda(), eps.cuda())
+    return _TRAJ[shape]
+
+
+@pytest.mark.parametrize('shape', R.TRAJ_SHAPES)
+@pytest.mark.parametrize('with_eps', [False, True])
+def test_trajectory_moments_match_fp64_dot_products(shape, with_eps):
+    from diff_sampler_amd import gits_utils
+    traj, eps, _, traj_d, eps_d = _traj(shape)
+    got = gits_utils.trajectory_moments(traj_d, eps_d if with_eps else None)
+    ref, ref_abs = R.traj_moments_ref(traj, eps if with_eps else None)
+    assert got.shape == ref.shape == (shape[0], shape[1], 6)
+    assert np.all(np.abs(got - ref) <= 1e-12 * ref_abs), float((np.abs(got - ref) / np.maximum(ref_abs, 1e-300)).max())
+    if not with_eps:
+        assert np.all(got[:, :, [1, 3, 4]] == 0)                 # Q, S, T: no direction tensor
+
+
+@pytest.mark.parametrize('shape', R.TRAJ_SHAPES)
+@pytest.mark.parametrize('metric', ['dev', 'l1', 'l2'])
+def test_cost_matrix_matches_the_definition(shape, metric):
+    """Every pair i < j: 'dev' (closed form from the six moments) within 1e-12 * s, 'l1' / 'l2' (fp32 jump and difference, fp64 sums and
+    atomicAdd over the batch) within the fp32 bound of the jump's three operands.  One value per sample puts every point on the chord:
+    there the closed form cancels to the square root of its rounding noise and the degenerate bound 1e-7 * s holds instead."""
+    from diff_sampler_amd import gits_utils
+    traj, eps, t, traj_d, eps_d = _traj(shape)
+    cost = gits_utils._cost_matrix_round(traj_d, eps_d, t, metric)
+    ref, tol = R.pair_costs_ref(traj, eps, t, metric)
+    if metric == 'dev' and shape[2] == 1:
+        tol = tol * 1e5
+    n = shape[0]
+    iu = np.triu_indices(n, 1)
+    print(metric, shape, 'worst error / bound', float((np.abs(cost - ref)[iu] / tol[iu]).max()))
+    assert cost.shape == (n, n) and np.all(np.abs(cost - ref)[iu] <= tol[iu])
+    assert np.all(cost[np.tril_indices(n)] == 0)
+
+
+def test_dev_cost_on_a_trajectory_that_lies_on_its_chord():
+    from diff_sampler_amd import gits_utils
+    traj, eps, t, traj_d, eps_d = _traj('degenerate')
+    cost = gits_utils._cost_matrix_round(traj_d, eps_d, t, 'dev')
+    ref, tol = R.pair_costs_ref(traj, eps, t, 'dev')
+    iu = np.triu_indices(len(t), 1)
+    assert np.all(np.abs(cost - ref)[iu] <= 1e5 * tol[iu]), float((np.abs(cost - ref)[iu] / tol[iu]).max())       # 1e-7 * s
+
+
+@pytest.mark.parametrize('shape', R.TRAJ_SHAPES)
+def test_cal_deviation_matches_the_definition(shape):
+    """fp32 result of the fp64 closed form sqrt(R - P^2 / N): one fp32 rounding plus 1e-12 of its scale sqrt(R) = |c - x_j|."""
+    from diff_sampler_amd import gits_utils
+    traj, _, _, traj_d, _ = _traj(shape)
+    dev = gits_utils.cal_deviation(traj_d)
+    ref, Rj = R.deviation_ref(traj)
+    assert tuple(dev.shape) == ref.shape == (shape[1], shape[0] - 2) and dev.dtype == torch.float32 and dev.is_cuda
+    assert np.all(np.abs(dev.cpu().double().numpy() - ref) <= R.U * ref + 1e-12 * np.sqrt(Rj))
+
+
+@pytest.mark.parametrize('shape', R.TRAJ_SHAPES)
+@pytest.mark.parametrize('p_norm', [1, 2])
+def test_traj_pair_cost_accumulates_and_leaves_the_lower_triangle_zero(shape, p_norm):
+    """ds_traj_pair_cost adds into `cost`: a second call on the same buffer doubles it.  With one sample per pair that is exact (v + v);
+    with B samples the second round's B atomicAdds each round once in fp64, in any order, onto partial sums that stay below twice the
+    first result (every term is a norm, >= 0): |second - 2 first| <= B * 2^-52 * 2 first."""
+    import ctypes as C
+    from diff_sampler_amd import _lib
+    _, _, t, traj_d, eps_d = _traj(shape)
+    n, B, per = shape
+    cost = torch.zeros(n, n, dtype=torch.float64, device='cuda')
+    td = torch.tensor(t, dtype=torch.float32, device='cuda')
+    call = lambda: _lib.load().ds_traj_pair_cost(C.c_void_p(traj_d.data_ptr()), C.c_void_p(eps_d.data_ptr()), C.c_void_p(td.data_ptr()), n, B,
+                                                 per, p_norm, C.c_void_p(cost.data_ptr()), _lib.stream_ptr())
+    assert call() == 0
+    first = cost.cpu().numpy().copy()
+    assert call() == 0
+    second = cost.cpu().numpy()
+    assert np.all(first[np.tril_indices(n)] == 0) and np.all(second[np.tril_indices(n)] == 0)
+    assert np.all(first[np.triu_indices(n, 1)] > 0)
+    if B == 1:
+        assert np.array_equal(second, 2 * first)
+    else:
+        assert np.all(np.abs(second - 2 * first) <= B * 2.0 ** -52 * 2 * first)
