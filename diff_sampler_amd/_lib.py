@@ -117,6 +117,14 @@ class NormArgs(C.Structure):
                 ('stats0', vp), ('stats1', vp), ('tune_variant', C.c_int)]          # ABI 4: the pass that computes its own GroupNorm statistics
 
 
+class NormRouteInfo(C.Structure):
+    # ds_norm_route (ABI 7): the routing of ds_norm_act (kernel 0 = 8-byte, 1 / 2 / 3 = 16-byte on planes / self-finalising / on mean + rstd)
+    # and of ds_gn_stats (stats_chunks = P) for one ds_norm_args
+    _fields_ = [('act_rc', C.c_int), ('kernel', C.c_int), ('resampling', C.c_int), ('threads', C.c_int), ('lanes', C.c_int),
+                ('chunk', C.c_int), ('chunks', C.c_int), ('stats_rc', C.c_int), ('stats_threads', C.c_int), ('stats_lanes', C.c_int),
+                ('stats_chunks', C.c_int)]
+
+
 class AttnArgs(C.Structure):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
@@ -211,6 +219,7 @@ _SIGNATURES = {
     'ds_gemm_nt_batched': (C.c_int, [C.POINTER(GemmArgs), vp]),
     'ds_gn_stats': (C.c_int, [C.POINTER(NormArgs), vp]),
     'ds_norm_act': (C.c_int, [C.POINTER(NormArgs), vp]),
+    'ds_norm_route': (C.c_int, [C.POINTER(NormArgs), C.POINTER(NormRouteInfo)]),
     'ds_gn_finalize': (C.c_int, [C.POINTER(GnFinalizeArgs), vp]),
     'ds_softmax_rows': (C.c_int, [vp, vp, C.c_longlong, C.c_int, C.c_int, vp]),
     'ds_attention': (C.c_int, [C.POINTER(AttnArgs), vp]),
@@ -280,8 +289,8 @@ def load():
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype, fn.argtypes = res, args
-    if lib.ds_version() != 6:
-        raise DsError(f'{LIB_PATH} reports ABI version {lib.ds_version()}, this binding is written for 6: rebuild it (python diff_sampler_amd/build.py)')
+    if lib.ds_version() != 7:
+        raise DsError(f'{LIB_PATH} reports ABI version {lib.ds_version()}, this binding is written for 7: rebuild it (python diff_sampler_amd/build.py)')
     _lib = lib
     return lib
 

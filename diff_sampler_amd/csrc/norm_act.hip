@@ -164,7 +164,7 @@ __global__ void __launch_bounds__(1024) norm_act_kernel(const ds_norm_args a, in
         mu[j] = m;
         gn_coefs(r, gm, bt, sc1, sh, A[j], Bc[j]);
     }
-    const bool identity = !planes && !a.mean && !a.gamma && !a.scale;
+    const bool identity = !planes && !a.mean && !a.gamma && !a.beta && !a.scale;      // a beta given alone is applied (gn_affine with mu 0, A 1)
     typedef _Float16 h4 __attribute__((ext_vector_type(4)));
     auto to_h4 = [](const f32x4 v) { h4 o = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]}; return o; };   // RNE, like .to(float16)
     auto xf = [&](const f32x4 v) {
@@ -449,6 +449,13 @@ __global__ void __launch_bounds__(512) norm_act16_kernel(const ds_norm_args a, i
     }
 }
 
+// norm_act16_kernel<1 / 2> read gamma / beta / scale / shift as 16-byte vectors (norm_act_kernel reads them one float at a time)
+static bool norm16_affine_ok(const ds_norm_args* a) {
+    if ((a->gamma && !ds_aligned16(a->gamma)) || (a->beta && !ds_aligned16(a->beta))) return false;
+    if (a->scale && (!ds_aligned16(a->scale) || !ds_aligned16(a->shift) || (a->ss_ld & 3))) return false;
+    return true;
+}
+
 // Which ds_norm_act calls take norm_act16_kernel: fp16 rows in (every source present) and out, whole channel octets; 2x resampling included
 // (not in the self-finalising form).
 static bool norm16_ok(const ds_norm_args* a) {
@@ -459,8 +466,9 @@ static bool norm16_ok(const ds_norm_args* a) {
     if (!ds_aligned16(a->x0) || (a->c1 && !ds_aligned16(a->x1)) || !ds_aligned16(a->out)) return false;
     if (a->raw_out && ((a->raw_ld & 7) || !ds_aligned16(a->raw_out))) return false;
     if (a->coefs != nullptr || a->stats0 != nullptr) return true;
-    // mean / rstd form: statistics present and an affine map to apply (the identity / raw-resampler uses of ds_norm_act keep the generic kernel)
-    return a->mean != nullptr && a->groups > 0 && (a->c0 + a->c1) % a->groups == 0;
+    // mean / rstd form: statistics present and an affine map to apply (the identity / raw-resampler uses of ds_norm_act keep the generic kernel);
+    // affine operands the 16-byte loads cannot take keep the generic kernel too (the self-finalising form has no other kernel: DS_E_ALIGN there)
+    return a->mean != nullptr && a->groups > 0 && (a->c0 + a->c1) % a->groups == 0 && norm16_affine_ok(a);
 }
 
 // --------------------------------------------------------------------------------------------------------------
@@ -739,45 +747,58 @@ int norm_geometry(const ds_norm_args* a, int* CQ, int* PL) {
     return DS_OK;
 }
 
-}  // namespace
+// The launch geometry of ds_gn_stats / ds_norm_act: ONE host function each, used by the launch and by ds_norm_route.
+struct gn_stats_plan { int CQ, PL, threads, P; };
+struct norm_act_plan { int kernel, rs, CX, PL, threads, chunk, chunks; size_t lds; };      // CX: channel quads (kernel 0) or octets per pixel
 
-extern "C" int ds_gn_stats(const ds_norm_args* a, void* stream) {
-    (void)hipGetLastError();   // drop stale errors of unrelated runtime calls
-    if (!a || !a->x0 || !a->mean || !a->rstd) return DS_E_ARG;
+static bool norm_source_aligned(const void* p, bool half) { return (reinterpret_cast<uintptr_t>(p) & (half ? 7u : 15u)) == 0; }
+
+static int gn_stats_route(const ds_norm_args* a, gn_stats_plan* r) {
+    if (!a || !a->x0 || !a->mean || !a->rstd || (a->c1 && !a->x1)) return DS_E_ARG;
+    if (a->n <= 0 || a->h <= 0 || a->w <= 0 || a->c0 <= 0 || a->c1 < 0) return DS_E_SHAPE;
     if (a->groups <= 0 || a->groups > 64 || (a->c0 + a->c1) % a->groups) return DS_E_SHAPE;
     if ((a->ld0 & 3) || (a->c1 && (a->ld1 & 3))) return DS_E_ALIGN;
+    if (a->ld0 < a->c0 || (a->c1 && a->ld1 < a->c1)) return DS_E_SHAPE;
     if ((a->in_f16 & ~3) || ((a->in_f16 & 2) && !a->c1)) return DS_E_ARG;
-    int CQ, PL;
-    int rc = norm_geometry(a, &CQ, &PL);
+    if ((a->scale == nullptr) != (a->shift == nullptr)) return DS_E_ARG;
+    // the kernel reads whole channel quads: 16 bytes of an fp32 source, 8 of an fp16 one
+    if (!norm_source_aligned(a->x0, a->in_f16 & 1) || (a->c1 && !norm_source_aligned(a->x1, a->in_f16 & 2))) return DS_E_ALIGN;
+    if (a->partial && (reinterpret_cast<uintptr_t>(a->partial) & 7u)) return DS_E_ALIGN;
+    int rc = norm_geometry(a, &r->CQ, &r->PL);
     if (rc) return rc;
-    int threads = CQ * PL;
+    int threads = r->CQ * r->PL;
     threads = ((threads + 63) / 64) * 64;
     if (threads < 64) threads = 64;
+    r->threads = threads;
     // small batches: split every image over P pixel chunks so that the launch still covers the chip
     int P = 1;
     if (a->partial && a->n < 256) {
         P = (512 + a->n - 1) / a->n;
-        const int maxp = (a->h * a->w) / (PL * 4);          // at least 4 pixel iterations per thread
+        const int maxp = (a->h * a->w) / (r->PL * 4);          // at least 4 pixel iterations per thread
         if (P > maxp) P = maxp;
         if (P > DS_GN_MAX_CHUNKS) P = DS_GN_MAX_CHUNKS;
         if (P < 1) P = 1;
     }
-    hipLaunchKernelGGL(gn_stats_kernel, dim3(a->n, P), dim3(threads), 0, (hipStream_t)stream, *a, CQ, PL);
-    if (P > 1) hipLaunchKernelGGL(gn_finalize_kernel, dim3(a->n), dim3(256), 0, (hipStream_t)stream, *a, P);
-    DS_CHECK_LAUNCH();
+    r->P = P;
     return DS_OK;
 }
 
-extern "C" int ds_norm_act(const ds_norm_args* a, void* stream) {
-    (void)hipGetLastError();   // drop stale errors of unrelated runtime calls
-    if (!a || !a->x0 || !a->out) return DS_E_ARG;
+static int norm_act_route(const ds_norm_args* a, norm_act_plan* r) {
+    if (!a || !a->x0 || !a->out || (a->c1 && !a->x1)) return DS_E_ARG;
     if ((a->mean == nullptr) != (a->rstd == nullptr)) return DS_E_ARG;
     if ((a->scale == nullptr) != (a->shift == nullptr)) return DS_E_ARG;
+    if (a->n <= 0 || a->h <= 0 || a->w <= 0 || a->c0 <= 0 || a->c1 < 0) return DS_E_SHAPE;
     if ((a->ld0 & 3) || (a->c1 && (a->ld1 & 3)) || (a->out_ld & 3)) return DS_E_ALIGN;
+    if (a->ld0 < a->c0 || (a->c1 && a->ld1 < a->c1) || a->out_ld < a->c0 + a->c1) return DS_E_SHAPE;
     if ((a->in_f16 & ~3) || ((a->in_f16 & 1) && (reinterpret_cast<uintptr_t>(a->x0) & 7u)) || ((a->in_f16 & 2) && (!a->c1 || (reinterpret_cast<uintptr_t>(a->x1) & 7u)))) return DS_E_ARG;
-    if (a->raw_out && (!a->out_f16 || (a->raw_ld & 3) || (reinterpret_cast<uintptr_t>(a->raw_out) & 7u))) return DS_E_ARG;
+    if (a->raw_out && (!a->out_f16 || (a->raw_ld & 3) || a->raw_ld < a->c0 + a->c1 || (reinterpret_cast<uintptr_t>(a->raw_out) & 7u))) return DS_E_ARG;
     if (a->out_f16 && (reinterpret_cast<uintptr_t>(a->out) & 7u)) return DS_E_ALIGN;
+    // fp32 tensors move as 16-byte channel quads
+    if (!(a->in_f16 & 1) && !ds_aligned16(a->x0)) return DS_E_ALIGN;
+    if (a->c1 && !(a->in_f16 & 2) && !ds_aligned16(a->x1)) return DS_E_ALIGN;
+    if (!a->out_f16 && !ds_aligned16(a->out)) return DS_E_ALIGN;
     if (a->resample == DS_RESAMPLE_DOWN && ((a->h | a->w) & 1)) return DS_E_SHAPE;
+    if (a->mean && (a->groups <= 0 || (a->c0 + a->c1) % a->groups)) return DS_E_SHAPE;      // the kernels divide by groups
     int CQ, PL;
     int rc = norm_geometry(a, &CQ, &PL);
     if (rc) return rc;
@@ -786,10 +807,14 @@ extern "C" int ds_norm_act(const ds_norm_args* a, void* stream) {
     if (a->coefs && a->out_f16 && !ds_aligned16(a->coefs)) return DS_E_ALIGN;
     if (a->stats0) {
         // the pass computes its own statistics from the producers' column sums (norm_act16_kernel<FIN>): no ds_gn_finalize launch in front of it
+        if (a->tune_variant & 1) return DS_E_ARG;          // the 8-byte kernel knows nothing of stats0
         if (!norm16_ok(a) || a->coefs || (a->c1 && !a->stats1) || a->groups <= 0 || a->groups > 64 || (a->c0 + a->c1) % a->groups) return DS_E_SHAPE;
         if ((a->h * a->w) & 63 || (a->h * a->w) > 1024) return DS_E_SHAPE;
-        if ((a->scale == nullptr) != (a->shift == nullptr)) return DS_E_ARG;
+        if ((size_t)2 * (a->c0 + a->c1) * sizeof(double) + 128 * sizeof(float) > 65536) return DS_E_SHAPE;      // the channel sums live in LDS
+        if (!norm16_affine_ok(a)) return DS_E_ALIGN;
     }
+    r->rs = a->resample != DS_RESAMPLE_NONE;
+    r->lds = 0;
     if (norm16_ok(a) && !(a->tune_variant & 1)) {
         const bool fin = a->stats0 != nullptr;
         const int C = a->c0 + a->c1, CO = C / 8, HW = OH * OW;          // the OUTPUT pixels of an image are what the workgroups share out
@@ -812,14 +837,9 @@ extern "C" int ds_norm_act(const ds_norm_args* a, void* stream) {
         int chunk = (HW + chunks - 1) / chunks;
         chunk = ((chunk + PL16 - 1) / PL16) * PL16;
         chunks = (HW + chunk - 1) / chunk;
-        const size_t lds = fin ? (size_t)2 * C * sizeof(double) + 128 * sizeof(float) : 0;
-        const bool rsm = a->resample != DS_RESAMPLE_NONE;
-#define DS_N16(MODE_, RS_, LDS_) hipLaunchKernelGGL((norm_act16_kernel<MODE_, RS_>), dim3(chunks, a->n), dim3(T), LDS_, (hipStream_t)stream, *a, CO, PL16, chunk)
-        if (fin) DS_N16(1, false, lds);
-        else if (a->coefs) { if (rsm) DS_N16(0, true, 0); else DS_N16(0, false, 0); }
-        else { if (rsm) DS_N16(2, true, 0); else DS_N16(2, false, 0); }
-#undef DS_N16
-        DS_CHECK_LAUNCH();
+        r->kernel = fin ? 2 : (a->coefs ? 1 : 3);
+        r->CX = CO; r->PL = PL16; r->threads = T; r->chunk = chunk; r->chunks = chunks;
+        r->lds = fin ? (size_t)2 * C * sizeof(double) + 128 * sizeof(float) : 0;
         return DS_OK;
     }
     if (a->out_f16) {
@@ -848,7 +868,52 @@ extern "C" int ds_norm_act(const ds_norm_args* a, void* stream) {
     int chunk = (OH * OW + chunks - 1) / chunks;
     chunk = ((chunk + PL - 1) / PL) * PL;
     chunks = (OH * OW + chunk - 1) / chunk;
-    hipLaunchKernelGGL(norm_act_kernel, dim3(chunks, a->n), dim3(threads), 0, (hipStream_t)stream, *a, CQ, PL, chunk);
+    r->kernel = 0;
+    r->CX = CQ; r->PL = PL; r->threads = threads; r->chunk = chunk; r->chunks = chunks;
+    return DS_OK;
+}
+
+}  // namespace
+
+extern "C" int ds_norm_route(const ds_norm_args* a, ds_norm_route_info* info) {
+    if (!a || !info) return DS_E_ARG;
+    ds_norm_route_info o = {};
+    norm_act_plan r = {};
+    o.act_rc = norm_act_route(a, &r);
+    if (o.act_rc == DS_OK) { o.kernel = r.kernel; o.resampling = r.rs; o.threads = r.threads; o.lanes = r.PL; o.chunk = r.chunk; o.chunks = r.chunks; }
+    gn_stats_plan g = {};
+    o.stats_rc = gn_stats_route(a, &g);
+    if (o.stats_rc == DS_OK) { o.stats_threads = g.threads; o.stats_lanes = g.PL; o.stats_chunks = g.P; }
+    *info = o;
+    return DS_OK;
+}
+
+extern "C" int ds_gn_stats(const ds_norm_args* a, void* stream) {
+    (void)hipGetLastError();   // drop stale errors of unrelated runtime calls
+    gn_stats_plan r;
+    int rc = gn_stats_route(a, &r);
+    if (rc) return rc;
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(a->n, r.P), dim3(r.threads), 0, (hipStream_t)stream, *a, r.CQ, r.PL);
+    if (r.P > 1) hipLaunchKernelGGL(gn_finalize_kernel, dim3(a->n), dim3(256), 0, (hipStream_t)stream, *a, r.P);
+    DS_CHECK_LAUNCH();
+    return DS_OK;
+}
+
+extern "C" int ds_norm_act(const ds_norm_args* a, void* stream) {
+    (void)hipGetLastError();   // drop stale errors of unrelated runtime calls
+    norm_act_plan r;
+    int rc = norm_act_route(a, &r);
+    if (rc) return rc;
+    const dim3 grid(r.chunks, a->n), block(r.threads);
+    if (r.kernel == 0) {
+        hipLaunchKernelGGL(norm_act_kernel, grid, block, 0, (hipStream_t)stream, *a, r.CX, r.PL, r.chunk);
+    } else {
+#define DS_N16(MODE_, RS_) hipLaunchKernelGGL((norm_act16_kernel<MODE_, RS_>), grid, block, r.lds, (hipStream_t)stream, *a, r.CX, r.PL, r.chunk)
+        if (r.kernel == 2) DS_N16(1, false);
+        else if (r.kernel == 1) { if (r.rs) DS_N16(0, true); else DS_N16(0, false); }
+        else { if (r.rs) DS_N16(2, true); else DS_N16(2, false); }
+#undef DS_N16
+    }
     DS_CHECK_LAUNCH();
     return DS_OK;
 }

@@ -680,7 +680,7 @@ extern "C" int ds_build_experiments(void) {          // bit 0: always clear (no 
     return 0;
 #endif
 }
-extern "C" int ds_version(void) { return 6; }      // ABI 6: ds_conv_tune.invariant appended; ABI 5: ds_conv_route, ds_attention_variant; ABI 4: ds_norm_args.stats0 / stats1 / tune_variant appended; ABI 3: ds_conv_args.update appended (head-fused solver update), ds_build_experiments(); ABI 2: ds_conv_args.tune / ds_update_args.variant, ds_fid_moments
+extern "C" int ds_version(void) { return 7; }      // ABI 7: ds_norm_route, the launcher checks of ds_norm_act / ds_gn_stats; ABI 6: ds_conv_tune.invariant appended; ABI 5: ds_conv_route, ds_attention_variant; ABI 4: ds_norm_args.stats0 / stats1 / tune_variant appended; ABI 3: ds_conv_args.update appended (head-fused solver update), ds_build_experiments(); ABI 2: ds_conv_args.tune / ds_update_args.variant, ds_fid_moments
 
 extern "C" const char* ds_error_string(int code) {
     switch (code) {

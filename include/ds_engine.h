@@ -47,7 +47,8 @@ extern "C" {
 #define DS_RESAMPLE_DOWN 1  /* 2x2 box filter, stride 2  (networks_edm.py:77 with resample_filter [1,1]) */
 #define DS_RESAMPLE_UP 2    /* nearest neighbour x2      (networks_edm.py:75 with resample_filter [1,1]) */
 
-DS_API int ds_version(void);      /* ABI version; a host must check it before passing argument structs.  6: ds_conv_tune.invariant appended (the
+DS_API int ds_version(void);      /* ABI version; a host must check it before passing argument structs.  7: ds_norm_route added (the routing of ds_norm_act / ds_gn_stats
+                               * as a query); ds_norm_act / ds_gn_stats refuse what their kernels' vector accesses cannot take (see ds_norm_args).  6: ds_conv_tune.invariant appended (the
                                * batch-invariant route; struct size changed); the row kernel of 1x1 / Linear layers takes any row count.  5: ds_conv_route / ds_attention_variant added (the
                                * library's routing decisions as queries; ds_conv_kernel_id answers negative codes for rejected arguments).  4 (round 6): ds_norm_args.stats0 / stats1 / tune_variant and ds_attn_args.variant
                                * appended (the pass that computes its own GroupNorm statistics; struct size changed).  3 (round 5): ds_conv_args.update appended (the head-fused
@@ -354,7 +355,8 @@ typedef struct ds_norm_args {
      * pass (fp16 rows in and out, no resampling, channel counts multiples of 8) on images of 64 ... 1 024 pixels (h * w % 64 == 0);
      * anything else returns DS_E_SHAPE.  (The engines do NOT use this form by default: measured, it saves the ~6 us launch and pays about as
      * much in every workgroup's own reduction -- profiles/r6_norm_pass_ab.txt; plan.FOLD_FINALIZE / DS_FOLD_GN_FINALIZE=1 switches it on.)
-     * tune_variant (benchmarks / tests): bit 0 keeps the 8-byte kernel of rounds 3 - 5 where the 16-byte one would be taken; bits 1 / 2 change how
+     * tune_variant (benchmarks / tests): bit 0 keeps the 8-byte kernel of rounds 3 - 5 where the 16-byte one would be taken (with stats0: DS_E_ARG --
+     * that kernel does not finalise; ABI 7); bits 1 / 2 change how
      * many workgroups share an image in the self-finalising form (0: column sums <= rows / 1 per workgroup; bit 1: <= rows / 4; bit 2: no cap). */
     const float* stats0; const float* stats1;
     int tune_variant;
@@ -376,6 +378,30 @@ typedef struct ds_gn_finalize_args {
 } ds_gn_finalize_args;
 DS_API int ds_gn_finalize(const ds_gn_finalize_args* a, void* stream);
 DS_API int ds_norm_act(const ds_norm_args* a, void* stream);
+
+/* ABI 7.  What ds_gn_stats / ds_norm_act check before they launch (both kernels move whole channel quads or octets):
+ *   DS_E_ARG    a NULL x0 / out (mean / rstd for ds_gn_stats), c1 without x1, mean without rstd, scale without shift, in_f16 bits without their
+ *               source, an fp16 source or raw_out off 8 bytes (ds_norm_act), raw_out without out_f16, stats0 with tune_variant bit 0;
+ *   DS_E_SHAPE  n, h, w, c0 <= 0, c1 < 0, c0 or c0 + c1 not a multiple of 4 or above 4096, a leading dimension below its channel count,
+ *               groups <= 0 or not dividing c0 + c1 wherever statistics are written or read (mean given), groups > 64 (ds_gn_stats, stats0),
+ *               an odd h or w under DS_RESAMPLE_DOWN, a stats0 call outside the self-finalising form's domain;
+ *   DS_E_ALIGN  a leading dimension that is no multiple of 4, an fp32 x0 / x1 / out off 16 bytes, an fp16 out (and, in ds_gn_stats, an fp16
+ *               source) off 8 bytes, coefs as input off 16 bytes, and -- in the self-finalising form, whose only kernel reads them as 16-byte
+ *               vectors -- gamma / beta / scale / shift off 16 bytes or ss_ld % 4 != 0.  In the mean / rstd form the same operands send the call
+ *               to the 8-byte kernel instead, which reads them one float at a time.
+ * ds_norm_route: the routing of BOTH calls for one argument struct, without a GPU (host logic only; the launches use the same two functions).
+ * Returns DS_E_ARG for a NULL pointer, else DS_OK with `info` filled; a field group is meaningful when its return code is DS_OK. */
+typedef struct ds_norm_route_info {
+    int act_rc;          /* what ds_norm_act returns for these arguments before it launches (DS_OK or a negative DS_E_* code)              */
+    int kernel;          /* 0: the 8-byte kernel; 1 / 2 / 3: the 16-byte kernel on {mu, A, B} planes / self-finalising / on mean + rstd     */
+    int resampling;      /* 1: the launch resamples (the 16-byte kernel's resampling instantiation)                                       */
+    int threads, lanes;  /* threads per workgroup; pixel lanes (threads / channel quads or octets, at most the output pixels)              */
+    int chunk, chunks;   /* output pixels per workgroup (a multiple of lanes) and workgroups per image                                    */
+    int stats_rc;        /* the same for ds_gn_stats                                                                                       */
+    int stats_threads, stats_lanes;
+    int stats_chunks;    /* P: workgroups per image (> 1: the small-batch split through `partial`)                                         */
+} ds_norm_route_info;
+DS_API int ds_norm_route(const ds_norm_args* a, ds_norm_route_info* info);
 
 /* Row softmax, in place or out of place: y[r, :] = softmax(x[r, :cols]) (networks_edm.py:108). */
 DS_API int ds_softmax_rows(const float* x, float* y, long long rows, int cols, int ld, void* stream);

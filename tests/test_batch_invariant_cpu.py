@@ -114,7 +114,7 @@ def test_default_plans_carry_no_invariant_flag(config):
 
 def test_abi_6_and_the_row_kernel_at_any_row_count():
     lib = _lib.load()
-    assert lib.ds_version() == 6
+    assert lib.ds_version() == 7
     assert C.sizeof(_lib.ConvTune) == 7 * C.sizeof(C.c_int)
     from diff_sampler_amd.plan import Builder
     import torch

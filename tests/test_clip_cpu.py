@@ -103,7 +103,7 @@ def test_the_new_symbols_bind_and_answer_host_side_queries():
     lib = _lib.load()
     for name in ('ds_attention_causal', 'ds_attention_causal_supported', 'ds_token_embed', 'ds_quick_gelu'):
         assert name in _lib.EXPORTS and hasattr(lib, name)
-    assert lib.ds_version() == 6 and len(_lib.EXPORTS) == 60
+    assert lib.ds_version() == 7 and len(_lib.EXPORTS) == 61
     assert (_lib.DS_OP_TOKEN_EMBED, _lib.DS_OP_ATTENTION_CAUSAL, _lib.DS_OP_QUICK_GELU) == (14, 15, 16)
     ok = lib.ds_attention_causal_supported
     assert [ok(64, s) for s in (1, 31, 32, 33, 77, 128)] == [1] * 6

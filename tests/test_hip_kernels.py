@@ -135,7 +135,7 @@ def test_groupnorm_stats_and_apply(C_, G, HW):
     c0 = 64 if C_ > 64 else C_
     xn = _nhwc(x).cuda()
     x0, x1 = xn[:, :c0].contiguous(), (xn[:, c0:].contiguous() if C_ > c0 else None)
-    mean, rstd = torch.empty(B * G, device='cuda'), torch.empty(B * G, device='cuda')
+    mean, rstd = torch.full((B * G,), float('nan'), device='cuda'), torch.full((B * G,), float('nan'), device='cuda')
     ops.gn_stats(x0, c0, c0, B, HW, HW, G, 1e-5, mean, rstd, x1=x1, c1=C_ - c0, ld1=C_ - c0)
     # same statistics gathered by several workgroups per image (small-batch path), twice to exercise the counter reset
     from diff_sampler_amd._lib import DS_GN_MAX_CHUNKS
@@ -149,7 +149,7 @@ def test_groupnorm_stats_and_apply(C_, G, HW):
     ref = F.silu(F.group_norm(x, G, gamma, beta, 1e-5))
     for rs, refr in [(0, ref), (DS_RESAMPLE_DOWN, F.avg_pool2d(ref, 2)), (DS_RESAMPLE_UP, F.interpolate(ref, scale_factor=2, mode='nearest'))]:
         ho = refr.shape[-1]
-        out = torch.empty(B * ho * ho, C_, device='cuda')
+        out = torch.full((B * ho * ho, C_), float('nan'), device='cuda')
         ops.norm_act(x0, c0, c0, B, HW, HW, out, C_, x1=x1, c1=C_ - c0, ld1=C_ - c0, groups=G, eps=1e-5, mean=mean, rstd=rstd,
                      gamma=gamma.cuda(), beta=beta.cuda(), act=DS_ACT_SILU, resample=rs)
         torch.cuda.synchronize()

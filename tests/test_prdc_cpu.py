@@ -98,7 +98,7 @@ def test_the_engine_library_does_not_see_the_metrics_sources():
     from diff_sampler_amd import build, _lib
     assert build.metrics_sources() and all(os.sep + 'metrics' + os.sep in s for s in build.metrics_sources())
     assert not [f for f in build.sources() + build.headers() if 'metrics' in f]
-    assert len(_lib.EXPORTS) == 60 and not [e for e in _lib.EXPORTS if e.startswith('dsm_')]
+    assert len(_lib.EXPORTS) == 61 and not [e for e in _lib.EXPORTS if e.startswith('dsm_')]
 
 
 # ------------------------------------------------------------------------------------------------------------------ host path

@@ -182,4 +182,4 @@ def test_route_refuses(kw, code):
 def test_conv_args_struct_ends_with_the_new_field():
     fields = [f[0] for f in _lib.ConvArgs._fields_]
     assert fields[-2:] == ['update', 'in_up2']
-    assert _lib.load().ds_version() == 6
+    assert _lib.load().ds_version() == 7
