@@ -12,9 +12,18 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DS_METRICS_LIB_PATH') or os.path.join(_HERE, 'csrc', 'metrics', 'libdsmetrics.so')
 
 vp = C.c_void_p
-DSM_VERSION = 1
+DSM_VERSION = 2
 DSM_MAX_K = 8
 DS_OK, DS_E_ARG, DS_E_ALIGN, DS_E_SHAPE = 0, -1, -2, -3
+
+
+
+class DsmAttnArgs(C.Structure):
+    """dsm_attn_args: ds_attn_args' fields, its three trailing switches reserved (0)."""
+    _fields_ = [('q', vp), ('k', vp), ('v', vp), ('out', vp), ('ldq', C.c_int), ('ldk', C.c_int), ('ldv', C.c_int), ('ldo', C.c_int),
+                ('q_bs', C.c_longlong), ('k_bs', C.c_longlong), ('v_bs', C.c_longlong), ('o_bs', C.c_longlong), ('batch', C.c_int),
+                ('heads', C.c_int), ('sq', C.c_int), ('skv', C.c_int), ('d', C.c_int), ('scale', C.c_float), ('reserved', C.c_int * 3)]
+
 
 _SIGNATURES = {
     'dsm_version': (C.c_int, []),
@@ -24,6 +33,13 @@ _SIGNATURES = {
     'dsm_knn_radii_sq': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_longlong, vp]),
     'dsm_prdc_cross': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,
                                  C.c_longlong, vp]),
+    'dsm_attention': (C.c_int, [C.POINTER(DsmAttnArgs), vp]),
+    'dsm_attention_supported': (C.c_int, [C.c_int]),
+    'dsm_gelu_rows': (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_longlong, C.c_int, vp]),
+    'dsm_vit_patch_rows': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, C.c_int, vp]),
+    'dsm_vit_tokens': (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    'dsm_gather_rows': (C.c_int, [vp, C.c_int, C.c_longlong, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    'dsm_clip_score': (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -1,6 +1,8 @@
 /* libdsmetrics.so -- evaluation metrics on the fp64 matrix pipe of the MI355X (gfx950), a SECOND library next to libdsamd.so
  * (include/ds_engine.h): nothing here is part of the sampling engine's ABI, its build hashes or its tile tables.
  *
+ * Second part (DSM_VERSION 2, below the PRDC entry points): the device code of the CLIP score -- csrc/metrics/clip_score.hip.
+ *
  * Precision / recall / density / coverage and per-sample realism (sfd-main/prdc.py) on detector features.  Features are
  * [n][ld] row-major with ld >= dim, fp32 (widened exactly) or fp64 chosen by a flag per operand; all arithmetic is fp64.
  * Squared distances take the expanded form  d2(i, j) = max(|x_i|^2 + |y_j|^2 - 2 x_i . y_j, 0)  with the dot products on
@@ -18,7 +20,7 @@ extern "C" {
 #endif
 
 #define DSM_API __attribute__((visibility("default")))
-#define DSM_VERSION 1
+#define DSM_VERSION 2      /* 2: the CLIP-score entry points (clip_score.hip) added; nothing of version 1 changed */
 #define DSM_MAX_K 8          /* largest nearest_k the selection kernel is instantiated for (list of k + 1 values per row) */
 
 DSM_API int dsm_version(void);
@@ -49,6 +51,52 @@ DSM_API int dsm_prdc_cross(const void* real, int real_f64, int ld_r, int n_real,
                            int dim, const double* radii_sq_real, const double* radii_sq_fake, int* fake_count, int* real_hit,
                            double* real_min_sq, const unsigned char* realism_mask, double* realism_sq, void* workspace,
                            long long workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------------
+ * CLIP score (clip_score.py of the reference repositories): what the two CLIP towers need beyond libdsamd.so, fp32 throughout.
+ * These calls need no workspace.  DS_E_ARG: NULL pointer, non-positive count, a leading dimension smaller than the columns it carries;
+ * DS_E_ALIGN: pointer not 16-byte aligned / columns or leading dimension not a multiple of 4 where a call says so; DS_E_SHAPE: a geometry
+ * no kernel covers. */
+
+/* Bidirectional attention  out[b, i, h*d : (h+1)*d] = sum_j softmax_j(scale * q[b,i,h,:] . k[b,j,h,:]) v[b,j,h,:]  with the operand
+ * convention of ds_attn_args (include/ds_engine.h), field for field: token-major matrices [rows][ld] whose head h occupies columns
+ * h*d ... (h+1)*d - 1, image b at b * *_bs floats, so a packed q|k|v projection is consumed in place.  Head sizes:
+ * dsm_attention_supported(d) -- 88 (ViT-g-14) only; the head sizes ds_attention covers are the caller's to route there (DS_E_SHAPE here).
+ * sq, skv >= 1 of any length.  Keys at or beyond skv have weight exactly 0 and are never read; rows at or beyond sq and columns beyond
+ * heads * d of `out` are not written; a row's summation order depends on the row alone.  Pointers 16-byte aligned, ld* and *_bs
+ * multiples of 4 (DS_E_ALIGN), ld* >= heads * d and `reserved` zero (DS_E_ARG). */
+typedef struct dsm_attn_args {
+    const float* q; const float* k; const float* v; float* out;
+    int ldq, ldk, ldv, ldo;
+    long long q_bs, k_bs, v_bs, o_bs;
+    int batch, heads, sq, skv, d;
+    float scale;
+    int reserved[3];     /* where ds_attn_args carries out_f16 / in_f16 / variant: must be 0 */
+} dsm_attn_args;
+
+DSM_API int dsm_attention(const dsm_attn_args* a, void* stream);
+DSM_API int dsm_attention_supported(int d);
+
+/* y[r, :cols] = 0.5 x (1 + erf(x / sqrt 2)) -- the exact (erf) GELU; in place allowed; columns [cols, ld) untouched.  cols, ldx, ldy multiples of 4. */
+DSM_API int dsm_gelu_rows(const float* x, int ldx, float* y, int ldy, long long rows, int cols, void* stream);
+
+/* The A operand of a ViT patch projection: images [n][3][size][size] (uint8, or fp32 in [0, 1] with images_f32 = 1) ->
+ * out[n * (size / patch)^2][ld], row = (image, patch row, patch column), column = (channel, py, px) as patch_embedding.weight.reshape(width, -1);
+ * value (v / 255 - mean[c]) / std[c] (fp32 input: (v - mean[c]) / std[c]); columns [3 patch^2, ld) are written as zeros.  mean3 / std3:
+ * three floats each in HOST memory, read during the call.  DS_E_SHAPE: size not a multiple of patch. */
+DSM_API int dsm_vit_patch_rows(const void* images, int images_f32, int n, int size, int patch, const float* mean3, const float* std3, float* out,
+                               int ld, void* stream);
+
+/* out[b * tokens + 0] = cls + pos[0];  out[b * tokens + 1 + i] = patches[b * (tokens - 1) + i] + pos[1 + i]   (pos [tokens][width], dense). */
+DSM_API int dsm_vit_tokens(const float* patches, int ldp, const float* cls, const float* pos, float* out, int ldo, int n, int tokens, int width,
+                           void* stream);
+
+/* out[i, :cols] = x[row_index[i], :cols] for i < n; row_index: int32 on the device, values in [0, x_rows) (the caller checks; the kernel clamps). */
+DSM_API int dsm_gather_rows(const float* x, int ldx, long long x_rows, const int* row_index, float* out, int ldo, int n, int cols, void* stream);
+
+/* scores[i] = 100 <a_i, b_i> / (|a_i| |b_i|) in fp32 for i < n, then  *sum += scores[0] + ... + scores[n - 1]  in fp64 in a fixed order
+ * (no atomics: two runs give the same bits). */
+DSM_API int dsm_clip_score(const float* a, int lda, const float* b, int ldb, int n, int dim, float* scores, double* sum, void* stream);
 
 #ifdef __cplusplus
 }
