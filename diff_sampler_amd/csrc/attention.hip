@@ -289,6 +289,7 @@ extern "C" int ds_attention(const ds_attn_args* a, void* stream) {
     if (a && (a->out_f16 || a->in_f16)) return DS_E_ARG;          // fp16 tensors: ds_attention_f16 only
     if (!a || !a->q || !a->k || !a->v || !a->out) return DS_E_ARG;
     if (a->batch <= 0 || a->heads <= 0 || a->sq <= 0 || a->skv <= 0 || a->batch > 65535 || a->heads > 65535) return DS_E_ARG;
+    if (a->variant < 0 || a->variant > 2) return DS_E_ARG;        // as ds_attention_f16: 0 = the library's choice, 1 / 2 = a named split
     if ((a->ldq & 3) || (a->ldk & 3) || (a->ldv & 3) || (a->ldo & 3) || (a->q_bs & 3) || (a->k_bs & 3) || (a->v_bs & 3) || (a->o_bs & 3))
         return DS_E_ALIGN;
     if (!ds_aligned16(a->q) || !ds_aligned16(a->k) || !ds_aligned16(a->v) || !ds_aligned16(a->out)) return DS_E_ALIGN;

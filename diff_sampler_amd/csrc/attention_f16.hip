@@ -362,6 +362,8 @@ extern "C" int ds_attention_f16(const ds_attn_args* a, void* stream) {
     if ((a->ldq & 3) || (a->ldk & 3) || (a->ldv & 3) || (a->ldo & 3) || (a->q_bs & 3) || (a->k_bs & 3) || (a->v_bs & 3) || (a->o_bs & 3))
         return DS_E_ALIGN;
     if ((a->in_f16 & ~3) || a->variant < 0 || a->variant > 2) return DS_E_ARG;
+    // fp16 q: the scale multiplies the fp32 scores and the running maximum is taken as max(score) * scale -- the maximum only for scale > 0
+    if ((a->in_f16 & 1) && !(a->scale > 0.f && a->scale <= 3.402823466e38f)) return DS_E_ARG;
     if ((a->in_f16 & 1) && ((a->ldq & 7) || (a->q_bs & 7))) return DS_E_ALIGN;          // fp16 rows are read in 16-byte (q, k) / 8-byte (v) pieces
     if ((a->in_f16 & 2) && ((a->ldk & 7) || (a->k_bs & 7))) return DS_E_ALIGN;
     if (!ds_aligned16(a->q) || !ds_aligned16(a->k) || !ds_aligned16(a->v) || !ds_aligned16(a->out)) return DS_E_ALIGN;

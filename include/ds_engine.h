@@ -422,14 +422,17 @@ typedef struct ds_attn_args {
     int out_f16;     /* ds_attention_f16 only: `out` is an fp16 tensor (ldo / o_bs in halfs): the operand of the output projection in fp16 mode */
     int in_f16;      /* ds_attention_f16 only: bit 0: q is an fp16 tensor (ldq / q_bs in halfs, multiples of 8), bit 1: k and v are (ldk, k_bs
                         multiples of 8; ldv, v_bs of 4) -- the fp16 tensors the reference's qkv projection emits in its fp16 mode
-                        (networks_edm.py:171-173; attention.py:168-176 under autocast); `scale` then multiplies the fp32 scores */
+                        (networks_edm.py:171-173; attention.py:168-176 under autocast); `scale` then multiplies the fp32 scores.  With fp16 q the
+                        running maximum is max(score) * scale, which is the maximum only for a positive factor: bit 0 with a scale that is not
+                        finite and > 0 is DS_E_ARG (fp32 q folds the scale into q: either sign is served, as by ds_attention) */
     int variant;     /* ABI 4.  ds_attention_f16: 0 = the library's choice (the kernel with one 32-query block per wave,
                         rounds 2 - 6); 1 = the same, explicitly; 2 = accepted for compatibility and served by the same kernel (it once chose a kernel with
                         two query blocks per wave, measured 5 - 8 % slower and removed: docs/HISTORY.md; head sizes <= 64, else DS_E_SHAPE):
                         results do not depend on it.  ds_attention (fp32), head sizes that are multiples of 128: 0 = the library's choice -- the channel-split block
                         (32 queries, four waves x d / 4 channels) while the query-split grid has fewer than 1 024 waves, i.e. small batches of the
                         single 256-wide head; 1 = query split, 2 = channel split.  The two agree to fp32 rounding (the scores are summed in a
-                        different order), not bit for bit; other head sizes ignore the field */
+                        different order), not bit for bit; other head sizes run the query split whatever 0 / 1 / 2 says.  Both entry points answer
+                        DS_E_ARG for a value outside 0 .. 2 */
 } ds_attn_args;
 
 DS_API int ds_attention(const ds_attn_args* a, void* stream);
