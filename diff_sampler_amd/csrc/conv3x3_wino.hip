@@ -26,6 +26,21 @@
 // Who orders what: barrier A after the transform (Vs published, Hs dead), barrier C after the slab's MFMAs (Vs and the
 // weight buffer dead; `s_waitcnt vmcnt(0)` in front of it: the next slab's weights have landed); the weight DMA of slab s+1 and the halo
 // store of slab s+1 are issued between A and C.
+//
+// Between A and C: the halo store of slab s+1 (branch-free, see below), the 8 fragment reads of position group 0, then ONE basic block of 64
+// micro-slots -- an MFMA, then at most one memory instruction, pinned there by __builtin_amdgcn_sched_barrier(0); the wave is alone on its SIMD
+// (512 registers), so nothing else fills the 64 cycles of an MFMA:
+//     slots  0 ..  7   one LDS-DMA piece of the weights of slab s+1
+//     slots  8 .. 14   the halo loads (one per active slot) and the 3 coefficient loads of slab s+2: ~50 MFMAs ahead of the `vmcnt(0)` at C
+//     and the 8 fragment reads of position group g+1 in slots 8 .. 15 (20 .. 27, 32 .. 39) of group g.
+// The halo store's arithmetic stays in FRONT of the MFMAs: placed between them it cost more than it hid (profiles/wino_pipe_ab.txt).
+// Nothing in the block branches: what is uniform per launch (normalisation none / affine / affine + SiLU; 3 or 4 halo slots per thread) is
+// a template parameter, the source a0 | a1 is a scalar base plus a bit-select between two per-slot offsets, out-of-image pixels are loaded
+// from the nearest pixel of the same image and replaced by 0 AFTER the activation, slots beyond the halo store into one spare cell behind
+// Hs, and s+1 / s+2 are clamped to the last slab: the last slab issues a redundant DMA (into the buffer nobody reads), halo store (Hs is
+// dead) and loads, all landed at its barrier C (`vmcnt(0)`; a wave's LDS writes complete in order in front of its later ones).
+#include <type_traits>
+
 #include "igemm_common.h"
 
 namespace igemm {
@@ -41,19 +56,19 @@ constexpr int WINO_IMG = 16 * WINO_POS;           // floats per U / V image (819
 constexpr int WINO_NSH = 4;                       // halo float4 slots per thread: NP * 2 <= 1024
 constexpr int WINO_EPI_LD = 36;                   // epilogue staging row: 32 + 4 floats
 
-__device__ float g_zero_page_wino[64];            // zero-initialised
-
 // `s_waitcnt vmcnt(0)` as the BUILTIN (simm16: vmcnt 0, expcnt 7, lgkmcnt 15), not inline asm: the compiler's own wait-count pass sees it, so it
 // knows that the halo registers requested a slab ago are there and does not put a second vmcnt(0) -- which would also wait for the weight DMA
 // just issued -- in front of the halo store in the middle of the slab's MFMAs.
 #define DS_WINO_WAIT_VM0() do { __builtin_amdgcn_s_waitcnt(0x0F70); asm volatile("" ::: "memory"); } while (0)
 
-template <int VAR>
+// NORM: the consumer's normalisation on the way into Hs -- 0 none, 1 affine, 2 affine + SiLU (uniform per launch: p.norm, p.norm_act)
+// NSL:  halo float4 slots per thread that can hold a halo pixel, ceil(2 NP / 256): 3 for 16- and 32-column images, 4 for 64-column ones
+template <int VAR, int NORM, int NSL>
 __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Us = smem;                              // [2][16][2][64][4]
     float* Vs = smem + 2 * WINO_IMG;               // [16][2][64][4]
-    float* Hs = Vs + WINO_IMG;                     // [2][2][HP][WP / 2][4]
+    float* Hs = Vs + WINO_IMG;                     // [2][2][HP][WP / 2][4], and one spare 16-byte cell behind it
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -66,57 +81,74 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
     const int WPH = p.WP >> 1, Wt = p.W >> 1;
     const int Ctot = p.c0 + p.c1;
     const int nslabs = Ctot / WINO_K;
-    const float* zero = g_zero_page_wino;
+    constexpr bool kDma = !(VAR & WV_NO_DMA), kHalo = !(VAR & WV_NO_HALO);
+    constexpr int kNorm = (VAR & WV_NO_NORM) ? 0 : NORM;       // the arithmetic of the halo store
 
     // ---- halo slots of this thread: (halo pixel, channel quad), fixed for the whole K loop ------------------------------------------
+    // Element offsets inside the tile's image for either source (an out-of-image pixel: the nearest pixel of the image, its value is
+    // replaced by 0 in the store), the LDS cell (a slot beyond the halo: the spare cell) and whether the pixel is inside the image.
     const int kh_h = tid & 1;
-    int h_pix[WINO_NSH], h_lds[WINO_NSH];
+    unsigned h_off0[WINO_NSH], h_off1[WINO_NSH];
+    int h_lds[WINO_NSH];
+    bool h_ok[WINO_NSH];
 #pragma unroll
     for (int j = 0; j < WINO_NSH; ++j) {
         const int hp = (tid + j * 256) >> 1;
         const int hr = hp / p.WP, hc = hp - hr * p.WP;
         const int y = r0 + hr - 1, x = hc - 1;
         const bool in = hp < p.NP;
-        const bool ok = in && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
-        h_pix[j] = ok ? (img0 * p.H + y) * p.W + x : -1;
-        h_lds[j] = in ? (((kh_h * 2 + (hc & 1)) * p.HP + hr) * WPH + (hc >> 1)) * 4 : -1;
+        h_ok[j] = in && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
+        const int pix = min(max(y, 0), p.H - 1) * p.W + min(max(x, 0), p.W - 1);
+        h_off0[j] = (unsigned)(pix * p.lda0 + kh_h * 4);
+        h_off1[j] = (unsigned)(pix * p.lda1 + kh_h * 4);
+        h_lds[j] = in ? (((kh_h * 2 + (hc & 1)) * p.HP + hr) * WPH + (hc >> 1)) * 4 : p.NP * WINO_K;
     }
+    const float* a0i = p.a0 + (size_t)img0 * p.HW * p.lda0;
+    const float* a1i = p.a1 + (size_t)img0 * p.HW * p.lda1;
+    const float* cpi = p.norm + (size_t)img0 * 3 * Ctot + kh_h * 4;
     f32x4 hreg[WINO_NSH];
-    auto halo_load = [&](int s) {
+    float h_t[4 * WINO_NSH], h_u[4 * WINO_NSH];    // an element chain's affine value and its sigmoid on the way
+    f32x4 cmu = {0.f, 0.f, 0.f, 0.f}, cga = {1.f, 1.f, 1.f, 1.f}, cbe = {0.f, 0.f, 0.f, 0.f};
+    // source of slab s: scalar base, and an all-ones / all-zeros word that selects the per-slot offset without a branch (kept opaque)
+    const float* h_src = nullptr;
+    unsigned h_sel = 0;
+    auto halo_src = [&](int s) {
         const int c = s * WINO_K;
         const bool first = c < p.c0;
-        const float* src = first ? p.a0 + c + kh_h * 4 : p.a1 + (c - p.c0) + kh_h * 4;
-        const int ld = first ? p.lda0 : p.lda1;
-#pragma unroll
-        for (int j = 0; j < WINO_NSH; ++j) {
-            const float* ptr = h_pix[j] >= 0 ? src + (size_t)h_pix[j] * ld : zero;
-            hreg[j] = *reinterpret_cast<const f32x4*>(ptr);
+        h_src = first ? a0i + c : a1i + (c - p.c0);
+        h_sel = (unsigned)__builtin_amdgcn_readfirstlane(first ? -1 : 0);
+        asm volatile("" : "+s"(h_sel));
+    };
+    auto halo_load1 = [&](auto J) {
+        constexpr int j = decltype(J)::value;
+        if constexpr (j >= NSL) return;
+        const unsigned off = (h_off0[j] & h_sel) | (h_off1[j] & ~h_sel);
+        hreg[j] = *reinterpret_cast<const f32x4*>(h_src + off);
+    };
+    // planes {mu, A, B} of the tile's image, one per call
+    auto coef_load1 = [&](int s, auto I) {
+        constexpr int i = decltype(I)::value;
+        if constexpr (NORM != 0) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(cpi + (size_t)i * Ctot + s * WINO_K);
+            if constexpr (i == 0) cmu = v; else if constexpr (i == 1) cga = v; else cbe = v;
         }
     };
-    // the consumer's GroupNorm affine + SiLU, applied once per element while the halo is written (planes {mu, A, B} of the tile's image)
-    const bool norm_on = p.norm != nullptr;
-    f32x4 cmu = {0.f, 0.f, 0.f, 0.f}, cga = {1.f, 1.f, 1.f, 1.f}, cbe = {0.f, 0.f, 0.f, 0.f};
-    auto coef_load = [&](int s) {
-        const float* cp = norm_on ? p.norm + (size_t)img0 * 3 * Ctot + s * WINO_K + kh_h * 4 : zero;
-        const int st = norm_on ? Ctot : 0;
-        cmu = *reinterpret_cast<const f32x4*>(cp);
-        cga = *reinterpret_cast<const f32x4*>(cp + st);
-        cbe = *reinterpret_cast<const f32x4*>(cp + 2 * st);
-    };
-    auto halo_store = [&]() {
-        const bool do_norm = norm_on && !(VAR & WV_NO_NORM);
-        DS_RACE_SKEW(wave);
-#pragma unroll
-        for (int j = 0; j < WINO_NSH; ++j) {
-            f32x4 v = hreg[j];
-            if (do_norm && h_pix[j] >= 0) {
-                v = (v - cmu) * cga + cbe;
-                if (p.norm_act == DS_ACT_SILU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = ds_silu(v[e]);
-                }
-            }
-            if (h_lds[j] >= 0) *reinterpret_cast<f32x4*>(Hs + h_lds[j]) = v;
+    // stage ST of element chain C (slot C / 4, float C % 4) of the halo store: the consumer's GroupNorm affine + SiLU, applied once per
+    // element; zeros are written after the activation.  The affine is a subtraction and ONE fma, the SiLU is ds_silu's operations.
+    auto halo_chain = [&](auto C, auto ST) {
+        constexpr int c = decltype(C)::value, st = decltype(ST)::value, j = c >> 2, e = c & 3;
+        if constexpr (j >= NSL) return;
+        if constexpr (st == 0 && kNorm != 0) {
+            h_t[c] = __builtin_fmaf(hreg[j][e] - cmu[e], cga[e], cbe[e]);
+            if constexpr (kNorm == 2) h_u[c] = __expf(-h_t[c]);
+        }
+        if constexpr (st == 1 && kNorm == 2) h_u[c] = __builtin_amdgcn_rcpf(1.0f + h_u[c]);
+        if constexpr (st == 2) {
+            float v = hreg[j][e];
+            if constexpr (kNorm == 1) v = h_t[c];
+            if constexpr (kNorm == 2) v = h_t[c] * h_u[c];
+            hreg[j][e] = h_ok[j] ? v : 0.f;
+            if constexpr (e == 3) *reinterpret_cast<f32x4*>(Hs + h_lds[j]) = hreg[j];
         }
     };
 
@@ -151,17 +183,14 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
         }
     };
 
-    // ---- transformed weights of slab s -> buffer buf: 8 LDS-DMA instructions per wave, source already in the LDS image's order --------
-    auto u_dma = [&](int s, int buf) {
-        const float* src = p.b + ((size_t)nt * nslabs + s) * WINO_IMG + tid * 4;
-        DS_RACE_SKEW(wave);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            float* dst = Us + buf * WINO_IMG + (i * 256 + wave * 64) * 4;          // wave-uniform base; the DMA writes lane-linear
-            typedef const __attribute__((address_space(1))) void* gptr_t;
-            typedef __attribute__((address_space(3))) void* lptr_t;
-            __builtin_amdgcn_global_load_lds((gptr_t)(src + i * 1024), (lptr_t)(dst), 16, 0, 0);
-        }
+    // ---- transformed weights -> a buffer of Us: 8 LDS-DMA pieces per wave, source already in the LDS image's order -------------------------
+    const float* u_src = p.b + (size_t)nt * nslabs * WINO_IMG + tid * 4;
+    auto u_dma1 = [&](const float* src, float* ubuf, auto I) {                          // src: u_src + slab * WINO_IMG
+        constexpr int i = decltype(I)::value;
+        float* dst = ubuf + (i * 256 + wave * 64) * 4;                                  // wave-uniform base; the DMA writes lane-linear
+        typedef const __attribute__((address_space(1))) void* gptr_t;
+        typedef __attribute__((address_space(3))) void* lptr_t;
+        __builtin_amdgcn_global_load_lds((gptr_t)(src + i * 1024), (lptr_t)(dst), 16, 0, 0);
     };
 
     f32x16 acc[16];
@@ -171,48 +200,98 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
         for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
     const int a_off = ((lane >> 5) * 64 + wr * 32 + (lane & 31)) * 4;
     const int b_off = ((lane >> 5) * 64 + wc * 32 + (lane & 31)) * 4;
-    // positions [Q0, Q0 + 4): four independent accumulators per K step
-#define DS_WINO_MFMA4(Q0, ub)                                                                                               \
-    {                                                                                                                       \
-        f32x4 fa[4], fb[4];                                                                                                 \
-        _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                                     \
-            fa[q] = *reinterpret_cast<const f32x4*>(Vs + ((Q0) + q) * WINO_POS + a_off);                                    \
-            fb[q] = *reinterpret_cast<const f32x4*>((ub) + ((Q0) + q) * WINO_POS + b_off);                                  \
-        }                                                                                                                   \
-        _Pragma("unroll") for (int r = 0; r < 4; ++r)                                                                       \
-            _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                                   \
-                acc[(Q0) + q] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][r], fb[q][r], acc[(Q0) + q], 0, 0, 0);           \
-    }
 
-    // ---- prologue --------------------------------------------------------------------------------------------------------------------
-    halo_load(0);
-    coef_load(0);
-    u_dma(0, 0);
-    halo_store();
-    if (nslabs > 1) { halo_load(1); coef_load(1); }
+#define DS_WINO_I(n) std::integral_constant<int, (n)>{}
+#define DS_WINO_EACH4(F) F(0) F(1) F(2) F(3)
+#define DS_WINO_EACH16(F, b) F((b) + 0) F((b) + 1) F((b) + 2) F((b) + 3) F((b) + 4) F((b) + 5) F((b) + 6) F((b) + 7)                \
+                             F((b) + 8) F((b) + 9) F((b) + 10) F((b) + 11) F((b) + 12) F((b) + 13) F((b) + 14) F((b) + 15)
+
+    // ---- prologue: slab 0 staged, slab 1 requested -------------------------------------------------------------------------------------
+    halo_src(0);
+#define DS_WINO_F(j) halo_load1(DS_WINO_I(j));
+    DS_WINO_EACH4(DS_WINO_F)
+#undef DS_WINO_F
+    coef_load1(0, DS_WINO_I(0)); coef_load1(0, DS_WINO_I(1)); coef_load1(0, DS_WINO_I(2));
+    DS_RACE_SKEW(wave);
+#define DS_WINO_F(i) u_dma1(u_src, Us, DS_WINO_I(i)); u_dma1(u_src, Us, DS_WINO_I((i) + 4));
+    DS_WINO_EACH4(DS_WINO_F)
+#undef DS_WINO_F
+    DS_RACE_SKEW(wave);
+#define DS_WINO_F(c) halo_chain(DS_WINO_I(c), DS_WINO_I(0)); halo_chain(DS_WINO_I(c), DS_WINO_I(1)); halo_chain(DS_WINO_I(c), DS_WINO_I(2));
+    DS_WINO_EACH16(DS_WINO_F, 0)
+#undef DS_WINO_F
+    {
+        const int s1 = min(1, nslabs - 1);
+        halo_src(s1);
+#define DS_WINO_F(j) halo_load1(DS_WINO_I(j));
+        DS_WINO_EACH4(DS_WINO_F)
+#undef DS_WINO_F
+        coef_load1(s1, DS_WINO_I(0)); coef_load1(s1, DS_WINO_I(1)); coef_load1(s1, DS_WINO_I(2));
+    }
     DS_WINO_WAIT_VM0();
     __syncthreads();
 
-    for (int s = 0; s < nslabs; ++s) {
+    // ---- K loop ------------------------------------------------------------------------------------------------------------------------
+    // fragments of position group g (positions 4 g .. 4 g + 3) live in fa / fb[g & 1]; group g+1 is read in slots FR(g) .. FR(g) + 7 of
+    // group g (behind the DMA pieces in group 0)
+    f32x4 fa[2][4], fb[2][4];
+    int s = 0;
+    do {                                               // nslabs >= 1 (conv3x3_wino_applicable)
         const float* ub = Us + (s & 1) * WINO_IMG;
         transform();                                   // Hs -> Vs (Vs died at barrier C of the previous slab)
         __syncthreads();                               // A: Vs published, Hs dead
-        if (s + 1 < nslabs) {
-            if (!(VAR & WV_NO_DMA)) u_dma(s + 1, (s + 1) & 1);     // that buffer was last read by the MFMAs of slab s-1 (barrier C passed)
-            if (!(VAR & WV_NO_HALO)) {
-                halo_store();                          // slab s+1 (its loads were issued a slab ago, landed at barrier C)
-                // the loads of slab s+2 go out BEFORE the slab's MFMAs: they must have landed at barrier C (vmcnt(0) for the weight DMA)
-                if (s + 2 < nslabs) { halo_load(s + 2); coef_load(s + 2); }
-            }
+        const int s1 = min(s + 1, nslabs - 1), s2 = min(s + 2, nslabs - 1);
+        const float* un = u_src + (size_t)s1 * WINO_IMG;
+        float* ubn = Us + ((s + 1) & 1) * WINO_IMG;    // last read by the MFMAs of slab s-1 (barrier C passed)
+        if constexpr (kHalo) halo_src(s2);
+        auto frag_read = [&](auto G, auto I) {
+            constexpr int g = decltype(G)::value, i = decltype(I)::value;
+            if constexpr (i < 4) fa[g & 1][i] = *reinterpret_cast<const f32x4*>(Vs + (g * 4 + i) * WINO_POS + a_off);
+            else fb[g & 1][i - 4] = *reinterpret_cast<const f32x4*>(ub + (g * 4 + i - 4) * WINO_POS + b_off);
+        };
+        if constexpr (kHalo) {                         // halo of slab s+1 (its loads were issued a slab ago, landed at barrier C)
+            DS_RACE_SKEW(wave);
+#define DS_WINO_F(c) halo_chain(DS_WINO_I(c), DS_WINO_I(0)); halo_chain(DS_WINO_I(c), DS_WINO_I(1)); halo_chain(DS_WINO_I(c), DS_WINO_I(2));
+            DS_WINO_EACH16(DS_WINO_F, 0)
+#undef DS_WINO_F
         }
-        DS_WINO_MFMA4(0, ub)
-        DS_WINO_MFMA4(4, ub)
-        DS_WINO_MFMA4(8, ub)
-        DS_WINO_MFMA4(12, ub)
+        auto fill = [&](auto K) {
+            constexpr int k = decltype(K)::value, g = k >> 4;
+            if constexpr (k < 8) {                     // weights of slab s+1
+                if constexpr (kDma) {
+                    if constexpr (k == 0) DS_RACE_SKEW(wave);
+                    u_dma1(un, ubn, DS_WINO_I(k));
+                }
+            } else if constexpr (k < 12) {             // loads of slab s+2: they land at barrier C (vmcnt(0) for the weight DMA)
+                if constexpr (kHalo) halo_load1(DS_WINO_I(k - 8));
+            } else if constexpr (k < 15) {
+                if constexpr (kHalo) coef_load1(s2, DS_WINO_I(k - 12));
+            }
+            constexpr int fr = g == 0 ? 8 : g == 1 ? 20 : g == 2 ? 32 : 64;
+            if constexpr (k >= fr && k < fr + 8) frag_read(DS_WINO_I(g + 1), DS_WINO_I(k - fr));
+        };
+        // micro-slot k: K step r = (k >> 2) & 3 of position 4 (k >> 4) + (k & 3), then its filler, pinned
+#define DS_WINO_STEP(k)                                                                                                                \
+        acc[((k) >> 4) * 4 + ((k) & 3)] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[((k) >> 4) & 1][(k) & 3][((k) >> 2) & 3],            \
+                                                                               fb[((k) >> 4) & 1][(k) & 3][((k) >> 2) & 3],            \
+                                                                               acc[((k) >> 4) * 4 + ((k) & 3)], 0, 0, 0);              \
+        fill(DS_WINO_I(k));                                                                                                            \
+        __builtin_amdgcn_sched_barrier(0);
+#define DS_WINO_F(i) frag_read(DS_WINO_I(0), DS_WINO_I(i)); frag_read(DS_WINO_I(0), DS_WINO_I((i) + 4));
+        DS_WINO_EACH4(DS_WINO_F)
+#undef DS_WINO_F
+        __builtin_amdgcn_sched_barrier(0);
+        DS_WINO_EACH16(DS_WINO_STEP, 0)
+        DS_WINO_EACH16(DS_WINO_STEP, 16)
+        DS_WINO_EACH16(DS_WINO_STEP, 32)
+        DS_WINO_EACH16(DS_WINO_STEP, 48)
+#undef DS_WINO_STEP
         DS_WINO_WAIT_VM0();                            // the LDS-DMA of slab s+1 has landed (hipcc waits only in front of LDS reads it can tie to it)
         __syncthreads();                               // C: Vs, Us[s & 1] dead; Hs and Us[(s+1) & 1] published
-    }
-#undef DS_WINO_MFMA4
+    } while (++s < nslabs);
+#undef DS_WINO_EACH16
+#undef DS_WINO_EACH4
+#undef DS_WINO_I
 
     if constexpr ((VAR & WV_NO_EPI) != 0) {
 #pragma unroll
@@ -353,13 +432,24 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
     }
 }
 
-template <int VAR>
-int launch_wino(KParams& p, hipStream_t stream) {
-    const int smem = (3 * WINO_IMG + p.NP * WINO_K) * (int)sizeof(float);
-    DS_ENSURE_DYN_LDS((&conv3x3_wino_kernel<VAR>), 128 * 1024);
-    hipLaunchKernelGGL((conv3x3_wino_kernel<VAR>), dim3(grid_1d(p.mtiles, p.ntiles)), dim3(256), smem, stream, p);
+template <int VAR, int NORM, int NSL>
+int launch_wino_ns(KParams& p, hipStream_t stream) {
+    const int smem = (3 * WINO_IMG + p.NP * WINO_K + 4) * (int)sizeof(float);        // + the spare halo cell
+    DS_ENSURE_DYN_LDS((&conv3x3_wino_kernel<VAR, NORM, NSL>), 128 * 1024);
+    hipLaunchKernelGGL((conv3x3_wino_kernel<VAR, NORM, NSL>), dim3(grid_1d(p.mtiles, p.ntiles)), dim3(256), smem, stream, p);
     DS_CHECK_LAUNCH();
     return DS_OK;
+}
+
+template <int VAR, int NORM>
+int launch_wino_n(KParams& p, hipStream_t stream) {
+    return p.NP * 2 <= 3 * 256 ? launch_wino_ns<VAR, NORM, 3>(p, stream) : launch_wino_ns<VAR, NORM, 4>(p, stream);
+}
+
+template <int VAR>
+int launch_wino(KParams& p, hipStream_t stream) {
+    if (!p.norm) return launch_wino_n<VAR, 0>(p, stream);
+    return p.norm_act == DS_ACT_SILU ? launch_wino_n<VAR, 2>(p, stream) : launch_wino_n<VAR, 1>(p, stream);
 }
 
 }  // namespace
@@ -372,7 +462,7 @@ bool conv3x3_wino_applicable(const KParams& p) {
     if ((p.N & 63) || (p.c0 % WINO_K) || (p.c1 % WINO_K) || !p.vec_ok || p.out_planar || p.out_f16 || p.res_f16 || p.rowbias) return false;
     if (p.act != DS_ACT_NONE && p.act != DS_ACT_SILU) return false;
     const int np = (256 / p.W + 2) * (p.W + 2);
-    if (np * 2 > WINO_NSH * 256 || (3 * WINO_IMG + np * WINO_K) * (int)sizeof(float) > 128 * 1024) return false;
+    if (np * 2 > WINO_NSH * 256 || (3 * WINO_IMG + np * WINO_K + 4) * (int)sizeof(float) > 128 * 1024) return false;
     return p.M % 256 == 0;
 }
 

@@ -461,7 +461,8 @@ static int route_conv(const ds_conv_args* a, KParams& p, ConvRoute& r) {
     r.splits = 1;
     if (!a || !a->x0 || !a->wgt || !a->out) return DS_E_ARG;
     if (a->taps != 1 && a->taps != 9) return DS_E_ARG;
-    if (a->c0 <= 0 || a->c0 % 32 || a->c1 < 0 || a->c1 % 32) return DS_E_SHAPE;
+    const int cq = a->wino ? 8 : 32;          // channel quantum of a source: the K slab of the kernels (conv3x3_wino.hip: 8 channels)
+    if (a->c0 <= 0 || a->c0 % cq || a->c1 < 0 || a->c1 % cq) return DS_E_SHAPE;
     if (a->c1 && !a->x1) return DS_E_ARG;
     if (a->out_f16 && (!a->in_f16 || (a->cout & 63) || (a->out_ld & 7) || !ds_aligned16(a->out))) return DS_E_ARG;   // fp16 output rows: the fp16-activation kernels only
     if (a->res_f16 && (!a->in_f16 || !a->res || (a->res_ld & 7) || !ds_aligned16(a->res))) return DS_E_ARG;          // fp16 residual rows: the same kernels
