@@ -40,6 +40,7 @@ _SIGNATURES = {
     'dsm_vit_tokens': (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     'dsm_gather_rows': (C.c_int, [vp, C.c_int, C.c_longlong, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     'dsm_clip_score': (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    'dsm_resize_crop_u8': (C.c_int, [vp, C.c_longlong, C.c_int] + [C.c_int] * 8 + [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -61,7 +62,11 @@ def load():
                              f'The device metrics have no CPU fallback.')
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in _SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError if the symbol is not exported
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise DsMetricsError(f'{LIB_PATH} does not export {name}: it was built from older sources, rebuild it '
+                                 f'(python diff_sampler_amd/build.py)') from None
         fn.restype, fn.argtypes = res, args
     if lib.dsm_version() != DSM_VERSION:
         raise DsMetricsError(f'{LIB_PATH} reports ABI version {lib.dsm_version()}, this binding is written for {DSM_VERSION}: rebuild it '

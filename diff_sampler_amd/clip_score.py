@@ -132,10 +132,36 @@ class ClipScorer:
         _metrics_lib.check(self.mlib.dsm_clip_score(vp(fi), E, vp(ft), E, B, E, vp(scores), vp(self.total), _lib.stream_ptr()), 'dsm_clip_score')
         return scores
 
+    def score_raw(self, images_hwc_u8, tokens_or_prompts) -> torch.Tensor:
+        """``score`` of undecorated images: uint8 [B, H, W, 3] of one size, host or device; the resize of the shorter side to the tower's
+        input size and the centre crop run on the device (clip_preprocess: the bits of ``preprocess``)."""
+        from .clip_preprocess import resize_center_crop
+        return self.score(resize_center_crop(images_hwc_u8, self.spec.image_size, self.device), tokens_or_prompts)
+
+
+def resize_mixed(arrays, size, device) -> torch.Tensor:
+    """Decoded RGB arrays [h, w, 3] of any mix of sizes -> device uint8 [B, 3, size, size] in the arrays' order: one device resize per
+    size (groups in order of first appearance)."""
+    from . import clip_preprocess
+    groups = {}
+    for j, a in enumerate(arrays):
+        groups.setdefault(tuple(a.shape[:2]), []).append(j)
+    out = None
+    for members in groups.values():
+        x = clip_preprocess.resize_center_crop(torch.from_numpy(np.stack([arrays[j] for j in members])), size, device)
+        if len(groups) == 1:
+            return x
+        if out is None:
+            out = torch.empty(len(arrays), *x.shape[1:], dtype=x.dtype, device=x.device)
+        out[torch.as_tensor(members, device=x.device)] = x
+    return out
+
 
 # ---- command line -------------------------------------------------------------------------------------------------------------------------
-def calc_clip_score(scorer, image_path, captions, num_expected=None, seed=0, max_batch_size=64, log=print):
-    """clip_score.py:43-94 with the model injected: list, shard over ranks, score, SUM-all-reduce, average.  Returns (average, images)."""
+def calc_clip_score(scorer, image_path, captions, num_expected=None, seed=0, max_batch_size=64, log=print, device_resize=False):
+    """clip_score.py:43-94 with the model injected: list, shard over ranks, score, SUM-all-reduce, average.  Returns (average, images).
+    `device_resize`: PIL only decodes (``convert('RGB')``); the images of a batch are grouped by size and every group is resized,
+    cropped on the device; the batch is scored in one call as on the host path, so the scores and the total have the host path's bits."""
     import torch.distributed as dist
     ds = ImageFolder(image_path, max_size=num_expected, random_seed=seed)
     if num_expected is not None and len(ds) < num_expected:
@@ -153,7 +179,11 @@ def calc_clip_score(scorer, image_path, captions, num_expected=None, seed=0, max
             dist.barrier()
         if len(idx) == 0:
             continue
-        imgs = torch.stack([preprocess(PIL.Image.open(os.path.join(ds.path, ds.names[int(ds.idx[i])])), size) for i in idx.tolist()])
+        files = [os.path.join(ds.path, ds.names[int(ds.idx[i])]) for i in idx.tolist()]
+        if device_resize:
+            imgs = resize_mixed([np.asarray(PIL.Image.open(f).convert('RGB'), dtype=np.uint8) for f in files], size, scorer.device)
+        else:
+            imgs = torch.stack([preprocess(PIL.Image.open(f), size) for f in files])
         scorer.score(imgs, [texts[i] for i in idx.tolist()])
     total = scorer.total.clone()
     if world > 1:
@@ -181,7 +211,8 @@ if click is not None:
     @click.option('--batch', help='Maximum batch size', metavar='INT', type=click.IntRange(min=1), default=64, show_default=True)
     @click.option('--desc', help='A description string (written to clip_score.txt in place of the folder names)', metavar='str', type=str)
     @click.option('--device', type=str, default=None)
-    def calc(image_path, prompt_path, model_path, tokenizer_path, num_expected, seed, batch, desc, device):
+    @click.option('--device_resize', help='Resize and crop on the device (the same bits as the host transform)', is_flag=True)
+    def calc(image_path, prompt_path, model_path, tokenizer_path, num_expected, seed, batch, desc, device, device_resize):
         """Calculate the CLIP score of a folder of images against their captions."""
         from .clip_tokenizer import ClipTokenizer
         dist, rank = _init_dist()
@@ -192,7 +223,8 @@ if click is not None:
         log(f'Loading the CLIP model from "{model_path}"...')
         with torch.no_grad():
             scorer = ClipScorer.from_checkpoint(model_path, ClipTokenizer(tokenizer_path), device)
-            avg, n = calc_clip_score(scorer, image_path, captions, num_expected=num_expected, seed=seed, max_batch_size=batch, log=log)
+            avg, n = calc_clip_score(scorer, image_path, captions, num_expected=num_expected, seed=seed, max_batch_size=batch, log=log,
+                                     device_resize=device_resize)
         if rank == 0:
             print(f'CLIP score: {avg}')
             with open('clip_score.txt', 'a') as fh:

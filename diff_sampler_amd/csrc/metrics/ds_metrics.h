@@ -1,7 +1,8 @@
 /* libdsmetrics.so -- evaluation metrics on the fp64 matrix pipe of the MI355X (gfx950), a SECOND library next to libdsamd.so
  * (include/ds_engine.h): nothing here is part of the sampling engine's ABI, its build hashes or its tile tables.
  *
- * Second part (DSM_VERSION 2, below the PRDC entry points): the device code of the CLIP score -- csrc/metrics/clip_score.hip.
+ * Second part (DSM_VERSION 2, below the PRDC entry points): the device code of the CLIP score -- csrc/metrics/clip_score.hip, and the
+ * resize and crop in front of it -- csrc/metrics/image_prep.hip (added without a version step: nothing existing changed).
  *
  * Precision / recall / density / coverage and per-sample realism (sfd-main/prdc.py) on detector features.  Features are
  * [n][ld] row-major with ld >= dim, fp32 (widened exactly) or fp64 chosen by a flag per operand; all arithmetic is fp64.
@@ -97,6 +98,24 @@ DSM_API int dsm_gather_rows(const float* x, int ldx, long long x_rows, const int
 /* scores[i] = 100 <a_i, b_i> / (|a_i| |b_i|) in fp32 for i < n, then  *sum += scores[0] + ... + scores[n - 1]  in fp64 in a fixed order
  * (no atomics: two runs give the same bits). */
 DSM_API int dsm_clip_score(const float* a, int lda, const float* b, int ldb, int n, int dim, float* scores, double* sum, void* stream);
+
+/* The resize and centre crop of the CLIP transform, bit for bit Pillow's 8-bit bicubic resampler (csrc/metrics/image_prep.hip; tables:
+ * clip_preprocess.resample_coeffs).  src: n images of h x w interleaved RGB bytes, row r of image i at src + i * image_stride + r * pitch;
+ * out: [n][3][size][size] bytes, the window of `size` rows from `top` and `size` columns from `left` of the image resized to nh x nw.
+ * Horizontal pass first, then vertical, each  clamp((2^21 + sum_k pixel[first + k] * weight[k]) >> 22, 0, 255)  in int32 with a uint8
+ * intermediate; a pass whose size does not change (nw == w, nh == h) is skipped and its table pointers are not read (they may be NULL).
+ * hbounds [nw][2] = (first tap, taps), hcoeffs [nw][hksize] for the columns, vbounds [nh][2], vcoeffs [nh][vksize] for the rows: int32
+ * on the device, weights in (-2^23, 2^23) (the kernel multiplies 24-bit operands); a table that contradicts the geometry yields wrong
+ * pixels, never an access outside src.
+ * DS_E_ARG: NULL src / out / table of a pass that runs, a non-positive size or count, negative image_stride, pitch < 3 w, a window outside
+ * nh x nw, a ksize below 2 ceil(2 max(in / out, 1)) + 1;  DS_E_ALIGN: out not 16-byte aligned, a table not 4-byte aligned (src may
+ * have any alignment: rows are read 16, 4 or 1 bytes at a time as src, pitch and image_stride allow);  DS_E_SHAPE: a side above 32768,
+ * more than 2^31 - 1 workgroups, or a geometry beyond the kernel's LDS: four rows of the source columns the window's taps reach must fit
+ * 24 KB (w <= 2048 for a full-width window) and the source rows one output row needs, times 3 (size rounded up to 4) bytes, 40 KB --
+ * any source up to 2048 x 2048 down to size 224 (and to 288 x 288 at size 32) is inside. */
+DSM_API int dsm_resize_crop_u8(const void* src, long long image_stride, int pitch, int n, int h, int w, int nh, int nw, int top, int left,
+                               int size, const int* hbounds, const int* hcoeffs, int hksize, const int* vbounds, const int* vcoeffs,
+                               int vksize, void* out, void* stream);
 
 #ifdef __cplusplus
 }
