@@ -60,6 +60,7 @@ constexpr int WINO_EPI_LD = 36;                   // epilogue staging row: 32 + 
 // knows that the halo registers requested a slab ago are there and does not put a second vmcnt(0) -- which would also wait for the weight DMA
 // just issued -- in front of the halo store in the middle of the slab's MFMAs.
 #define DS_WINO_WAIT_VM0() do { __builtin_amdgcn_s_waitcnt(0x0F70); asm volatile("" ::: "memory"); } while (0)
+#define DS_WINO_WAIT_VM(n) do { __builtin_amdgcn_s_waitcnt(0x0F70 | (n)); asm volatile("" ::: "memory"); } while (0)      // vmcnt(n), n < 16
 
 // NORM: the consumer's normalisation on the way into Hs -- 0 none, 1 affine, 2 affine + SiLU (uniform per launch: p.norm, p.norm_act)
 // NSL:  halo float4 slots per thread that can hold a halo pixel, ceil(2 NP / 256): 3 for 16- and 32-column images, 4 for 64-column ones
@@ -289,9 +290,6 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
         DS_WINO_WAIT_VM0();                            // the LDS-DMA of slab s+1 has landed (hipcc waits only in front of LDS reads it can tie to it)
         __syncthreads();                               // C: Vs, Us[s & 1] dead; Hs and Us[(s+1) & 1] published
     } while (++s < nslabs);
-#undef DS_WINO_EACH16
-#undef DS_WINO_EACH4
-#undef DS_WINO_I
 
     if constexpr ((VAR & WV_NO_EPI) != 0) {
 #pragma unroll
@@ -311,9 +309,26 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
     }
 
     // ---- appended 1x1 slabs (the fused skip projection; e0 | e1, 32 raw channels per slab): four plain MFMA groups on the post-transform
-    // accumulators, one per patch pixel.  The slab's 256 pixels x 32 channels go global -> registers -> Vs as [patch pixel][8-channel group]
-    // [kh][tile][4], the untransformed weights (behind the U images in `wgt`, already in LDS order [group][kh][row][4]) by LDS-DMA into the
-    // two U buffers.  Barriers: E1 after the store (Vs and the weights of this slab published), E2 after the slab's MFMAs (both dead).
+    // accumulators, one per patch pixel.  The slab's 256 pixels x 32 channels go global -> registers -> a V buffer as [patch pixel][8-channel
+    // group][kh][tile][4], the untransformed weights (behind the U images in `wgt`, already in LDS order [group][kh][row][4]) by LDS-DMA into
+    // a weight buffer.  Every LDS buffer of the K loop died at its last barrier C (its clamped redundant DMA landed at the `vmcnt(0)` in
+    // front of it, and the redundant halo store went to Hs, which this loop does not touch), so both are doubled inside the three images:
+    //     W[b] = smem + b * 2048 (8 KB each, the first half of Us[0]),   V[0] = Vs,   V[1] = Us[1]
+    // ONE barrier per slab.  Between barrier es-1 and barrier es, one basic block of 64 micro-slots in the K loop's style (an MFMA, then at
+    // most one memory instruction, pinned): the MFMAs of slab es on V[es & 1] and W[es & 1], in the order group, K step r, patch pixel, and
+    //     slots  0 ..  1   the two LDS-DMA pieces of the weights of slab es+1 -> W[(es+1) & 1]   (last read by slab es-1)
+    //     slots  2 ..  6   (24 .. 28, 36 .. 40 of groups 1, 2) the five fragment reads of group g+1
+    //     slots  7 .. 14   the eight ds_write_b128 of the pixels of slab es+1, registers -> V[(es+1) & 1]   (last read by slab es-1; the
+    //                      registers were requested a slab ago and landed at the `vmcnt(0)` in front of barrier es-1)
+    //     slots 15 .. 22   the eight global loads of slab es+2 into the registers just stored: ~40 MFMAs ahead of the `vmcnt(0)`
+    // es+1 / es+2 are clamped to the last slab, as in the K loop: the last slab issues a redundant DMA and store into the buffers nobody
+    // reads and redundant loads, all landed at its barrier, behind which the epilogue reuses smem from offset 0.  No VALU between the
+    // MFMAs but the address adds of the stores and loads: the source e0 | e1 (scalar base, row step, per-thread offset) is selected in front.
+    // The V buffers are swizzled: tile t of chunk c = 2 group + kh (the 8 lanes of a ds_write_b128 lane group hold the 8 chunks of ONE
+    // pixel, i.e. one t) lives in row t ^ c of its 64-row block.  Unswizzled, the 8 cells of a lane group are 1 KB apart -- one bank, 8 LDS
+    // cycles per group, 64 instead of 8 per store, and the four waves' stores kept the LDS busy for half of the slab's MFMA time; swizzled
+    // they are 8 consecutive 16-byte cells.  The fragment read of (group, kh) reads row (its row) ^ c: still one contiguous 512-byte block
+    // per 32 lanes, permuted inside aligned groups of 8 rows.
     const int nextra = (p.ec0 + p.ec1) / 32;
     if (nextra > 0) {
         const float* wsk = p.b + (size_t)p.ntiles * nslabs * WINO_IMG + (size_t)nt * nextra * 2048 + tid * 4;
@@ -324,51 +339,108 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
             const int lp = (tid >> 3) + 32 * j;        // pixel of the tile
             const int yl = lp / p.W, x = lp - yl * p.W;
             const int ph = (yl & 1) * 2 + (x & 1), t = (yl >> 1) * Wt + (x >> 1);
-            e_lds[j] = (((ph * 4 + (e_chunk >> 1)) * 2 + (e_chunk & 1)) * 64 + t) * 4;
+            e_lds[j] = (((ph * 4 + (e_chunk >> 1)) * 2 + (e_chunk & 1)) * 64 + (t ^ e_chunk)) * 4;
         }
-        f32x4 ereg[8];
-        auto e_load = [&](int es) {
+        int ea_off[4];                                 // a_off of group g, swizzled: row ^ (2 g + kh)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) ea_off[g] = ((lane >> 5) * 64 + ((wr * 32 + (lane & 31)) ^ (2 * g + (lane >> 5)))) * 4;
+        // pixel (tid >> 3) + 32 j of the tile, channels 4 e_chunk .. + 3: element offset of j = 0 for either source; j steps 32 rows
+        const unsigned e_t0 = (unsigned)((tid >> 3) * p.elda0 + e_chunk * 4), e_t1 = (unsigned)((tid >> 3) * p.elda1 + e_chunk * 4);
+        const float* e_src = nullptr;
+        unsigned e_off = 0;
+        int e_step = 0;
+        auto e_sel = [&](int es) {
             const int c = es * 32;
             const bool first = c < p.ec0;
-            const float* src = (first ? p.e0 + c : p.e1 + (c - p.ec0)) + e_chunk * 4;
             const int ld = first ? p.elda0 : p.elda1;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) ereg[j] = *reinterpret_cast<const f32x4*>(src + (size_t)(m0 + (tid >> 3) + 32 * j) * ld);
+            e_src = (first ? p.e0 + c : p.e1 + (c - p.ec0)) + (size_t)m0 * ld;
+            e_step = 32 * ld;
+            e_off = first ? e_t0 : e_t1;
         };
-        auto w_dma = [&](int es, int buf) {
+        auto e_load1 = [&](f32x4* dst, auto J) {
+            constexpr int j = decltype(J)::value;
+            dst[j] = *reinterpret_cast<const f32x4*>(e_src + (size_t)(j * e_step) + e_off);
+        };
+        auto w_dma1 = [&](int es, float* wbuf, auto I) {
+            constexpr int i = decltype(I)::value;
+            float* dst = wbuf + (i * 256 + wave * 64) * 4;
+            typedef const __attribute__((address_space(1))) void* gptr_t;
+            typedef __attribute__((address_space(3))) void* lptr_t;
+            __builtin_amdgcn_global_load_lds((gptr_t)(wsk + (size_t)es * 2048 + i * 1024), (lptr_t)(dst), 16, 0, 0);
+        };
+#define DS_WINO_EACH8(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7)
+
+        // prologue: weights and pixels of slab 0 staged, pixels of slab 1 requested behind them
+        f32x4 ereg[8];
+        {
+            f32x4 ereg0[8];
+            DS_RACE_SKEW(wave);
+            w_dma1(0, smem, DS_WINO_I(0)); w_dma1(0, smem, DS_WINO_I(1));
+            e_sel(0);
+#define DS_WINO_F(j) e_load1(ereg0, DS_WINO_I(j));
+            DS_WINO_EACH8(DS_WINO_F)
+#undef DS_WINO_F
+            e_sel(min(1, nextra - 1));
+#define DS_WINO_F(j) e_load1(ereg, DS_WINO_I(j));
+            DS_WINO_EACH8(DS_WINO_F)
+#undef DS_WINO_F
+            DS_WINO_WAIT_VM(8);                        // all but the eight loads of slab 1
             DS_RACE_SKEW(wave);
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                float* dst = Us + buf * WINO_IMG + (i * 256 + wave * 64) * 4;
-                typedef const __attribute__((address_space(1))) void* gptr_t;
-                typedef __attribute__((address_space(3))) void* lptr_t;
-                __builtin_amdgcn_global_load_lds((gptr_t)(wsk + (size_t)es * 2048 + i * 1024), (lptr_t)(dst), 16, 0, 0);
-            }
-        };
-        e_load(0);
-        w_dma(0, 0);
-        for (int es = 0; es < nextra; ++es) {
-            DS_RACE_SKEW(wave);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4*>(Vs + e_lds[j]) = ereg[j];
-            DS_WINO_WAIT_VM0();
-            __syncthreads();                           // E1
-            if (es + 1 < nextra) { e_load(es + 1); w_dma(es + 1, (es + 1) & 1); }
-            const float* wb = Us + (es & 1) * WINO_IMG;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 fa[4];
-                const f32x4 fb = *reinterpret_cast<const f32x4*>(wb + g * WINO_POS + b_off);
-#pragma unroll
-                for (int ph = 0; ph < 4; ++ph) fa[ph] = *reinterpret_cast<const f32x4*>(Vs + (ph * 4 + g) * WINO_POS + a_off);
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int ph = 0; ph < 4; ++ph) Y[ph] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[ph][r], fb[r], Y[ph], 0, 0, 0);
-            }
-            __syncthreads();                           // E2
+            for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4*>(Vs + e_lds[j]) = ereg0[j];
         }
+        __syncthreads();
+
+        f32x4 ga[2][4], gb[2];                         // fragments of group g: the four patch pixels' pixels and the weights
+        int es = 0;
+        do {
+            const float* vb = smem + (2 - (es & 1)) * WINO_IMG;
+            float* vn = smem + (1 + (es & 1)) * WINO_IMG;
+            const float* wb = smem + (es & 1) * 2048;
+            float* wn = smem + ((es + 1) & 1) * 2048;
+            const int es1 = min(es + 1, nextra - 1);
+            e_sel(min(es + 2, nextra - 1));
+            auto frag_read = [&](auto G, auto I) {
+                constexpr int g = decltype(G)::value, i = decltype(I)::value;
+                if constexpr (i < 4) ga[g & 1][i] = *reinterpret_cast<const f32x4*>(vb + (i * 4 + g) * WINO_POS + ea_off[g]);
+                else gb[g & 1] = *reinterpret_cast<const f32x4*>(wb + g * WINO_POS + b_off);
+            };
+            auto fill = [&](auto K) {
+                constexpr int k = decltype(K)::value, g = k >> 4;
+                if constexpr (k < 2) {                 // weights of slab es+1
+                    if constexpr (k == 0) DS_RACE_SKEW(wave);
+                    w_dma1(es1, wn, DS_WINO_I(k));
+                } else if constexpr (k >= 7 && k < 15) {   // pixels of slab es+1
+                    if constexpr (k == 7) DS_RACE_SKEW(wave);
+                    *reinterpret_cast<f32x4*>(vn + e_lds[k - 7]) = ereg[k - 7];
+                } else if constexpr (k >= 15 && k < 23) {  // loads of slab es+2
+                    e_load1(ereg, DS_WINO_I(k - 15));
+                }
+                constexpr int fr = g == 0 ? 2 : g == 1 ? 24 : g == 2 ? 36 : 64;
+                if constexpr (k >= fr && k < fr + 5) frag_read(DS_WINO_I(g + 1), DS_WINO_I(k - fr));
+            };
+            // micro-slot k: K step r = (k >> 2) & 3 of group k >> 4 into patch pixel k & 3, then its filler, pinned
+#define DS_WINO_STEP(k)                                                                                                                \
+            Y[(k) & 3] = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[((k) >> 4) & 1][(k) & 3][((k) >> 2) & 3], gb[((k) >> 4) & 1][((k) >> 2) & 3], \
+                                                              Y[(k) & 3], 0, 0, 0);                                                    \
+            fill(DS_WINO_I(k));                                                                                                        \
+            __builtin_amdgcn_sched_barrier(0);
+            frag_read(DS_WINO_I(0), DS_WINO_I(0)); frag_read(DS_WINO_I(0), DS_WINO_I(4)); frag_read(DS_WINO_I(0), DS_WINO_I(1));
+            frag_read(DS_WINO_I(0), DS_WINO_I(2)); frag_read(DS_WINO_I(0), DS_WINO_I(3));
+            __builtin_amdgcn_sched_barrier(0);
+            DS_WINO_EACH16(DS_WINO_STEP, 0)
+            DS_WINO_EACH16(DS_WINO_STEP, 16)
+            DS_WINO_EACH16(DS_WINO_STEP, 32)
+            DS_WINO_EACH16(DS_WINO_STEP, 48)
+#undef DS_WINO_STEP
+            DS_WINO_WAIT_VM0();                        // the weights of slab es+1 and the pixels of slab es+2 have landed
+            __syncthreads();                           // V[es & 1], W[es & 1] dead; V[(es+1) & 1], W[(es+1) & 1] published
+        } while (++es < nextra);
+#undef DS_WINO_EACH8
     }
+#undef DS_WINO_EACH16
+#undef DS_WINO_EACH4
+#undef DS_WINO_I
 
     // ---- the fused epilogue, one patch pixel (a, b) at a time ----------------------------------------------------------------------------
     float* stage = smem + wave * 32 * WINO_EPI_LD;     // wave-private rows; every LDS buffer died at the last barrier C
