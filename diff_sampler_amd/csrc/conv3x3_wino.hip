@@ -13,7 +13,8 @@
 //               consumer's GroupNorm affine + SiLU applied on the way (norm_coefs; out-of-image pixels are written as zeros AFTER the
 //               activation), is transformed to V = B^T d B in LDS `Vs` (16 positions x 64 tiles x 8 channels), and the transformed weights
 //               U of the workgroup's 64 columns (ops.pack_conv_weight_wino, already in the LDS image's order) stream global -> LDS by
-//               LDS-DMA into a double buffer `Us`.  16 positions x 4 K steps of v_mfma_f32_32x32x2_f32 per wave and slab.
+//               LDS-DMA into `Us`.  16 positions x 4 K steps of v_mfma_f32_32x32x2_f32 per wave and slab.  Us, Vs and Hs are double
+//               buffers: 4 x 32 KiB + 2 x (NP x 32 + 16) bytes, at most 156 448 bytes of LDS.
 //   LDS image = [position][channel quad kh = 0 / 1][row 0..63][4 floats] for U and V alike: an MFMA fragment read is one ds_read_b128 per
 //               lane at (kh = lane >> 5, row = lane & 31), 512 contiguous bytes per 32 lanes -- conflict-free, and the K index of step r is
 //               channel 4 kh + r on both operands.  Hs is split into planes [kh][column parity][row][column / 2][4] so that the tiles of a
@@ -23,22 +24,36 @@
 //               GroupNorm column sums of 64-pixel blocks (a wave's 32 tiles x one patch row = 64 pixels; an image's HW / 64 blocks stay
 //               contiguous, which is all ds_gn_finalize assumes).
 //
-// Who orders what: barrier A after the transform (Vs published, Hs dead), barrier C after the slab's MFMAs (Vs and the
-// weight buffer dead; `s_waitcnt vmcnt(0)` in front of it: the next slab's weights have landed); the weight DMA of slab s+1 and the halo
-// store of slab s+1 are issued between A and C.
+// Who orders what: ONE barrier per slab.  Us, Vs and Hs are all doubled; between barrier s-1 and barrier s a wave
+//     reads   Vs[s & 1], Us[s & 1]      the MFMAs of slab s
+//     reads   Hs[(s+1) & 1]             the transform of slab s+1 (published at barrier s-1)
+//     writes  Vs[(s+1) & 1]             the same; last read by the MFMAs of slab s-1 (barrier s-1 passed)
+//     writes  Hs[s & 1]                 the halo store of slab s+2, from registers; last read by the transform of slab s, which ran in
+//                                       front of barrier s-1
+//     writes  Us[(s+1) & 1]             the weight DMA of slab s+1; last read by the MFMAs of slab s-1
+//     loads                             the halo and the coefficients of slab s+3 into the registers the halo store has just consumed
+// and `s_waitcnt vmcnt(0)` stands in front of the barrier (the DMA and the loads have landed).  The prologue stages halo 0 and 1 (requested
+// together) and transform 0 and requests halo 2: two barriers.  s+1 / s+2 / s+3 are clamped to the last slab: the last slab issues a
+// redundant transform, halo store and DMA into the buffers nobody reads and redundant loads, all landed at ITS barrier (`vmcnt(0)`; a
+// wave's LDS writes complete in order in front of its later ones).  BEHIND THE LAST BARRIER EVERY K-LOOP BUFFER IS DEAD: the skip-slab loop
+// and the epilogue staging reuse the LDS from offset 0 on that ground alone.
 //
-// Between A and C: the halo store of slab s+1 (branch-free, see below), the 8 fragment reads of position group 0, then ONE basic block of 64
-// micro-slots -- an MFMA, then at most one memory instruction, pinned there by __builtin_amdgcn_sched_barrier(0); the wave is alone on its SIMD
-// (512 registers), so nothing else fills the 64 cycles of an MFMA:
+// Between two barriers, in program order: the 16 LDS reads of the transform, the halo store with its arithmetic, the transform's adds and
+// writes, the 8 fragment reads of position group 0, then ONE basic block of 64 micro-slots -- an MFMA, then at most one memory
+// instruction, pinned there by __builtin_amdgcn_sched_barrier(0); the wave is alone on its SIMD (512 registers):
 //     slots  0 ..  7   one LDS-DMA piece of the weights of slab s+1
-//     slots  8 .. 14   the halo loads (one per active slot) and the 3 coefficient loads of slab s+2: ~50 MFMAs ahead of the `vmcnt(0)` at C
+//     slots  8 .. 14   the halo loads (one per active slot) and the 3 coefficient loads of slab s+3: ~50 MFMAs ahead of the `vmcnt(0)`
 //     and the 8 fragment reads of position group g+1 in slots 8 .. 15 (20 .. 27, 32 .. 39) of group g.
-// The halo store's arithmetic stays in FRONT of the MFMAs: placed between them it cost more than it hid (profiles/wino_pipe_ab.txt).
+// What stands between the fp32 MFMAs is MEMORY instructions only.  Vector arithmetic beside v_mfma_f32_32x32x2_f32 is not hidden by it
+// (profiles/wino_kloop_ab.txt: the transform costs the same in front of the block as spread over its slots, one packed add per slot is
+// slower than both, and taking the 64-bit address adds of a slab's 14 or 15 global loads and DMA pieces out of the block gained 4-6 % per
+// layer).  So the halo store's arithmetic and the transform's adds stay in FRONT of the block, and the global loads and the DMA between
+// the MFMAs take a SCALAR base and a 32-bit lane offset (the `global_load ... v, s[..]` form; the offsets are kept in bytes and opaque,
+// so that the compiler does not widen them outside the loop).
 // Nothing in the block branches: what is uniform per launch (normalisation none / affine / affine + SiLU; 3 or 4 halo slots per thread) is
 // a template parameter, the source a0 | a1 is a scalar base plus a bit-select between two per-slot offsets, out-of-image pixels are loaded
-// from the nearest pixel of the same image and replaced by 0 AFTER the activation, slots beyond the halo store into one spare cell behind
-// Hs, and s+1 / s+2 are clamped to the last slab: the last slab issues a redundant DMA (into the buffer nobody reads), halo store (Hs is
-// dead) and loads, all landed at its barrier C (`vmcnt(0)`; a wave's LDS writes complete in order in front of its later ones).
+// from the nearest pixel of the same image and replaced by 0 AFTER the activation, and slots beyond the halo store into the spare cell
+// behind their Hs buffer.
 #include <type_traits>
 
 #include "igemm_common.h"
@@ -68,8 +83,8 @@ template <int VAR, int NORM, int NSL>
 __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Us = smem;                              // [2][16][2][64][4]
-    float* Vs = smem + 2 * WINO_IMG;               // [16][2][64][4]
-    float* Hs = Vs + WINO_IMG;                     // [2][2][HP][WP / 2][4], and one spare 16-byte cell behind it
+    float* Vs = smem + 2 * WINO_IMG;               // [2][16][2][64][4]
+    float* Hs = smem + 4 * WINO_IMG;               // [2] x { [2][2][HP][WP / 2][4], and one spare 16-byte cell behind it }
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -100,16 +115,22 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
         const bool in = hp < p.NP;
         h_ok[j] = in && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
         const int pix = min(max(y, 0), p.H - 1) * p.W + min(max(x, 0), p.W - 1);
-        h_off0[j] = (unsigned)(pix * p.lda0 + kh_h * 4);
-        h_off1[j] = (unsigned)(pix * p.lda1 + kh_h * 4);
+        h_off0[j] = (unsigned)(pix * p.lda0 + kh_h * 4) * 4u;       // BYTES: a load's address is the scalar base plus this 32-bit offset,
+        h_off1[j] = (unsigned)(pix * p.lda1 + kh_h * 4) * 4u;       // with no 64-bit vector arithmetic between the MFMAs
         h_lds[j] = in ? (((kh_h * 2 + (hc & 1)) * p.HP + hr) * WPH + (hc >> 1)) * 4 : p.NP * WINO_K;
     }
     const float* a0i = p.a0 + (size_t)img0 * p.HW * p.lda0;
     const float* a1i = p.a1 + (size_t)img0 * p.HW * p.lda1;
-    const float* cpi = p.norm + (size_t)img0 * 3 * Ctot + kh_h * 4;
-    f32x4 hreg[WINO_NSH];
+    const float* cpi = p.norm + (size_t)img0 * 3 * Ctot;       // scalar; the lane's channel quad is the byte offset c_lane
+    unsigned c_lane = (unsigned)(kh_h * 16);
+    const int h_buf = p.NP * WINO_K + 4;           // floats per buffer of Hs, its spare cell included
+    // a slab's halo on its way: the raw pixels of this thread's slots and the slab's coefficient planes {mu, A, B}
+    struct HaloRegs {
+        f32x4 h[WINO_NSH];
+        f32x4 mu = {0.f, 0.f, 0.f, 0.f}, ga = {1.f, 1.f, 1.f, 1.f}, be = {0.f, 0.f, 0.f, 0.f};
+    };
+    HaloRegs hreg;
     float h_t[4 * WINO_NSH], h_u[4 * WINO_NSH];    // an element chain's affine value and its sigmoid on the way
-    f32x4 cmu = {0.f, 0.f, 0.f, 0.f}, cga = {1.f, 1.f, 1.f, 1.f}, cbe = {0.f, 0.f, 0.f, 0.f};
     // source of slab s: scalar base, and an all-ones / all-zeros word that selects the per-slot offset without a branch (kept opaque)
     const float* h_src = nullptr;
     unsigned h_sel = 0;
@@ -120,78 +141,78 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
         h_sel = (unsigned)__builtin_amdgcn_readfirstlane(first ? -1 : 0);
         asm volatile("" : "+s"(h_sel));
     };
-    auto halo_load1 = [&](auto J) {
+    auto halo_load1 = [&](HaloRegs& R, auto J) {
         constexpr int j = decltype(J)::value;
         if constexpr (j >= NSL) return;
         const unsigned off = (h_off0[j] & h_sel) | (h_off1[j] & ~h_sel);
-        hreg[j] = *reinterpret_cast<const f32x4*>(h_src + off);
+        R.h[j] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(h_src) + off);
     };
     // planes {mu, A, B} of the tile's image, one per call
-    auto coef_load1 = [&](int s, auto I) {
+    auto coef_load1 = [&](HaloRegs& R, int s, auto I) {
         constexpr int i = decltype(I)::value;
         if constexpr (NORM != 0) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(cpi + (size_t)i * Ctot + s * WINO_K);
-            if constexpr (i == 0) cmu = v; else if constexpr (i == 1) cga = v; else cbe = v;
+            const char* cs = reinterpret_cast<const char*>(cpi + (size_t)i * Ctot + s * WINO_K);
+            asm volatile("" : "+v"(c_lane));  // kept 32 bits wide up to the load, which takes the scalar `cs` as its base
+            const f32x4 v = *reinterpret_cast<const f32x4*>(cs + c_lane);
+            if constexpr (i == 0) R.mu = v; else if constexpr (i == 1) R.ga = v; else R.be = v;
         }
     };
-    // stage ST of element chain C (slot C / 4, float C % 4) of the halo store: the consumer's GroupNorm affine + SiLU, applied once per
-    // element; zeros are written after the activation.  The affine is a subtraction and ONE fma, the SiLU is ds_silu's operations.
-    auto halo_chain = [&](auto C, auto ST) {
+    // stage ST of element chain C (slot C / 4, float C % 4) of the halo store into the buffer `hs` of Hs: the consumer's GroupNorm affine
+    // + SiLU, applied once per element; zeros are written after the activation.  The affine is a subtraction and ONE fma, the SiLU is
+    // ds_silu's operations.
+    auto halo_chain = [&](HaloRegs& R, float* hs, auto C, auto ST) {
         constexpr int c = decltype(C)::value, st = decltype(ST)::value, j = c >> 2, e = c & 3;
         if constexpr (j >= NSL) return;
         if constexpr (st == 0 && kNorm != 0) {
-            h_t[c] = __builtin_fmaf(hreg[j][e] - cmu[e], cga[e], cbe[e]);
+            h_t[c] = __builtin_fmaf(R.h[j][e] - R.mu[e], R.ga[e], R.be[e]);
             if constexpr (kNorm == 2) h_u[c] = __expf(-h_t[c]);
         }
         if constexpr (st == 1 && kNorm == 2) h_u[c] = __builtin_amdgcn_rcpf(1.0f + h_u[c]);
         if constexpr (st == 2) {
-            float v = hreg[j][e];
+            float v = R.h[j][e];
             if constexpr (kNorm == 1) v = h_t[c];
             if constexpr (kNorm == 2) v = h_t[c] * h_u[c];
-            hreg[j][e] = h_ok[j] ? v : 0.f;
-            if constexpr (e == 3) *reinterpret_cast<f32x4*>(Hs + h_lds[j]) = hreg[j];
+            R.h[j][e] = h_ok[j] ? v : 0.f;
+            if constexpr (e == 3) *reinterpret_cast<f32x4*>(hs + h_lds[j]) = R.h[j];
         }
     };
 
     // ---- input transform: this thread owns (tile t_t, channels 4 kh_t + 2 cpl .. + 1) -----------------------------------------------
     const int t_t = (tid >> 1) & 63, cpl = tid & 1, kh_t = tid >> 7;
     const int t_ty = t_t / Wt, t_tx = t_t - t_ty * Wt;
-    const float* h_rd = Hs + ((kh_t * 2 * p.HP + 2 * t_ty) * WPH + t_tx) * 4 + cpl * 2;
+    const int h_rd = ((kh_t * 2 * p.HP + 2 * t_ty) * WPH + t_tx) * 4 + cpl * 2;         // float offsets inside a buffer of Hs / of Vs
     const int h_par = p.HP * WPH * 4;              // odd-column plane
-    float* v_wr = Vs + (kh_t * 64 + t_t) * 4 + cpl * 2;
-    auto transform = [&]() {
-        f32x2 d[4][4];
+    const int v_wr = (kh_t * 64 + t_t) * 4 + cpl * 2;
+    // in 16 + 16 pieces, so that the K loop can place them: piece I of the reads is d[I / 4][I % 4], piece I of the writes is position I
+    // (row I / 4 of B^T d, made when its first position is written: it needs rows 0,2 / 1,2 / 1,2 / 1,3 of d)
+    f32x2 t_d[4][4], t_r[4];
+    auto tr_read1 = [&](const float* hs, auto I) {
+        constexpr int i = decltype(I)::value >> 2, j = decltype(I)::value & 3;
+        t_d[i][j] = *reinterpret_cast<const f32x2*>(hs + h_rd + (j & 1) * h_par + i * WPH * 4 + (j >> 1) * 4);
+    };
+    auto tr_write1 = [&](float* vs, auto I) {
+        constexpr int i = decltype(I)::value >> 2, j = decltype(I)::value & 3;
+        if constexpr (j == 0) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                d[i][j] = *reinterpret_cast<const f32x2*>(h_rd + (j & 1) * h_par + i * WPH * 4 + (j >> 1) * 4);
-        DS_RACE_SKEW(wave);
-        f32x2 t[4][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {              // B^T d
-            t[0][j] = d[0][j] - d[2][j];
-            t[1][j] = d[1][j] + d[2][j];
-            t[2][j] = d[2][j] - d[1][j];
-            t[3][j] = d[1][j] - d[3][j];
+            for (int q = 0; q < 4; ++q)            // B^T d
+                t_r[q] = i == 0 ? t_d[0][q] - t_d[2][q] : i == 1 ? t_d[1][q] + t_d[2][q] : i == 2 ? t_d[2][q] - t_d[1][q] : t_d[1][q] - t_d[3][q];
         }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {              // (B^T d) B
-            *reinterpret_cast<f32x2*>(v_wr + (i * 4 + 0) * WINO_POS) = t[i][0] - t[i][2];
-            *reinterpret_cast<f32x2*>(v_wr + (i * 4 + 1) * WINO_POS) = t[i][1] + t[i][2];
-            *reinterpret_cast<f32x2*>(v_wr + (i * 4 + 2) * WINO_POS) = t[i][2] - t[i][1];
-            *reinterpret_cast<f32x2*>(v_wr + (i * 4 + 3) * WINO_POS) = t[i][1] - t[i][3];
-        }
+        const f32x2 v = j == 0 ? t_r[0] - t_r[2] : j == 1 ? t_r[1] + t_r[2] : j == 2 ? t_r[2] - t_r[1] : t_r[1] - t_r[3];     // (B^T d) B
+        *reinterpret_cast<f32x2*>(vs + v_wr + (i * 4 + j) * WINO_POS) = v;
     };
 
     // ---- transformed weights -> a buffer of Us: 8 LDS-DMA pieces per wave, source already in the LDS image's order -------------------------
-    const float* u_src = p.b + (size_t)nt * nslabs * WINO_IMG + tid * 4;
+    const float* u_src = p.b + (size_t)nt * nslabs * WINO_IMG;                         // scalar; the lane's piece of a DMA is the byte offset tid * 16
+    unsigned u_lane = (unsigned)tid * 16u;
     auto u_dma1 = [&](const float* src, float* ubuf, auto I) {                          // src: u_src + slab * WINO_IMG
         constexpr int i = decltype(I)::value;
         float* dst = ubuf + (i * 256 + wave * 64) * 4;                                  // wave-uniform base; the DMA writes lane-linear
         typedef const __attribute__((address_space(1))) void* gptr_t;
         typedef __attribute__((address_space(3))) void* lptr_t;
-        __builtin_amdgcn_global_load_lds((gptr_t)(src + i * 1024), (lptr_t)(dst), 16, 0, 0);
+        const char* us = reinterpret_cast<const char*>(src + i * 1024);
+        asm volatile("" : "+s"(us));          // kept scalar: the DMA takes it as its base ...
+        asm volatile("" : "+v"(u_lane));     // ... and the offset 32 bits wide up to the load
+        __builtin_amdgcn_global_load_lds((gptr_t)(us + u_lane), (lptr_t)(dst), 16, 0, 0);
     };
 
     f32x16 acc[16];
@@ -207,55 +228,84 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
 #define DS_WINO_EACH16(F, b) F((b) + 0) F((b) + 1) F((b) + 2) F((b) + 3) F((b) + 4) F((b) + 5) F((b) + 6) F((b) + 7)                \
                              F((b) + 8) F((b) + 9) F((b) + 10) F((b) + 11) F((b) + 12) F((b) + 13) F((b) + 14) F((b) + 15)
 
-    // ---- prologue: slab 0 staged, slab 1 requested -------------------------------------------------------------------------------------
+#define DS_WINO_LOADS(R, sl)                                                                                                           \
+    halo_load1(R, DS_WINO_I(0)); halo_load1(R, DS_WINO_I(1)); halo_load1(R, DS_WINO_I(2)); halo_load1(R, DS_WINO_I(3));                \
+    coef_load1(R, sl, DS_WINO_I(0)); coef_load1(R, sl, DS_WINO_I(1)); coef_load1(R, sl, DS_WINO_I(2));
+
+    // ---- prologue: halo 0 and 1 and transform 0 staged, halo 2 requested (two barriers) ------------------------------------------------
     halo_src(0);
-#define DS_WINO_F(j) halo_load1(DS_WINO_I(j));
-    DS_WINO_EACH4(DS_WINO_F)
-#undef DS_WINO_F
-    coef_load1(0, DS_WINO_I(0)); coef_load1(0, DS_WINO_I(1)); coef_load1(0, DS_WINO_I(2));
-    DS_RACE_SKEW(wave);
-#define DS_WINO_F(i) u_dma1(u_src, Us, DS_WINO_I(i)); u_dma1(u_src, Us, DS_WINO_I((i) + 4));
-    DS_WINO_EACH4(DS_WINO_F)
-#undef DS_WINO_F
-    DS_RACE_SKEW(wave);
-#define DS_WINO_F(c) halo_chain(DS_WINO_I(c), DS_WINO_I(0)); halo_chain(DS_WINO_I(c), DS_WINO_I(1)); halo_chain(DS_WINO_I(c), DS_WINO_I(2));
-    DS_WINO_EACH16(DS_WINO_F, 0)
-#undef DS_WINO_F
+    DS_WINO_LOADS(hreg, 0)
     {
+        HaloRegs hreg1;                                // slab 1, requested behind slab 0 so that the two latencies overlap
         const int s1 = min(1, nslabs - 1);
         halo_src(s1);
-#define DS_WINO_F(j) halo_load1(DS_WINO_I(j));
+        DS_WINO_LOADS(hreg1, s1)
+        DS_RACE_SKEW(wave);
+#define DS_WINO_F(i) u_dma1(u_src, Us, DS_WINO_I(i)); u_dma1(u_src, Us, DS_WINO_I((i) + 4));
         DS_WINO_EACH4(DS_WINO_F)
 #undef DS_WINO_F
-        coef_load1(s1, DS_WINO_I(0)); coef_load1(s1, DS_WINO_I(1)); coef_load1(s1, DS_WINO_I(2));
+        DS_RACE_SKEW(wave);
+#define DS_WINO_CHAIN1(c) halo_chain(hreg, Hs, DS_WINO_I(c), DS_WINO_I(0)); halo_chain(hreg, Hs, DS_WINO_I(c), DS_WINO_I(1));          \
+                          halo_chain(hreg, Hs, DS_WINO_I(c), DS_WINO_I(2));
+        DS_WINO_EACH16(DS_WINO_CHAIN1, 0)
+#undef DS_WINO_CHAIN1
+        DS_RACE_SKEW(wave);
+#define DS_WINO_CHAIN1(c) halo_chain(hreg1, Hs + h_buf, DS_WINO_I(c), DS_WINO_I(0)); halo_chain(hreg1, Hs + h_buf, DS_WINO_I(c), DS_WINO_I(1)); \
+                          halo_chain(hreg1, Hs + h_buf, DS_WINO_I(c), DS_WINO_I(2));
+        DS_WINO_EACH16(DS_WINO_CHAIN1, 0)
+#undef DS_WINO_CHAIN1
     }
+    {
+        const int s2 = min(2, nslabs - 1);
+        halo_src(s2);
+        DS_WINO_LOADS(hreg, s2)
+    }
+    __syncthreads();                                   // Hs[0], Hs[1] published
+#define DS_WINO_F(i) tr_read1(Hs, DS_WINO_I(i));
+    DS_WINO_EACH16(DS_WINO_F, 0)
+#undef DS_WINO_F
+    DS_RACE_SKEW(wave);
+#define DS_WINO_F(i) tr_write1(Vs, DS_WINO_I(i));
+    DS_WINO_EACH16(DS_WINO_F, 0)
+#undef DS_WINO_F
     DS_WINO_WAIT_VM0();
-    __syncthreads();
+    __syncthreads();                                   // Vs[0], Us[0] published; the halo of slab 2 is in its registers
 
-    // ---- K loop ------------------------------------------------------------------------------------------------------------------------
+    // ---- K loop: ONE barrier per slab -----------------------------------------------------------------------------------------------------
     // fragments of position group g (positions 4 g .. 4 g + 3) live in fa / fb[g & 1]; group g+1 is read in slots FR(g) .. FR(g) + 7 of
     // group g (behind the DMA pieces in group 0)
     f32x4 fa[2][4], fb[2][4];
     int s = 0;
     do {                                               // nslabs >= 1 (conv3x3_wino_applicable)
-        const float* ub = Us + (s & 1) * WINO_IMG;
-        transform();                                   // Hs -> Vs (Vs died at barrier C of the previous slab)
-        __syncthreads();                               // A: Vs published, Hs dead
-        const int s1 = min(s + 1, nslabs - 1), s2 = min(s + 2, nslabs - 1);
+        const int par = s & 1;
+        const float* ub = Us + par * WINO_IMG;
+        const float* vb = Vs + par * WINO_IMG;
+        float* ubn = Us + (par ^ 1) * WINO_IMG;        // last read by the MFMAs of slab s-1 (barrier s-1 passed)
+        float* vbn = Vs + (par ^ 1) * WINO_IMG;        // likewise
+        float* hb = Hs + par * h_buf;                  // last read by the transform of slab s, in front of barrier s-1
+        const float* hbn = Hs + (par ^ 1) * h_buf;     // the halo of slab s+1, published at barrier s-1
+        const int s1 = min(s + 1, nslabs - 1), s3 = min(s + 3, nslabs - 1);
         const float* un = u_src + (size_t)s1 * WINO_IMG;
-        float* ubn = Us + ((s + 1) & 1) * WINO_IMG;    // last read by the MFMAs of slab s-1 (barrier C passed)
-        if constexpr (kHalo) halo_src(s2);
         auto frag_read = [&](auto G, auto I) {
             constexpr int g = decltype(G)::value, i = decltype(I)::value;
-            if constexpr (i < 4) fa[g & 1][i] = *reinterpret_cast<const f32x4*>(Vs + (g * 4 + i) * WINO_POS + a_off);
+            if constexpr (i < 4) fa[g & 1][i] = *reinterpret_cast<const f32x4*>(vb + (g * 4 + i) * WINO_POS + a_off);
             else fb[g & 1][i - 4] = *reinterpret_cast<const f32x4*>(ub + (g * 4 + i - 4) * WINO_POS + b_off);
         };
-        if constexpr (kHalo) {                         // halo of slab s+1 (its loads were issued a slab ago, landed at barrier C)
-            DS_RACE_SKEW(wave);
-#define DS_WINO_F(c) halo_chain(DS_WINO_I(c), DS_WINO_I(0)); halo_chain(DS_WINO_I(c), DS_WINO_I(1)); halo_chain(DS_WINO_I(c), DS_WINO_I(2));
-            DS_WINO_EACH16(DS_WINO_F, 0)
+#define DS_WINO_F(i) tr_read1(hbn, DS_WINO_I(i));         // transform of slab s+1, first half: Hs[par ^ 1] -> registers
+        DS_WINO_EACH16(DS_WINO_F, 0)
 #undef DS_WINO_F
+        if constexpr (kHalo) {                         // halo of slab s+2 (its loads were issued a slab ago, landed at barrier s-1)
+            DS_RACE_SKEW(wave);
+#define DS_WINO_CHAIN1(c) halo_chain(hreg, hb, DS_WINO_I(c), DS_WINO_I(0)); halo_chain(hreg, hb, DS_WINO_I(c), DS_WINO_I(1));          \
+                          halo_chain(hreg, hb, DS_WINO_I(c), DS_WINO_I(2));
+            DS_WINO_EACH16(DS_WINO_CHAIN1, 0)
+#undef DS_WINO_CHAIN1
+            halo_src(s3);
         }
+        DS_RACE_SKEW(wave);
+#define DS_WINO_F(i) tr_write1(vbn, DS_WINO_I(i));        // second half: its adds, registers -> Vs[par ^ 1]
+        DS_WINO_EACH16(DS_WINO_F, 0)
+#undef DS_WINO_F
         auto fill = [&](auto K) {
             constexpr int k = decltype(K)::value, g = k >> 4;
             if constexpr (k < 8) {                     // weights of slab s+1
@@ -263,15 +313,15 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
                     if constexpr (k == 0) DS_RACE_SKEW(wave);
                     u_dma1(un, ubn, DS_WINO_I(k));
                 }
-            } else if constexpr (k < 12) {             // loads of slab s+2: they land at barrier C (vmcnt(0) for the weight DMA)
-                if constexpr (kHalo) halo_load1(DS_WINO_I(k - 8));
+            } else if constexpr (k < 12) {             // loads of slab s+3: they land at the barrier (vmcnt(0) for the weight DMA)
+                if constexpr (kHalo) halo_load1(hreg, DS_WINO_I(k - 8));
             } else if constexpr (k < 15) {
-                if constexpr (kHalo) coef_load1(s2, DS_WINO_I(k - 12));
+                if constexpr (kHalo) coef_load1(hreg, s3, DS_WINO_I(k - 12));
             }
             constexpr int fr = g == 0 ? 8 : g == 1 ? 20 : g == 2 ? 32 : 64;
             if constexpr (k >= fr && k < fr + 8) frag_read(DS_WINO_I(g + 1), DS_WINO_I(k - fr));
         };
-        // micro-slot k: K step r = (k >> 2) & 3 of position 4 (k >> 4) + (k & 3), then its filler, pinned
+        // micro-slot k: K step r = (k >> 2) & 3 of position 4 (k >> 4) + (k & 3), then its fillers, pinned
 #define DS_WINO_STEP(k)                                                                                                                \
         acc[((k) >> 4) * 4 + ((k) & 3)] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[((k) >> 4) & 1][(k) & 3][((k) >> 2) & 3],            \
                                                                                fb[((k) >> 4) & 1][(k) & 3][((k) >> 2) & 3],            \
@@ -288,8 +338,9 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
         DS_WINO_EACH16(DS_WINO_STEP, 48)
 #undef DS_WINO_STEP
         DS_WINO_WAIT_VM0();                            // the LDS-DMA of slab s+1 has landed (hipcc waits only in front of LDS reads it can tie to it)
-        __syncthreads();                               // C: Vs, Us[s & 1] dead; Hs and Us[(s+1) & 1] published
+        __syncthreads();                               // slab s done: Vs[par], Us[par] dead; Vs, Us and Hs [par ^ 1] published
     } while (++s < nslabs);
+#undef DS_WINO_LOADS
 
     if constexpr ((VAR & WV_NO_EPI) != 0) {
 #pragma unroll
@@ -311,9 +362,10 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
     // ---- appended 1x1 slabs (the fused skip projection; e0 | e1, 32 raw channels per slab): four plain MFMA groups on the post-transform
     // accumulators, one per patch pixel.  The slab's 256 pixels x 32 channels go global -> registers -> a V buffer as [patch pixel][8-channel
     // group][kh][tile][4], the untransformed weights (behind the U images in `wgt`, already in LDS order [group][kh][row][4]) by LDS-DMA into
-    // a weight buffer.  Every LDS buffer of the K loop died at its last barrier C (its clamped redundant DMA landed at the `vmcnt(0)` in
-    // front of it, and the redundant halo store went to Hs, which this loop does not touch), so both are doubled inside the three images:
-    //     W[b] = smem + b * 2048 (8 KB each, the first half of Us[0]),   V[0] = Vs,   V[1] = Us[1]
+    // a weight buffer.  Every LDS buffer of the K loop died at its last barrier (its clamped redundant DMA landed at the `vmcnt(0)` in
+    // front of it, its redundant transform wrote a Vs buffer in front of it, and the redundant halo store went to Hs, which this loop does
+    // not touch), so both are doubled inside the first three images:
+    //     W[b] = smem + b * 2048 (8 KB each, the first half of Us[0]),   V[0] = Vs[0],   V[1] = Us[1]
     // ONE barrier per slab.  Between barrier es-1 and barrier es, one basic block of 64 micro-slots in the K loop's style (an MFMA, then at
     // most one memory instruction, pinned): the MFMAs of slab es on V[es & 1] and W[es & 1], in the order group, K step r, patch pixel, and
     //     slots  0 ..  1   the two LDS-DMA pieces of the weights of slab es+1 -> W[(es+1) & 1]   (last read by slab es-1)
@@ -443,7 +495,7 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
 #undef DS_WINO_I
 
     // ---- the fused epilogue, one patch pixel (a, b) at a time ----------------------------------------------------------------------------
-    float* stage = smem + wave * 32 * WINO_EPI_LD;     // wave-private rows; every LDS buffer died at the last barrier C
+    float* stage = smem + wave * 32 * WINO_EPI_LD;     // wave-private rows; every LDS buffer died at the last barrier
     const int c4 = (lane & 7) * 4;
     const int col = n0 + wc * 32 + c4;
     f32x4 cb = {0.f, 0.f, 0.f, 0.f}, cvu = {0.f, 0.f, 0.f, 0.f};
@@ -506,8 +558,8 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
 
 template <int VAR, int NORM, int NSL>
 int launch_wino_ns(KParams& p, hipStream_t stream) {
-    const int smem = (3 * WINO_IMG + p.NP * WINO_K + 4) * (int)sizeof(float);        // + the spare halo cell
-    DS_ENSURE_DYN_LDS((&conv3x3_wino_kernel<VAR, NORM, NSL>), 128 * 1024);
+    const int smem = (4 * WINO_IMG + 2 * (p.NP * WINO_K + 4)) * (int)sizeof(float);  // Us, Vs and Hs doubled; + a spare halo cell each
+    DS_ENSURE_DYN_LDS((&conv3x3_wino_kernel<VAR, NORM, NSL>), 160 * 1024);
     hipLaunchKernelGGL((conv3x3_wino_kernel<VAR, NORM, NSL>), dim3(grid_1d(p.mtiles, p.ntiles)), dim3(256), smem, stream, p);
     DS_CHECK_LAUNCH();
     return DS_OK;
@@ -534,7 +586,7 @@ bool conv3x3_wino_applicable(const KParams& p) {
     if ((p.N & 63) || (p.c0 % WINO_K) || (p.c1 % WINO_K) || !p.vec_ok || p.out_planar || p.out_f16 || p.res_f16 || p.rowbias) return false;
     if (p.act != DS_ACT_NONE && p.act != DS_ACT_SILU) return false;
     const int np = (256 / p.W + 2) * (p.W + 2);
-    if (np * 2 > WINO_NSH * 256 || (3 * WINO_IMG + np * WINO_K + 4) * (int)sizeof(float) > 128 * 1024) return false;
+    if (np * 2 > WINO_NSH * 256 || (4 * WINO_IMG + 2 * (np * WINO_K + 4)) * (int)sizeof(float) > 160 * 1024) return false;
     return p.M % 256 == 0;
 }
 

@@ -70,7 +70,8 @@ DS_API int ds_build_experiments(void);   /* build flags.  Bit 0: always clear (u
  *   out[m, co] = act( ( sum_{tap,c} X(m, tap, c) * W[co, k(tap, c)] + bias[co] + cbias[img(m), co] + res[m, co] )
  *                     * out_scale )
  *   X(m, tap, c): zero-padded 3x3 neighbourhood of pixel m in the channel-concatenation [x0 | x1].
- * Constraints: c0 % 32 == 0, c1 % 32 == 0, all leading dimensions % 4 == 0, pointers 16-byte aligned,
+ * Constraints: c0 % 32 == 0, c1 % 32 == 0 (Winograd calls, `wino` != 0: % 8, the slab of conv3x3_wino.hip), all leading dimensions
+ * % 4 == 0, pointers 16-byte aligned,
  * W has ceil(cout/128)*128 rows (zero padded).
  */
 struct ds_update_args;            /* defined below ("Solver side"); ds_conv_args.update points to one */
