@@ -10,10 +10,10 @@
 //               output channels, four waves (2 x 2), one per SIMD; a wave holds ALL 16 positions of its 32 tiles x 32 channels
 //               (16 x f32x16 = 256 accumulator registers), so the output transform is lane-local
 //   slab      = 8 input channels.  Per slab: the raw halo (TH+2) x (W+2) pixels x 8 channels goes global -> registers -> LDS `Hs` with the
-//               consumer's GroupNorm affine + SiLU applied on the way (norm_coefs; out-of-image pixels are written as zeros AFTER the
-//               activation), is transformed to V = B^T d B in LDS `Vs` (16 positions x 64 tiles x 8 channels), and the transformed weights
-//               U of the workgroup's 64 columns (ops.pack_conv_weight_wino, already in the LDS image's order) stream global -> LDS by
-//               LDS-DMA into `Us`.  16 positions x 4 K steps of v_mfma_f32_32x32x2_f32 per wave and slab.  Us, Vs and Hs are double
+//               consumer's GroupNorm affine + SiLU applied on the way (norm_coefs; the cells of out-of-image pixels hold zeros, which
+//               the activation never sees), is transformed to V = B^T d B in LDS `Vs` (16 positions x 64 tiles x 8 channels), and the
+//               transformed weights U of the workgroup's 64 columns (ops.pack_conv_weight_wino, already in the LDS image's order) stream
+//               global -> LDS by LDS-DMA into `Us`.  16 positions x 4 K steps of v_mfma_f32_32x32x2_f32 per wave and slab.  Us, Vs and Hs are double
 //               buffers: 4 x 32 KiB + 2 x (NP x 32 + 16) bytes, at most 156 448 bytes of LDS.
 //   LDS image = [position][channel quad kh = 0 / 1][row 0..63][4 floats] for U and V alike: an MFMA fragment read is one ds_read_b128 per
 //               lane at (kh = lane >> 5, row = lane & 31), 512 contiguous bytes per 32 lanes -- conflict-free, and the K index of step r is
@@ -51,9 +51,20 @@
 // the MFMAs take a SCALAR base and a 32-bit lane offset (the `global_load ... v, s[..]` form; the offsets are kept in bytes and opaque,
 // so that the compiler does not widen them outside the loop).
 // Nothing in the block branches: what is uniform per launch (normalisation none / affine / affine + SiLU; 3 or 4 halo slots per thread) is
-// a template parameter, the source a0 | a1 is a scalar base plus a bit-select between two per-slot offsets, out-of-image pixels are loaded
-// from the nearest pixel of the same image and replaced by 0 AFTER the activation, and slots beyond the halo store into the spare cell
-// behind their Hs buffer.
+// a template parameter, the source a0 | a1 is a scalar base plus a bit-select between two per-slot offsets, and a slot that holds no
+// in-image pixel -- an out-of-image pixel of the halo, loaded from the nearest pixel of the same image, or a slot beyond the halo --
+// stores into the spare cell behind its Hs buffer.
+//
+// Out-of-image cells: which halo cells lie outside the image is fixed for the tile (its left and right columns; its top or bottom row
+// where the tile touches the image's), so their zeros are written ONCE, into both Hs buffers, where the thread's slots are set up in
+// front of the prologue -- by the thread that owns the slot, which never stores there again; the prologue's first barrier publishes
+// them with halo 0 and 1, and the LDS may hold whatever the workgroup before left.  The halo store used to select `in-image ? v : 0`
+// per element, 12 v_cndmask per slab and thread on top of the MFMAs (profiles/wino_persist_ab.txt: - 2.0 ... - 2.8 % per layer).
+//
+// One workgroup per tile.  A persistent form (one workgroup per compute unit, looping over the tiles b, b + G, ..., the next tile's
+// halo and weight requests in front of the epilogue and its halo stores in the epilogue's middle, epilogue staging moved to Vs[1]) was
+// built bit-identical and measured: + 1 % per layer by itself, nothing gained by the look-ahead (profiles/wino_persist_ab.txt).  It is
+// in no committed source.
 #include <type_traits>
 
 #include "igemm_common.h"
@@ -101,29 +112,36 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
     constexpr int kNorm = (VAR & WV_NO_NORM) ? 0 : NORM;       // the arithmetic of the halo store
 
     // ---- halo slots of this thread: (halo pixel, channel quad), fixed for the whole K loop ------------------------------------------
-    // Element offsets inside the tile's image for either source (an out-of-image pixel: the nearest pixel of the image, its value is
-    // replaced by 0 in the store), the LDS cell (a slot beyond the halo: the spare cell) and whether the pixel is inside the image.
+    // Element offsets inside the tile's image for either source (an out-of-image pixel: the nearest pixel of the image) and the LDS cell.
+    // An out-of-image pixel's cell holds zeros in BOTH Hs buffers for the whole tile: this thread writes them here, once, in front of
+    // every halo store (the LDS is whatever the workgroup before left), and sends the slot's stores to the spare cell, as it does for a
+    // slot beyond the halo.  No other thread writes those cells; the prologue's first barrier publishes them with halo 0 and 1.
     const int kh_h = tid & 1;
+    const int h_buf = p.NP * WINO_K + 4;           // floats per buffer of Hs, its spare cell included
     unsigned h_off0[WINO_NSH], h_off1[WINO_NSH];
     int h_lds[WINO_NSH];
-    bool h_ok[WINO_NSH];
 #pragma unroll
     for (int j = 0; j < WINO_NSH; ++j) {
         const int hp = (tid + j * 256) >> 1;
         const int hr = hp / p.WP, hc = hp - hr * p.WP;
         const int y = r0 + hr - 1, x = hc - 1;
         const bool in = hp < p.NP;
-        h_ok[j] = in && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
+        const bool ok = in && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
         const int pix = min(max(y, 0), p.H - 1) * p.W + min(max(x, 0), p.W - 1);
         h_off0[j] = (unsigned)(pix * p.lda0 + kh_h * 4) * 4u;       // BYTES: a load's address is the scalar base plus this 32-bit offset,
         h_off1[j] = (unsigned)(pix * p.lda1 + kh_h * 4) * 4u;       // with no 64-bit vector arithmetic between the MFMAs
-        h_lds[j] = in ? (((kh_h * 2 + (hc & 1)) * p.HP + hr) * WPH + (hc >> 1)) * 4 : p.NP * WINO_K;
+        const int cell = (((kh_h * 2 + (hc & 1)) * p.HP + hr) * WPH + (hc >> 1)) * 4;
+        h_lds[j] = ok ? cell : p.NP * WINO_K;
+        if (in && !ok) {
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<f32x4*>(Hs + cell) = z;
+            *reinterpret_cast<f32x4*>(Hs + h_buf + cell) = z;
+        }
     }
     const float* a0i = p.a0 + (size_t)img0 * p.HW * p.lda0;
     const float* a1i = p.a1 + (size_t)img0 * p.HW * p.lda1;
     const float* cpi = p.norm + (size_t)img0 * 3 * Ctot;       // scalar; the lane's channel quad is the byte offset c_lane
     unsigned c_lane = (unsigned)(kh_h * 16);
-    const int h_buf = p.NP * WINO_K + 4;           // floats per buffer of Hs, its spare cell included
     // a slab's halo on its way: the raw pixels of this thread's slots and the slab's coefficient planes {mu, A, B}
     struct HaloRegs {
         f32x4 h[WINO_NSH];
@@ -158,8 +176,8 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
         }
     };
     // stage ST of element chain C (slot C / 4, float C % 4) of the halo store into the buffer `hs` of Hs: the consumer's GroupNorm affine
-    // + SiLU, applied once per element; zeros are written after the activation.  The affine is a subtraction and ONE fma, the SiLU is
-    // ds_silu's operations.
+    // + SiLU, applied once per element (an out-of-image pixel's value goes to the spare cell; its own cell holds zeros).  The affine
+    // is a subtraction and ONE fma, the SiLU is ds_silu's operations.
     auto halo_chain = [&](HaloRegs& R, float* hs, auto C, auto ST) {
         constexpr int c = decltype(C)::value, st = decltype(ST)::value, j = c >> 2, e = c & 3;
         if constexpr (j >= NSL) return;
@@ -172,7 +190,7 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
             float v = R.h[j][e];
             if constexpr (kNorm == 1) v = h_t[c];
             if constexpr (kNorm == 2) v = h_t[c] * h_u[c];
-            R.h[j][e] = h_ok[j] ? v : 0.f;
+            R.h[j][e] = v;
             if constexpr (e == 3) *reinterpret_cast<f32x4*>(hs + h_lds[j]) = R.h[j];
         }
     };

@@ -1,5 +1,6 @@
 """sha256 of the output and of the statistics of the Winograd convolution (csrc/conv3x3_wino.hip) on the cases of tests/test_hip_wino_pipe.py,
-tests/test_hip_wino.py, tests/test_hip_wino_pipe2.py and tests/test_hip_wino_kloop.py: a change to the kernel that claims bit identity is run once from each tree and the two listings compared.
+tests/test_hip_wino.py, tests/test_hip_wino_pipe2.py, tests/test_hip_wino_kloop.py and tests/test_hip_wino_persist.py (launches of more
+tiles than compute units): a change to the kernel that claims bit identity is run once from each tree and the two listings compared.
 
     python tools/wino_bits.py [--root TREE] [--out FILE]
 
@@ -36,7 +37,7 @@ def main():
     lib = _lib.load()
     lines = [f'# tree {os.path.relpath(root, HERE)}  library {os.path.relpath(_lib.LIB_PATH, root)}']
     for fname, builder in (('test_hip_wino_pipe.py', 'conv_args'), ('test_hip_wino.py', '_args'), ('test_hip_wino_pipe2.py', 'conv_args'),
-                           ('test_hip_wino_kloop.py', 'conv_args')):
+                           ('test_hip_wino_kloop.py', 'conv_args'), ('test_hip_wino_persist.py', 'conv_args')):
         mod = _load(os.path.join(HERE, 'tests', fname))
         for name in mod.CASES:
             args, out, stats, keep = getattr(mod, builder)(name)
