@@ -15,7 +15,7 @@ vp = C.c_void_p
 DSM_VERSION = 2
 DSM_MAX_K = 8
 DS_OK, DS_E_ARG, DS_E_ALIGN, DS_E_SHAPE = 0, -1, -2, -3
-
+DSM_ACT_NONE, DSM_ACT_GELU, DSM_ACT_QUICK_GELU = 0, 1, 2          # dsm_gemm_split_args.act
 
 
 class DsmAttnArgs(C.Structure):
@@ -23,6 +23,12 @@ class DsmAttnArgs(C.Structure):
     _fields_ = [('q', vp), ('k', vp), ('v', vp), ('out', vp), ('ldq', C.c_int), ('ldk', C.c_int), ('ldv', C.c_int), ('ldo', C.c_int),
                 ('q_bs', C.c_longlong), ('k_bs', C.c_longlong), ('v_bs', C.c_longlong), ('o_bs', C.c_longlong), ('batch', C.c_int),
                 ('heads', C.c_int), ('sq', C.c_int), ('skv', C.c_int), ('d', C.c_int), ('scale', C.c_float), ('reserved', C.c_int * 3)]
+
+
+class DsmGemmSplitArgs(C.Structure):
+    """dsm_gemm_split_args: out = act(x W^T 2^-shift + bias) + res with split-fp16 weights (ops.pack_linear_weight_split)."""
+    _fields_ = [('x', vp), ('ldx', C.c_int), ('rows', C.c_longlong), ('k', C.c_int), ('w_split', vp), ('shift', C.c_int), ('cout', C.c_int),
+                ('bias', vp), ('res', vp), ('res_ld', C.c_int), ('act', C.c_int), ('out', vp), ('out_ld', C.c_int), ('reserved', C.c_int * 3)]
 
 
 _SIGNATURES = {
@@ -41,6 +47,8 @@ _SIGNATURES = {
     'dsm_gather_rows': (C.c_int, [vp, C.c_int, C.c_longlong, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     'dsm_clip_score': (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     'dsm_resize_crop_u8': (C.c_int, [vp, C.c_longlong, C.c_int] + [C.c_int] * 8 + [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]),
+    'dsm_gemm_split': (C.c_int, [C.POINTER(DsmGemmSplitArgs), vp]),
+    'dsm_gemm_split_supported': (C.c_int, [C.c_longlong, C.c_int, C.c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

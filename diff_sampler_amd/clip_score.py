@@ -12,6 +12,10 @@ The CLIP weights are a local file (``--model``: a HF ``CLIPModel`` or an open_cl
 downloaded), the captions a csv with a ``text`` column (``--prompts``; the reference fetches the COCO captions file itself), the tokenizer
 a directory holding ``vocab.json`` and ``merges.txt`` (``clip_tokenizer``).
 
+``--dtype fp16x3`` (``ClipScorer(..., dtype='fp16x3')``): the four projections of every transformer layer run as split-fp16 GEMMs with fp32
+operands and results (``dsm_gemm_split``, csrc/metrics/gemm_split.hip) -- fp32 tolerances at about 2.3 times the tower throughput.  The
+activations entering a projection must stay within fp16's range (65504); the scorer checks the features of every batch and raises otherwise.
+
 CAPTION PAIRING: image i of the sorted FULL listing goes with caption i.  That equals the reference whenever no subset is taken.  With
 ``--num`` the reference pairs position j of the shuffled-and-sorted subset with caption j (clip_score.py:79 slices the captions by subset
 position while dataset.py picked other images), i.e. it scores images against other images' captions; that is not reproduced.
@@ -88,11 +92,11 @@ def load_state_dict(path):
 class ClipScorer:
     """``ClipScorer(spec, params, tokenizer).score(images_u8, tokens_or_prompts) -> [B]`` fp32: ``100 * cos(image feature, text feature)``."""
 
-    def __init__(self, spec: arch.ClipScoreSpec, params, tokenizer=None, device='cuda'):
+    def __init__(self, spec: arch.ClipScoreSpec, params, tokenizer=None, device='cuda', dtype='fp32'):
         from .clip_score_engine import ClipImageEncoder, ClipPooledTextEncoder
-        self.spec, self.tokenizer, self.device = spec, tokenizer, torch.device(device)
-        self.image = ClipImageEncoder(spec, params, device)
-        self.text = ClipPooledTextEncoder(spec, params, device)
+        self.spec, self.tokenizer, self.device, self.dtype = spec, tokenizer, torch.device(device), dtype
+        self.image = ClipImageEncoder(spec, params, device, dtype=dtype)
+        self.text = ClipPooledTextEncoder(spec, params, device, dtype=dtype)
         self.mlib = _metrics_lib.load()
         self.total = torch.zeros(1, dtype=torch.float64, device=self.device)       # running fp64 sum of every score() since reset()
 
@@ -102,11 +106,11 @@ class ClipScorer:
         return cls(spec, arch.init_clip_score_params(spec, seed), **kw)
 
     @classmethod
-    def from_checkpoint(cls, path, tokenizer=None, device='cuda', act='gelu'):
+    def from_checkpoint(cls, path, tokenizer=None, device='cuda', act='gelu', dtype='fp32'):
         sd = load_state_dict(path)
         spec = arch.spec_from_state_dict(sd, act=act)
         params = arch.from_open_clip(spec, sd) if arch.is_open_clip(sd) else arch.params_from_state_dict(spec, sd)
-        return cls(spec, params, tokenizer, device)
+        return cls(spec, params, tokenizer, device, dtype=dtype)
 
     def tokens(self, tokens_or_prompts) -> torch.Tensor:
         x = tokens_or_prompts
@@ -127,6 +131,11 @@ class ClipScorer:
         fi, _ = self.image.raw(images_u8)
         ft, _ = self.text.raw(t)
         B, E = fi.shape
+        if self.dtype == 'fp16x3':
+            for which, f in (('image', fi), ('text', ft)):
+                if not bool(torch.isfinite(f).all()):
+                    raise FloatingPointError(f"{which} features are not finite: dtype='fp16x3' splits every projection input into fp16 halves and "
+                                             f'holds activations up to 65504 in magnitude only; score this model with --dtype fp32')
         scores = torch.empty(B, dtype=torch.float32, device=self.device)
         vp = lambda x: C.c_void_p(x.data_ptr())
         _metrics_lib.check(self.mlib.dsm_clip_score(vp(fi), E, vp(ft), E, B, E, vp(scores), vp(self.total), _lib.stream_ptr()), 'dsm_clip_score')
@@ -212,7 +221,9 @@ if click is not None:
     @click.option('--desc', help='A description string (written to clip_score.txt in place of the folder names)', metavar='str', type=str)
     @click.option('--device', type=str, default=None)
     @click.option('--device_resize', help='Resize and crop on the device (the same bits as the host transform)', is_flag=True)
-    def calc(image_path, prompt_path, model_path, tokenizer_path, num_expected, seed, batch, desc, device, device_resize):
+    @click.option('--dtype', help='fp16x3: the towers\' projections on the fp16 matrix pipe with split fp32 operands (fp32 accuracy, activations up to 65504)',
+                  type=click.Choice(['fp32', 'fp16x3']), default='fp32', show_default=True)
+    def calc(image_path, prompt_path, model_path, tokenizer_path, num_expected, seed, batch, desc, device, device_resize, dtype):
         """Calculate the CLIP score of a folder of images against their captions."""
         from .clip_tokenizer import ClipTokenizer
         dist, rank = _init_dist()
@@ -222,7 +233,7 @@ if click is not None:
         captions = read_captions(prompt_path)
         log(f'Loading the CLIP model from "{model_path}"...')
         with torch.no_grad():
-            scorer = ClipScorer.from_checkpoint(model_path, ClipTokenizer(tokenizer_path), device)
+            scorer = ClipScorer.from_checkpoint(model_path, ClipTokenizer(tokenizer_path), device, dtype=dtype)
             avg, n = calc_clip_score(scorer, image_path, captions, num_expected=num_expected, seed=seed, max_batch_size=batch, log=log,
                                      device_resize=device_resize)
         if rank == 0:

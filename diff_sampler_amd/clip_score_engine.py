@@ -15,6 +15,12 @@ ctypes calls per layer, noise next to a ViT-g layer.
     text      ds_token_embed -> the same layer with ds_attention_causal -> dsm_gather_rows (row of the first argmax(ids) per prompt, computed
               on the host) -> final LayerNorm (a row operation: applied to the B gathered rows only) -> text_projection
 
+``dtype='fp16x3'`` (trailing keyword of both encoders; default ``'fp32'``, whose launch lists it leaves alone): the four projections of every
+layer -- q | k | v, out_proj, fc1, fc2 -- become ``dsm_gemm_split`` launches (csrc/metrics/gemm_split.hip: fp32 operands split into two fp16
+halves, three products on the fp16 matrix pipe, fp32 accumulation and fp32 results), fc1 carries the GELU in its epilogue (no GELU launch),
+out_proj and fc2 the residual.  LayerNorm, attention, the token assembly, the gathers, the patch projection and the pooled head projection
+stay on the fp32 kernels above.  Activations must stay inside fp16's range (|x| <= 65504); ``ClipScorer`` checks the features.
+
 Plans build on ``device='cpu'`` without running anything (the launch list is then testable without a GPU); a geometry no kernel covers is a
 ``NotImplementedError`` at build time, never a fallback.
 """
@@ -26,17 +32,28 @@ from typing import Dict
 import torch
 
 from . import _lib, _metrics_lib, clip_score_arch as arch
-from .ops import pack_linear_weight
+from .ops import pack_linear_weight, pack_linear_weight_split
 from .plan import Builder, Plan, ptr
 
 
-def _pack_layers(w, g, prefix, t):
+DTYPES = ('fp32', 'fp16x3')
+
+
+def _pack_layers(w, g, prefix, t, split=False):
+    """split: the four projections as split-fp16 operands of dsm_gemm_split (ops.pack_linear_weight_split), their power-of-two shift under '<name>.s'."""
+    def pack(dst, m):
+        if split:
+            w[f'{dst}.w'], w[f'{dst}.s'] = pack_linear_weight_split(m)
+        else:
+            w[f'{dst}.w'] = pack_linear_weight(m)
+
     for i in range(t.layers):
         p = f'{prefix}.encoder.layers.{i}'
-        w[f'{i}.qkv.w'] = pack_linear_weight(torch.cat([g(f'{p}.self_attn.{x}_proj.weight') for x in 'qkv'], 0))
+        pack(f'{i}.qkv', torch.cat([g(f'{p}.self_attn.{x}_proj.weight') for x in 'qkv'], 0))
         w[f'{i}.qkv.b'] = torch.cat([g(f'{p}.self_attn.{x}_proj.bias') for x in 'qkv'], 0).contiguous()
         for dst, src in (('o', 'self_attn.out_proj'), ('fc1', 'mlp.fc1'), ('fc2', 'mlp.fc2')):
-            w[f'{i}.{dst}.w'], w[f'{i}.{dst}.b'] = pack_linear_weight(g(f'{p}.{src}.weight')), g(f'{p}.{src}.bias')
+            pack(f'{i}.{dst}', g(f'{p}.{src}.weight'))
+            w[f'{i}.{dst}.b'] = g(f'{p}.{src}.bias')
         for dst, src in (('n1', 'layer_norm1'), ('n2', 'layer_norm2')):
             w[f'{i}.{dst}.g'], w[f'{i}.{dst}.b'] = g(f'{p}.{src}.weight'), g(f'{p}.{src}.bias')
 
@@ -45,9 +62,13 @@ class _Tower:
     """What the two encoders share: the libraries, the per-batch plan cache, the transformer layer and the foreign launches."""
     prefix = ''
 
-    def __init__(self, spec: arch.ClipScoreSpec, params: Dict[str, torch.Tensor], device='cuda'):
+    def __init__(self, spec: arch.ClipScoreSpec, params: Dict[str, torch.Tensor], device='cuda', dtype='fp32'):
+        if dtype not in DTYPES:
+            raise ValueError(f'dtype must be one of {DTYPES}, got {dtype!r}')
         self.spec = spec
         self.device = torch.device(device)
+        self.dtype = dtype
+        self.split = dtype == 'fp16x3'
         self.lib = _lib.load()
         self.mlib = _metrics_lib.load()
         self._plans: Dict[int, Plan] = {}
@@ -80,6 +101,23 @@ class _Tower:
                                          kw['v_bs'], kw['o_bs'], N, H, S, S, D, kw['scale'])
             bd.add(self.mlib.dsm_attention, (C.byref(a),), name, keep=(a,))
 
+    def _split_linear(self, bd, x, k, rows, key, cout, out, name, res=None, act=_metrics_lib.DSM_ACT_NONE):
+        """fp16x3: out[rows, cout] = act(x[rows, k] W^T + bias) + res as ONE dsm_gemm_split launch (dense operands)."""
+        if not self.mlib.dsm_gemm_split_supported(rows, k, cout):
+            raise NotImplementedError(f'{name}: dsm_gemm_split does not cover {rows} rows x {k} -> {cout} (k and cout must be multiples of 32)')
+        w = self.w
+        a = _metrics_lib.DsmGemmSplitArgs(ptr(x), k, rows, k, ptr(w[key + '.w']), w[key + '.s'], cout, ptr(w[key + '.b']), ptr(res), cout if res is not None else 0,
+                                          act, ptr(out), cout)
+        bd.add(self.mlib.dsm_gemm_split, (C.byref(a),), name, keep=(a,))
+
+    def _split_ok(self, t, tower):
+        """fp16x3 at build time: every projection of the tower's layers must be a geometry dsm_gemm_split takes."""
+        if not self.split:
+            return
+        for name, k, cout in (('qkv', t.width, 3 * t.width), ('out_proj', t.width, t.width), ('fc1', t.width, t.ffn), ('fc2', t.ffn, t.width)):
+            if not self.mlib.dsm_gemm_split_supported(1, k, cout):
+                raise NotImplementedError(f"{tower} tower: dtype='fp16x3' has no kernel for {name} ({k} -> {cout}): width and ffn must be multiples of 32")
+
     def _attention_ok(self, D, S, causal):
         if causal:
             return bool(self.lib.ds_attention_causal_supported(D, S))
@@ -95,22 +133,35 @@ class _Tower:
             n = bd.alloc(M, W)
             bd.layernorm(x, W, w[f'{i}.n1.g'], w[f'{i}.n1.b'], eps, n, W, M, W, p + '.layer_norm1')
             qkv = bd.alloc(M, 3 * W)
-            bd.linear(n, W, M, w[f'{i}.qkv.w'], 3 * W, qkv, p + '.qkv', bias=w[f'{i}.qkv.b'])
+            if self.split:
+                self._split_linear(bd, n, W, M, f'{i}.qkv', 3 * W, qkv, p + '.qkv')
+            else:
+                bd.linear(n, W, M, w[f'{i}.qkv.w'], 3 * W, qkv, p + '.qkv', bias=w[f'{i}.qkv.b'])
             bd.free(n)
             ao = bd.alloc(M, W)
             self._attention(bd, qkv, ao, p + '.attention', N, H, S, D, W, causal)
             bd.free(qkv)
             x1 = bd.alloc(M, W)
-            bd.linear(ao, W, M, w[f'{i}.o.w'], W, x1, p + '.out_proj', bias=w[f'{i}.o.b'], res=x, res_ld=W)
+            if self.split:
+                self._split_linear(bd, ao, W, M, f'{i}.o', W, x1, p + '.out_proj', res=x)
+            else:
+                bd.linear(ao, W, M, w[f'{i}.o.w'], W, x1, p + '.out_proj', bias=w[f'{i}.o.b'], res=x, res_ld=W)
             bd.free(ao, x)
             n = bd.alloc(M, W)
             bd.layernorm(x1, W, w[f'{i}.n2.g'], w[f'{i}.n2.b'], eps, n, W, M, W, p + '.layer_norm2')
             hid = bd.alloc(M, F)
-            bd.linear(n, W, M, w[f'{i}.fc1.w'], F, hid, p + '.fc1', bias=w[f'{i}.fc1.b'])
-            bd.free(n)
-            self._gelu(bd, hid, F, M, F, p)
-            x = bd.alloc(M, W)
-            bd.linear(hid, F, M, w[f'{i}.fc2.w'], W, x, p + '.fc2', bias=w[f'{i}.fc2.b'], res=x1, res_ld=W)
+            if self.split:               # the GELU rides in fc1's epilogue: no pass over [M, F] of its own
+                act = _metrics_lib.DSM_ACT_QUICK_GELU if self.spec.act == 'quick_gelu' else _metrics_lib.DSM_ACT_GELU
+                self._split_linear(bd, n, W, M, f'{i}.fc1', F, hid, p + '.fc1', act=act)
+                bd.free(n)
+                x = bd.alloc(M, W)
+                self._split_linear(bd, hid, F, M, f'{i}.fc2', W, x, p + '.fc2', res=x1)
+            else:
+                bd.linear(n, W, M, w[f'{i}.fc1.w'], F, hid, p + '.fc1', bias=w[f'{i}.fc1.b'])
+                bd.free(n)
+                self._gelu(bd, hid, F, M, F, p)
+                x = bd.alloc(M, W)
+                bd.linear(hid, F, M, w[f'{i}.fc2.w'], W, x, p + '.fc2', bias=w[f'{i}.fc2.b'], res=x1, res_ld=W)
             bd.free(hid, x1)
         return x
 
@@ -137,9 +188,9 @@ class ClipImageEncoder(_Tower):
     The CLIP mean / std are applied on the device while the patch rows are formed."""
     keys = ('vision_model.', 'visual_projection.')
 
-    def __init__(self, spec, params, device='cuda', mean=arch.CLIP_MEAN, std=arch.CLIP_STD):
+    def __init__(self, spec, params, device='cuda', mean=arch.CLIP_MEAN, std=arch.CLIP_STD, dtype='fp32'):
         self.mean, self.std = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
-        super().__init__(spec, params, device)
+        super().__init__(spec, params, device, dtype)
 
     def _check_geometry(self):
         t, S = self.spec.vision, self.spec.vision_tokens
@@ -147,6 +198,7 @@ class ClipImageEncoder(_Tower):
             raise NotImplementedError(f'image tower: no attention kernel for head size {t.head_dim}')
         if t.width > 2048:
             raise NotImplementedError('image tower: the LayerNorm row kernel ends at 2048 columns')
+        self._split_ok(t, 'image')
 
     def _pack(self, g):
         spec, w = self.spec, {}
@@ -154,7 +206,7 @@ class ClipImageEncoder(_Tower):
         w['patch.w'] = pack_linear_weight(g('vision_model.embeddings.patch_embedding.weight').reshape(spec.vision.width, -1))
         assert w['patch.w'].shape[1] == self.kpad
         w['cls'], w['pos'] = g('vision_model.embeddings.class_embedding'), g('vision_model.embeddings.position_embedding.weight')
-        _pack_layers(w, g, 'vision_model', spec.vision)
+        _pack_layers(w, g, 'vision_model', spec.vision, self.split)
         for dst, src in (('pre', 'pre_layrnorm'), ('post', 'post_layernorm')):
             w[f'{dst}.g'], w[f'{dst}.b'] = g(f'vision_model.{src}.weight'), g(f'vision_model.{src}.bias')
         w['proj'] = pack_linear_weight(g('visual_projection.weight'))
@@ -227,11 +279,12 @@ class ClipPooledTextEncoder(_Tower):
             raise NotImplementedError(f'text tower: no causal attention kernel for head size {t.head_dim} over {S} tokens')
         if t.width > 2048:
             raise NotImplementedError('text tower: the LayerNorm row kernel ends at 2048 columns')
+        self._split_ok(t, 'text')
 
     def _pack(self, g):
         spec, w = self.spec, {}
         w['tok'], w['pos'] = g('text_model.embeddings.token_embedding.weight'), g('text_model.embeddings.position_embedding.weight')
-        _pack_layers(w, g, 'text_model', spec.text)
+        _pack_layers(w, g, 'text_model', spec.text, self.split)
         w['nf.g'], w['nf.b'] = g('text_model.final_layer_norm.weight'), g('text_model.final_layer_norm.bias')
         w['proj'] = pack_linear_weight(g('text_projection.weight'))
         self.w = w

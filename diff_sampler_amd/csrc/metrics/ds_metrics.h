@@ -3,6 +3,8 @@
  *
  * Second part (DSM_VERSION 2, below the PRDC entry points): the device code of the CLIP score -- csrc/metrics/clip_score.hip, and the
  * resize and crop in front of it -- csrc/metrics/image_prep.hip (added without a version step: nothing existing changed).
+ * Third part (at the end; again without a version step): dsm_gemm_split -- csrc/metrics/gemm_split.hip, the Linear layer of the towers' fp16x3
+ * mode: fp32 operands and fp32 results, every product as three fp16 products (split hi / lo halves) on the fp16 matrix pipe.
  *
  * Precision / recall / density / coverage and per-sample realism (sfd-main/prdc.py) on detector features.  Features are
  * [n][ld] row-major with ld >= dim, fp32 (widened exactly) or fp64 chosen by a flag per operand; all arithmetic is fp64.
@@ -116,6 +118,41 @@ DSM_API int dsm_clip_score(const float* a, int lda, const float* b, int ldb, int
 DSM_API int dsm_resize_crop_u8(const void* src, long long image_stride, int pitch, int n, int h, int w, int nh, int nw, int top, int left,
                                int size, const int* hbounds, const int* hcoeffs, int hksize, const int* vbounds, const int* vcoeffs,
                                int vksize, void* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------------
+ * fp16x3: a Linear layer with fp32 operands and results on the fp16 matrix pipe (csrc/metrics/gemm_split.hip; added without a version
+ * step: nothing existing changed).
+ *
+ *     out[r, :cout] = act(x[r, :k] . W^T . 2^-shift + bias) + res[r, :cout]          for r < rows
+ *
+ * x, bias, res, out: fp32.  w_split: the weights W [cout][k] split once on the host (ops.pack_linear_weight_split): W' = W 2^shift,
+ * hi = fp16(W'), lo = fp16(W' - hi), stored as fp16 [ceil(cout / 128) * 128][2 k] -- per 32-column block of K 32 hi halves, then 32 lo halves;
+ * the rows beyond cout are zeros and ARE read.  The kernel splits x the same way while it stages a tile, without scaling, and adds
+ * hi.hi + hi.lo + lo.hi per product on v_mfma_f32_32x32x16_f16 into an fp32 accumulator, which the epilogue multiplies by the exact 2^-shift.
+ * DOMAIN: finite inputs with |x| <= 65504 (beyond that the hi half is infinite); x below 2^-3 in magnitude carries an absolute error of up to
+ * 2^-24 |w| per product (the lo half is an fp16 subnormal), everything else a relative 3 * 2^-22 per product.
+ * No split-K, no atomics, a fixed K order: the bits of an output row depend on that row of x (and res) and on the weights alone -- not on
+ * `rows`, not on the row's position.  Columns [cout, out_ld) of out are never written.
+ * act: DSM_ACT_NONE, DSM_ACT_GELU (0.5 v (1 + erf(v / sqrt 2)), dsm_gelu_rows' form) or DSM_ACT_QUICK_GELU (v sigmoid(1.702 v), ds_quick_gelu's form);
+ * an activation and a residual exclude each other.  bias and res may be NULL.
+ * Geometry: dsm_gemm_split_supported(rows, k, cout) -- rows >= 1, k and cout positive multiples of 32 -- otherwise DS_E_SHAPE.
+ * DS_E_ARG: NULL a / x / w_split / out, ldx < k, out_ld < cout, res_ld < cout (with res), res == out (res must not overlap out), res with an
+ * activation, an unknown act, shift outside [0, 126], a non-zero reserved field;  DS_E_ALIGN: a pointer not 16-byte aligned, ldx / out_ld /
+ * res_ld (with res) not a multiple of 4.  No workspace, no allocation, no synchronisation. */
+#define DSM_ACT_NONE 0
+#define DSM_ACT_GELU 1
+#define DSM_ACT_QUICK_GELU 2
+
+typedef struct dsm_gemm_split_args {
+    const float* x; int ldx; long long rows; int k;
+    const void* w_split; int shift; int cout;
+    const float* bias; const float* res; int res_ld; int act;
+    float* out; int out_ld;
+    int reserved[3];     /* must be 0 */
+} dsm_gemm_split_args;
+
+DSM_API int dsm_gemm_split(const dsm_gemm_split_args* a, void* stream);
+DSM_API int dsm_gemm_split_supported(long long rows, int k, int cout);
 
 #ifdef __cplusplus
 }

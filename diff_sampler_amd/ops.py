@@ -161,6 +161,34 @@ def pack_conv_weight_split(w: torch.Tensor, extra: Optional[torch.Tensor] = None
     return out.contiguous().view(torch.float32), shift
 
 
+def pack_linear_weight_split(w: torch.Tensor, row_pad: int = 128):
+    """Split-fp16 weights of the fp32-emulated Linear layer (libdsmetrics' dsm_gemm_split) -> (packed tensor, shift).
+
+    [Cout, K] with K % 32 == 0.  The scaling rule of pack_conv_weight_split: the weights are multiplied by 2**shift (exact; the largest
+    magnitude lands in [2**13, 2**14)), split as hi = fp16(w'), lo = fp16(w' - hi) and laid out per 32-column block of K as 32 hi halfs
+    followed by 32 lo halfs: half 64 * (c // 32) + {c % 32 | 32 + c % 32} of a row; rows zero-padded to a multiple of `row_pad` (the kernel
+    reads whole 128-row tiles).  All-zero weights give shift 0; weights fp16 cannot hold (non-finite, or |w| >= 65504, which leaves shift 0)
+    raise ValueError.  Float32-typed view of the bytes: [rows, K] floats = [rows, 2 K] halfs."""
+    import math
+    if w.dim() != 2 or w.shape[1] % 32 != 0 or w.shape[1] == 0:
+        raise ValueError(f'pack_linear_weight_split takes [cout, k] weights with k a positive multiple of 32, got {tuple(w.shape)}')
+    if row_pad < 1 or row_pad % 128 != 0:
+        raise ValueError(f'row_pad must be a positive multiple of 128 (the kernel reads 128-row weight tiles), got {row_pad}')
+    cout, k = w.shape
+    w = w.to(torch.float32)
+    wmax = float(w.abs().max()) if w.numel() else 0.0
+    if not math.isfinite(wmax) or wmax >= 65504.0:
+        raise ValueError(f'pack_linear_weight_split: largest weight magnitude {wmax} is outside the fp16 range (|w| < 65504)')
+    shift = 0 if wmax == 0 else max(0, min(24, 13 - math.floor(math.log2(wmax))))
+    m = w.reshape(cout, k // 32, 32) * float(1 << shift)
+    hi = m.to(torch.float16)
+    lo = (m - hi.to(torch.float32)).to(torch.float16)
+    rows = -(-cout // row_pad) * row_pad
+    out = torch.zeros(rows, 2 * k, dtype=torch.float16, device=w.device)
+    out[:cout] = torch.cat([hi, lo], dim=-1).reshape(cout, 2 * k)
+    return out.contiguous().view(torch.float32), shift
+
+
 def pack_stem_weight(w: torch.Tensor, row_pad: int = 128, k_pad: int = 32) -> torch.Tensor:
     """Stem conv [Cout, C, 3, 3] for the im2col'd input of ds_stem_im2col: K = tap*C + c, zero-padded to 32."""
     cout, cin, kh, kw = w.shape

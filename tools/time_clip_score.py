@@ -3,12 +3,13 @@
 next to the plain-torch restatement of the same towers (tests/_clip_vit_ref.py) in stock PyTorch-ROCm fp32 on the same GPU in the same
 process.
 
-    python tools/time_clip_score.py [--config vit_g_14] [--batch 64] [--calls 5] [--session NAME] [--out profiles/clip_score_timing.txt]
+    python tools/time_clip_score.py [--config vit_g_14] [--batch 64] [--calls 5] [--session NAME] [--out profiles/clip_score_timing.txt] [--dtype fp32|fp16x3]
 
 Every timing is a pair of events around ONE call on the current stream, after warm-up calls of every variant; engine and stock calls
 alternate; median with min / max.  The per-launch table is one replay of each tower's plan with an event pair per launch, grouped by
 launch kind.  The host preprocessing (PIL: 512 x 512 RGB -> uint8 224 x 224, the reference's own path) is timed on the host per image and
 reported as a share of host + device time per image -- it is not part of the device numbers.  No GPU: the tool fails.
+``--dtype fp16x3`` times the engine in that mode (ClipScorer(dtype='fp16x3')) and, alternating in the same rounds, the fp32 engine too.
 """
 import argparse
 import collections
@@ -77,6 +78,7 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--session', default='')
     ap.add_argument('--out', default='')
+    ap.add_argument('--dtype', default='fp32', choices=['fp32', 'fp16x3'])
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'tools/time_clip_score.py measures on the GPU only'
     import _clip_vit_ref as R
@@ -93,9 +95,10 @@ def main():
     spec = A.named_spec(args.config)
     B = args.batch
     say(f'# tools/time_clip_score.py on {pr.gcnArchName} / {pr.multi_processor_count} CUs, session {args.session or "-"}: {args.config}, seed weights, '
-        f'batch {B}, fp32; median of {args.calls} timed calls after 2 warm-up rounds, engine and stock calls alternated')
+        f'batch {B}, engine dtype {args.dtype} (stock: fp32); median of {args.calls} timed calls after 2 warm-up rounds, engine and stock calls alternated')
     params = A.init_clip_score_params(spec, args.seed)
-    scorer = ClipScorer(spec, params)
+    scorer = ClipScorer(spec, params, dtype=args.dtype)
+    scorer32 = ClipScorer(spec, params) if args.dtype != 'fp32' else None
     dev = {k: v.cuda() for k, v in params.items()}
     images = R.seed_images(1, B, spec.image_size)
     g = torch.Generator().manual_seed(2)
@@ -128,8 +131,12 @@ def main():
     def engine_score():
         out['es'] = scorer.score(images_d, tokens)
 
-    acc = alternate({'engine image': engine_image, 'stock image': stock_image, 'engine text': engine_text, 'stock text': stock_text,
-                     'engine scorer': engine_score, 'stock scorer': stock_score}, args.calls)
+    fns = {'engine image': engine_image, 'stock image': stock_image, 'engine text': engine_text, 'stock text': stock_text,
+           'engine scorer': engine_score, 'stock scorer': stock_score}
+    if scorer32 is not None:
+        fns['engine-fp32 image'] = lambda: scorer32.image.raw(images_d)
+        fns['engine-fp32 text'] = lambda: scorer32.text.raw(tokens)
+    acc = alternate(fns, args.calls)
     torch.cuda.synchronize()
     rel = lambda a, b: float((a - b).abs().max() / b.abs().max())
     say(f'agreement engine vs stock (max |a - b| / max |b|): image features {rel(out["ei"], out["si"]):.2e}, text features '
@@ -140,6 +147,10 @@ def main():
         me, ms_ = statistics.median(acc[f'engine {what}']), statistics.median(acc[f'stock {what}'])
         say(f'{what:7s} engine {fmt(acc["engine " + what])}  {B / me * 1e3:9.1f} {unit}  {fl * B / me / 1e9:7.1f} TFLOP/s (algorithmic)')
         say(f'{what:7s} stock  {fmt(acc["stock " + what])}  {B / ms_ * 1e3:9.1f} {unit}  {fl * B / ms_ / 1e9:7.1f} TFLOP/s   engine / stock time {me / ms_:.3f}')
+    if scorer32 is not None:
+        for what in ('image', 'text'):
+            me, m32 = statistics.median(acc[f'engine {what}']), statistics.median(acc[f'engine-fp32 {what}'])
+            say(f'{what:7s} engine fp32 mode {fmt(acc["engine-fp32 " + what])}   {args.dtype} / fp32 time {me / m32:.3f}')
     say()
     say('per-launch, image tower (one replay, an event pair per launch):')
     launch_table(scorer.image.plan(B), say)
