@@ -31,6 +31,18 @@ class DsmGemmSplitArgs(C.Structure):
                 ('bias', vp), ('res', vp), ('res_ld', C.c_int), ('act', C.c_int), ('out', vp), ('out_ld', C.c_int), ('reserved', C.c_int * 3)]
 
 
+class DsmFirArgs(C.Structure):
+    """dsm_fir_args: out = (fir(x) + bias + res) * out_scale, fir = the depthwise 4-tap down (up = 0; pad 0 / 1) or up (up = 1, pad = 1) filter."""
+    _fields_ = [('x', vp), ('ld_x', C.c_int), ('n', C.c_int), ('h', C.c_int), ('w', C.c_int), ('c', C.c_int), ('up', C.c_int), ('pad', C.c_int),
+                ('taps', C.c_float * 4), ('bias', vp), ('res', vp), ('res_ld', C.c_int), ('out_scale', C.c_float), ('out', vp),
+                ('out_ld', C.c_int), ('reserved', C.c_int * 3)]
+
+
+class DsmZeroBorderArgs(C.Structure):
+    """The by-value arguments of dsm_zero_border as a record (tools/plan_dump.py reads launches field by field)."""
+    _fields_ = [('x', vp), ('out', vp), ('outer', C.c_longlong), ('h', C.c_int), ('w', C.c_int), ('inner', C.c_int), ('p', C.c_int)]
+
+
 _SIGNATURES = {
     'dsm_version': (C.c_int, []),
     'dsm_error_string': (C.c_char_p, [C.c_int]),
@@ -49,6 +61,9 @@ _SIGNATURES = {
     'dsm_resize_crop_u8': (C.c_int, [vp, C.c_longlong, C.c_int] + [C.c_int] * 8 + [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]),
     'dsm_gemm_split': (C.c_int, [C.POINTER(DsmGemmSplitArgs), vp]),
     'dsm_gemm_split_supported': (C.c_int, [C.c_longlong, C.c_int, C.c_int]),
+    'dsm_fir_resample': (C.c_int, [C.POINTER(DsmFirArgs), vp]),
+    'dsm_fir_resample_supported': (C.c_int, [C.c_int] * 5),
+    'dsm_zero_border': (C.c_int, [vp, vp, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

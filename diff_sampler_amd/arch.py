@@ -9,9 +9,10 @@ resampling, attention heads and the *reference state_dict key prefix* its
 weights live under, so that a pickled EDM network (or a random-init one with the
 same key names) can be bound by name.
 
-Only what the BASELINE configs use is described: DDPM++ (``embedding_type=
-'positional'``, ``encoder_type='standard'``, ``decoder_type='standard'``,
-``resample_filter=[1,1]``) and ADM.  NCSN++ options raise NotImplementedError.
+Described: both SongUNet families of the published EDM checkpoints -- DDPM++ (``embedding_type='positional'``,
+``encoder_type='standard'``, ``resample_filter=[1,1]``, ``channel_mult_noise=1``) and NCSN++ (``'fourier'``,
+``'residual'``, ``[1,3,3,1]``, ``channel_mult_noise=2``), the four options independently of each other -- and ADM.
+``encoder_type='skip'``, ``decoder_type='skip'`` and other filters raise NotImplementedError (no EDM checkpoint uses them).
 """
 from __future__ import annotations
 
@@ -25,7 +26,7 @@ import torch
 @dataclass
 class BlockSpec:
     name: str                 # e.g. 'enc.16x16_block0'
-    kind: str                 # 'conv' (plain 3x3 stem) | 'block' (UNetBlock)
+    kind: str                 # 'conv' (plain 3x3 stem) | 'block' (UNetBlock) | 'aux' (enc.RxR_aux_residual: cin = caux, right after enc.RxR_down)
     cin: int
     cout: int
     res_in: int               # spatial size of the block input
@@ -65,6 +66,15 @@ class UNetSpec:
     sigma_min: float = 0.002
     sigma_max: float = 80.0
     use_fp16: bool = False
+    # SongUNet variants (networks_edm.py:237-241)
+    embedding_type: str = 'positional'  # 'positional' | 'fourier' (FourierEmbedding: a `map_noise.freqs` buffer in the state dict)
+    encoder_type: str = 'standard'      # 'standard' | 'residual' ('aux' entries in `blocks`)
+    resample_filter: Tuple[int, ...] = (1, 1)      # (1, 1) | (1, 3, 3, 1): the 1-D taps of every up / down block (and of the aux layers)
+
+    @property
+    def ncsnpp(self) -> bool:
+        """Does the network use any NCSN++ option (plans with launches outside libdsamd; fp32 only)?"""
+        return self.embedding_type != 'positional' or self.encoder_type != 'standard' or tuple(self.resample_filter) != (1, 1)
 
     @property
     def enc(self) -> List[BlockSpec]:
@@ -82,10 +92,15 @@ def song_unet_spec(
     channel_mult_noise=1, encoder_type='standard', decoder_type='standard',
     resample_filter=(1, 1),
 ) -> UNetSpec:
-    """DDPM++ layer list; mirrors the construction order of networks_edm.py:260-310."""
-    if embedding_type != 'positional' or encoder_type != 'standard' or decoder_type != 'standard' \
-            or list(resample_filter) != [1, 1]:
-        raise NotImplementedError('only the DDPM++ variant of SongUNet (positional/standard/standard/[1,1]) is supported')
+    """DDPM++ / NCSN++ layer list; mirrors the construction order of networks_edm.py:260-310."""
+    if embedding_type not in ('positional', 'fourier'):
+        raise ValueError(f'unknown embedding_type {embedding_type!r}')
+    if encoder_type not in ('standard', 'residual') or decoder_type != 'standard':
+        raise NotImplementedError(f'SongUNet encoder_type={encoder_type!r} / decoder_type={decoder_type!r}: only the standard and the residual '
+                                  f'encoder and the standard decoder are supported (no EDM checkpoint uses the skip variants)')
+    resample_filter = tuple(int(v) for v in resample_filter)
+    if resample_filter not in ((1, 1), (1, 3, 3, 1)):
+        raise NotImplementedError(f'SongUNet resample_filter={list(resample_filter)}: only [1,1] and [1,3,3,1] are supported')
     emb_channels = model_channels * channel_mult_emb
     noise_channels = model_channels * channel_mult_noise
     spec = UNetSpec(
@@ -93,10 +108,10 @@ def song_unet_spec(
         label_dim=label_dim, augment_dim=augment_dim, model_channels=model_channels, emb_channels=emb_channels,
         noise_channels=noise_channels, pos_endpoint=True, pos_max_positions=10000, swap_sincos=True,
         out_norm=f'dec.{img_resolution}x{img_resolution}_aux_norm', out_conv=f'dec.{img_resolution}x{img_resolution}_aux_conv',
-        out_eps=1e-6,
+        out_eps=1e-6, embedding_type=embedding_type, encoder_type=encoder_type, resample_filter=resample_filter,
     )
     common = dict(skip_scale=math.sqrt(0.5), eps=1e-6, adaptive_scale=False)
-    cout = in_channels
+    cout = caux = in_channels
     skips: List[int] = []
     for level, mult in enumerate(channel_mult):
         res = img_resolution >> level
@@ -106,6 +121,11 @@ def song_unet_spec(
         else:
             spec.blocks.append(BlockSpec(f'enc.{res}x{res}_down', 'block', cout, cout, res * 2, res, down=True,
                                          skip_conv=True, pushes_skip=True, **common))
+            if encoder_type == 'residual':
+                # x = skips[-1] = aux = (x + aux_residual(aux)) / sqrt(2)  (networks_edm.py:283, :335): replaces the down block's skip entry
+                spec.blocks.append(BlockSpec(f'enc.{res}x{res}_aux_residual', 'aux', caux, cout, res * 2, res, down=True,
+                                             skip_scale=math.sqrt(0.5)))
+                caux = cout
         skips.append(cout)
         for idx in range(num_blocks):
             cin, cout = cout, model_channels * mult
@@ -209,6 +229,19 @@ NAMED_CONFIGS: Dict[str, dict] = {
                    model_channels=128, channel_mult=[1, 2, 2, 2], dropout=0.05, augment_dim=9),
     'imagenet64': dict(img_resolution=64, img_channels=3, label_dim=1000, model_type='DhariwalUNet',
                        model_channels=192, channel_mult=[1, 2, 3, 4]),
+    # NCSN++ ('-ve' checkpoints: edm-cifar10-32x32-{uncond,cond}-ve, edm-ffhq-64x64-uncond-ve, edm-afhqv2-64x64-uncond-ve).  These
+    # hyper-parameters are quoted from memory of the published EDM training script, which is not in the reference tree: the
+    # architecture options are the ones networks_edm.py:237-241 names for NCSN++, dropout and augment_dim are those of the DDPM++
+    # entries above.  A real pickle does not depend on them: it goes through engine.spec_from_module.
+    'cifar10_ve': dict(img_resolution=32, img_channels=3, label_dim=0, model_type='SongUNet', embedding_type='fourier',
+                       encoder_type='residual', decoder_type='standard', channel_mult_noise=2, resample_filter=[1, 3, 3, 1],
+                       model_channels=128, channel_mult=[2, 2, 2], dropout=0.13, augment_dim=9),
+    'ffhq_ve': dict(img_resolution=64, img_channels=3, label_dim=0, model_type='SongUNet', embedding_type='fourier',
+                    encoder_type='residual', decoder_type='standard', channel_mult_noise=2, resample_filter=[1, 3, 3, 1],
+                    model_channels=128, channel_mult=[1, 2, 2, 2], dropout=0.05, augment_dim=9),
+    'afhqv2_ve': dict(img_resolution=64, img_channels=3, label_dim=0, model_type='SongUNet', embedding_type='fourier',
+                      encoder_type='residual', decoder_type='standard', channel_mult_noise=2, resample_filter=[1, 3, 3, 1],
+                      model_channels=128, channel_mult=[1, 2, 2, 2], dropout=0.05, augment_dim=9),
     # Reduced nets used by the parity tests (same code paths, seconds on CPU).
     'tiny_song': dict(img_resolution=16, img_channels=3, label_dim=0, model_type='SongUNet', model_channels=32,
                       channel_mult=[1, 2], num_blocks=1, attn_resolutions=[8], augment_dim=9),
@@ -219,6 +252,13 @@ NAMED_CONFIGS: Dict[str, dict] = {
                            channel_mult=[1, 2], num_blocks=4, attn_resolutions=[8], augment_dim=9),
     'tiny_song_amed_cond': dict(img_resolution=16, img_channels=3, label_dim=10, model_type='SongUNet', model_channels=32,
                                 channel_mult=[1, 2], num_blocks=4, attn_resolutions=[8], augment_dim=0),
+    # reduced NCSN++ nets: three levels, so that the second aux layer -- whose input is the previous level's aux, not the image -- exists
+    'tiny_ncsnpp': dict(img_resolution=32, img_channels=3, label_dim=0, model_type='SongUNet', embedding_type='fourier',
+                        encoder_type='residual', channel_mult_noise=2, resample_filter=[1, 3, 3, 1], model_channels=32,
+                        channel_mult=[1, 2, 2], num_blocks=1, attn_resolutions=[16], augment_dim=9),
+    'tiny_ncsnpp_cond': dict(img_resolution=32, img_channels=3, label_dim=10, model_type='SongUNet', embedding_type='fourier',
+                             encoder_type='residual', channel_mult_noise=2, resample_filter=[1, 3, 3, 1], model_channels=32,
+                             channel_mult=[1, 2, 2], num_blocks=1, attn_resolutions=[16], augment_dim=0),
     'tiny_adm': dict(img_resolution=16, img_channels=3, label_dim=10, model_type='DhariwalUNet', model_channels=64,
                      channel_mult=[1, 2], num_blocks=1, attn_resolutions=[8]),
 }
@@ -248,6 +288,8 @@ def param_table(spec: UNetSpec) -> List[Tuple[str, Tuple[int, ...], tuple]]:
     keys: list = []
     m = 'model'
     if spec.model_type == 'SongUNet':
+        if spec.embedding_type == 'fourier':       # a registered buffer of FourierEmbedding (networks_edm.py:207): first in the state dict
+            keys.append((f'{m}.map_noise.freqs', (spec.noise_channels // 2,), ('fourier', 16.0)))
         if spec.label_dim:
             _linear(keys, f'{m}.map_label', spec.label_dim, spec.noise_channels)
         if spec.augment_dim:
@@ -263,7 +305,7 @@ def param_table(spec: UNetSpec) -> List[Tuple[str, Tuple[int, ...], tuple]]:
             _linear(keys, f'{m}.map_label', spec.label_dim, spec.emb_channels, bias=False)
     for b in spec.blocks:
         p = f'{m}.{b.name}'
-        if b.kind == 'conv':
+        if b.kind in ('conv', 'aux'):
             _conv(keys, p, b.cin, b.cout, 3)
             continue
         _gn(keys, f'{p}.norm0', b.cin)
@@ -297,13 +339,21 @@ def init_params(spec: UNetSpec, seed: int = 0, mode: str = 'signal') -> Dict[str
         benchmark use this mode.
     mode='reference': the distributions of the reference initialisers (xavier_uniform / kaiming_uniform with
         the init_weight multipliers) — same statistics, not the same random stream.
+    The NCSN++ tensors (``map_noise.freqs`` ~ N(0, 16^2) in both modes, networks_edm.py:207; the ``aux_residual`` layers) are drawn from
+    a generator of their own: every other tensor of a network keeps the bits it has without them.
     """
-    g = torch.Generator(device='cpu').manual_seed(int(seed))
+    g_main = torch.Generator(device='cpu').manual_seed(int(seed))
+    g_ncsnpp = torch.Generator(device='cpu').manual_seed(int(seed) + 0x4e43534e)
     out: Dict[str, torch.Tensor] = {}
     song = spec.model_type == 'SongUNet'
+    if mode not in ('signal', 'reference'):
+        raise ValueError(mode)
     for key, shape, rule in param_table(spec):
         kind = rule[0]
-        if mode == 'signal':
+        g = g_ncsnpp if (kind == 'fourier' or '_aux_residual.' in key) else g_main
+        if kind == 'fourier':
+            t = torch.randn(shape, generator=g) * rule[1]
+        elif mode == 'signal':
             if kind in ('conv', 'linear'):
                 t = torch.randn(shape, generator=g) * (1.0 / math.sqrt(rule[1]))
             elif kind in ('conv_bias', 'linear_bias', 'zeros'):
@@ -346,6 +396,9 @@ def flops_per_image(spec: UNetSpec) -> float:
         hw = b.res_out * b.res_out
         if b.kind == 'conv':
             f += 2.0 * hw * 9 * b.cin * b.cout
+            continue
+        if b.kind == 'aux':         # the fused down form: the 3x3 runs at (res_in + 2)^2 (conv2d(padding=2), networks_edm.py:71)
+            f += 2.0 * (b.res_in + 2) ** 2 * 9 * b.cin * b.cout
             continue
         f += 2.0 * hw * 9 * b.cin * b.cout + 2.0 * hw * 9 * b.cout * b.cout
         f += 2.0 * spec.emb_channels * b.cout * (2 if b.adaptive_scale else 1)

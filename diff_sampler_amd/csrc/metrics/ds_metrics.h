@@ -5,6 +5,9 @@
  * resize and crop in front of it -- csrc/metrics/image_prep.hip (added without a version step: nothing existing changed).
  * Third part (at the end; again without a version step): dsm_gemm_split -- csrc/metrics/gemm_split.hip, the Linear layer of the towers' fp16x3
  * mode: fp32 operands and fp32 results, every product as three fp16 products (split hi / lo halves) on the fp16 matrix pipe.
+ * Fourth part (after it; no version step either): dsm_fir_resample / dsm_zero_border -- csrc/metrics/fir_resample.hip, the two launches the
+ * NCSN++ denoisers need beyond libdsamd.so.  They are no metric; they live here because a declaration in a header of csrc/ or include/ enters every
+ * source hash of the engine (tile table, profile ties), and this library is where every kernel since those were pinned has gone.
  *
  * Precision / recall / density / coverage and per-sample realism (sfd-main/prdc.py) on detector features.  Features are
  * [n][ld] row-major with ld >= dim, fp32 (widened exactly) or fp64 chosen by a flag per operand; all arithmetic is fp64.
@@ -153,6 +156,42 @@ typedef struct dsm_gemm_split_args {
 
 DSM_API int dsm_gemm_split(const dsm_gemm_split_args* a, void* stream);
 DSM_API int dsm_gemm_split_supported(long long rows, int k, int cout);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------------
+ * FIR resampling of the NCSN++ networks (csrc/metrics/fir_resample.hip; added without a version step: nothing existing changed): the
+ * depthwise forms of the reference's Conv2d.forward (networks_edm.py:56-82) for a separable 4-tap resample_filter, on fp32 NHWC rows
+ * x [n * h * w][ld_x] -> out [n * ho * wo][out_ld], columns [c, ld) neither read nor written.
+ *
+ *     f2d[i][j] = taps[i] taps[j] / (sum taps)^2                                   (formed in fp32, as the reference's buffer is)
+ *     down:  fir[y, x] = sum_{i, j < 4} f2d[i][j] x[2y + i - pad, 2x + j - pad]     zero outside the image, not renormalised at the border;
+ *            ho = (h + 2 pad - 4) / 2 + 1 (likewise wo); pad = 1: conv2d(stride 2, padding 1); pad = 0: the second half of fused_resample
+ *     up:    fir[Y, X] = sum 4 f2d[i][j] x[y, x] over Y = 2y + i - 1, X = 2x + j - 1   conv_transpose2d(4 f2d, stride 2, padding 1); ho = 2h
+ *     out[m, ch] = (fir + bias[ch] + res[m, ch]) * out_scale                         bias [c] and res [n * ho * wo][res_ld] may be NULL
+ *
+ * One fp32 FMA per tap in a fixed order (16 down, 4 up), then the epilogue's three operations.  res may be `out` itself (element-wise).
+ * DS_E_ARG: NULL a / x / out, x == out, n, h, w or c <= 0, up not 0 / 1, pad not 0 / 1 (up: not 1), ld_x < c, out_ld < c, res_ld < c (with res),
+ * taps whose sum is zero or not finite, a non-zero reserved field;  DS_E_ALIGN: c, ld_x, out_ld or res_ld (with res) not a multiple of 4, a
+ * pointer not 16-byte aligned;  DS_E_SHAPE: down with h + 2 pad - 4 or w + 2 pad - 4 negative or odd, more than 2^31 - 1 rows.
+ * dsm_fir_resample_supported(up, pad, h, w, c): 1 where a call of this geometry launches (host logic only). */
+typedef struct dsm_fir_args {
+    const float* x; int ld_x;
+    int n, h, w, c;          /* the INPUT geometry */
+    int up;                  /* 0 = down (stride 2), 1 = up (x 2) */
+    int pad;
+    float taps[4];
+    const float* bias; const float* res; int res_ld;
+    float out_scale;
+    float* out; int out_ld;
+    int reserved[3];         /* must be 0 */
+} dsm_fir_args;
+
+DSM_API int dsm_fir_resample(const dsm_fir_args* a, void* stream);
+DSM_API int dsm_fir_resample_supported(int up, int pad, int h, int w, int c);
+
+/* out [outer][h + 2p][w + 2p][inner] = x [outer][h][w][inner] inside a ring of p zeros (NHWC: outer = n, inner = c; channel-planar: outer = n c,
+ * inner = 1).  Whole 16-byte quads when inner is a multiple of 4 (pointers 16-byte aligned then, else 4-byte: DS_E_ALIGN).  DS_E_ARG: NULL
+ * pointer, x == out, a non-positive size, p < 0;  DS_E_SHAPE: a side or p above 32768, more than 2^31 - 1 output pixels. */
+DSM_API int dsm_zero_border(const float* x, float* out, long long outer, int h, int w, int inner, int p, void* stream);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,7 @@ import os
 from types import SimpleNamespace
 from typing import Dict
 
+import numpy as np
 import torch
 
 from . import _lib, arch
@@ -58,6 +59,12 @@ class UNetEngine:
         q / k / v and the embedding path are fp32.  DESIGN.md section 2 states the bounds, tests/test_hip_fp16.py enforces them."""
         self.spec = spec
         self.device = torch.device(device)
+        if spec.ncsnpp and (use_fp16 or split_fp16 or batch_invariant):
+            # the FIR resampler and the aux-residual pyramid (csrc/metrics/fir_resample.hip) are fp32 launches outside libdsamd: no fp16
+            # storage form, no split-fp16 convolution and no batch-invariant route is defined for them (DESIGN.md section 9)
+            raise NotImplementedError('NCSN++ options (fourier embedding / residual encoder / [1,3,3,1] filter) run in the exact fp32 mode only: '
+                                      'use_fp16, split_fp16 and batch_invariant are not supported with them')
+        self.fir = tuple(spec.resample_filter) != (1, 1)      # up / down blocks resample through dsm_fir_resample, not ds_norm_act
         self.use_fp16 = bool(use_fp16)
         self.split_fp16 = bool(split_fp16) and not self.use_fp16
         self.batch_invariant = bool(batch_invariant)
@@ -84,7 +91,10 @@ class UNetEngine:
         freqs = torch.arange(0, half, dtype=torch.float32)
         freqs = freqs / (half - (1 if spec.pos_endpoint else 0))
         freqs = (1 / spec.pos_max_positions) ** freqs            # exactly networks_edm.py:193-195, on the host
-        w['freqs'] = freqs.to(dev)
+        if spec.embedding_type == 'fourier':                     # FourierEmbedding: the reference's own expression on its fp32 buffer (networks_edm.py:210)
+            freqs = (2 * np.pi * params[f'{m}.map_noise.freqs'].detach().to(device='cpu', dtype=torch.float32)).to(torch.float32)
+            assert freqs.shape == (half,), (tuple(freqs.shape), half)
+        w['freqs'] = freqs.contiguous().to(dev)
         w['map0.w'] = pack_linear_weight(g(f'{m}.map_layer0.weight')); w['map0.b'] = g(f'{m}.map_layer0.bias')
         w['map1.w'] = pack_linear_weight(g(f'{m}.map_layer1.weight')); w['map1.b'] = g(f'{m}.map_layer1.bias')
         if spec.label_dim:
@@ -111,11 +121,15 @@ class UNetEngine:
             if b.kind == 'conv':
                 w[f'{b.name}.w'] = pack_stem_weight(g(f'{p}.weight')); w[f'{b.name}.b'] = g(f'{p}.bias')
                 continue
+            if b.kind == 'aux':      # the first aux layer reads the network input through ds_stem_im2col, like the stem
+                pack = pack_stem_weight if b.res_in == spec.img_resolution else pack_conv_weight
+                w[f'{b.name}.w'] = pack(g(f'{p}.weight')); w[f'{b.name}.b'] = g(f'{p}.bias')
+                continue
             for leaf in ('norm0', 'norm1'):
                 w[f'{b.name}.{leaf}.g'] = g(f'{p}.{leaf}.weight'); w[f'{b.name}.{leaf}.b'] = g(f'{p}.{leaf}.bias')
             w[f'{b.name}.conv0.w'] = pack_conv_weight(g(f'{p}.conv0.weight')); w[f'{b.name}.conv0.b'] = g(f'{p}.conv0.bias')
             w[f'{b.name}.conv1.w'] = pack_conv_weight(g(f'{p}.conv1.weight')); w[f'{b.name}.conv1.b'] = g(f'{p}.conv1.bias')
-            if self.up_phase and b.up and b.cin % 32 == 0:
+            if self.up_phase and b.up and b.cin % 32 == 0 and not self.fir:
                 w[f'{b.name}.conv0.wup'] = pack_conv_weight_up2(g(f'{p}.conv0.weight'))      # the four folded phase matrices, once per build
             if self.winograd and b.cin % 32 == 0 and b.cout % 256 == 0:
                 # Winograd-transformed weights, once per build (a fused skip projection's 1x1 columns follow them untransformed)
@@ -176,9 +190,15 @@ class UNetEngine:
         # (values are widened when loaded).  Otherwise the stream stays fp32 (the mixed layout of smaller / unusual geometries).
         P.stream16 = ws.stream16 = self.conv_mode == 1 and all(self._dma16(bd, B, b) for b in spec.blocks if b.kind == 'block')
         P.f16_views = []          # (address, bytes) of fp32-typed storage that some launches use as fp16 rows (tests/test_plan_cpu.py's dtype lint)
-        x_cur, skips = None, []
+        x_cur, skips, aux = None, [], None
         for b in spec.blocks:
             nm, Ho, cout = b.name, b.res_out, b.cout
+            if b.kind == 'aux':
+                # x = skips[-1] = aux = (x + aux_residual(aux)) / sqrt(2)  (networks_edm.py:335): the down block's own output stays in bufs
+                out = self._aux_residual(bd, ws, b, aux, x_cur[0])
+                x_cur = aux = skips[-1] = (out, cout)
+                bufs[nm] = out
+                continue
             if b.kind == 'conv':
                 bd.add(lib.ds_stem_im2col, (_ptr(bufs['x']), _ptr(bufs['sigma']), Bs, spec.sigma_data, B, spec.in_channels, R, R,
                                             _ptr(ws.act), kpad), 'stem_im2col')
@@ -224,6 +244,9 @@ class UNetEngine:
         ws = SimpleNamespace(B=B, Bs=Bs, max_h=max_h, dec_pp=[None, None], dec_i=0)
         ws.act, ws.hbuf = new(B * max_act), new(B * max_h)
         ws.sres = new(B * max_h)            # resampled skip-path input
+        if self.fir:                        # FIR-resampled activated tensor (conv0's input); norm0 of a down block writes ws.act at the INPUT size
+            assert max_act >= max(b.cin * b.res_in ** 2 for b in spec.blocks if b.kind == 'block')
+            ws.fir = new(B * max_act)
         ws.sproj = new(B * max_h)           # projected skip
         bd.coefs = new(B * 3 * max(max(b.cin, b.cout) for b in spec.blocks))      # {mu, A, B} planes of the fused GroupNorm
         if self.conv_mode == 1:          # fp16 activated tensors: norm0 output, norm1 output, raw copy for the fused skip projection, conv0 output
@@ -361,7 +384,19 @@ class UNetEngine:
             fuse = False        # fp16 operands without the fused normalisation (8x8: four images per tile): normalise in a pass
         conv0 = dict(bias=w[f'{nm}.conv0.b'], stats=True, w16=w16_0, **cb)      # (+ per-image embedding for the non-adaptive variant)
         wup = w.get(f'{nm}.conv0.wup') if b.up and w16_0 is None else None
-        if wup is not None and bd.up2_ok(ws.act, cin, cin, n, Ho, Ho, wup, cout, ws.hbuf, cout, **conv0):
+        if self.fir and rs != DS_RESAMPLE_NONE:
+            # resample_filter [1,3,3,1] (networks_edm.py:74-79): activate at the input size, filter (x2 up / stride-2 down, padding 1), convolve
+            assert x1 is None and c0 == cin
+            M = n * Ho * Ho
+            act, rsd = ws.act[:n * Hin * Hin * cin].view(-1, cin), ws.fir[:M * cin].view(M, cin)
+            bd.norm('stats', x0, c0, c0, n, Hin, Hin, nm + '.norm0.stats', groups=G_in, eps=b.eps)
+            bd.norm('apply', x0, c0, c0, n, Hin, Hin, nm + '.norm0', groups=G_in, eps=b.eps, gamma=w[f'{nm}.norm0.g'], beta=w[f'{nm}.norm0.b'],
+                    act=DS_ACT_SILU, resample=DS_RESAMPLE_NONE, out=act, out_ld=cin)
+            bd.fir_resample(act, cin, n, Hin, Hin, cin, rsd, cin, nm + '.conv0.fir', up=b.up, taps=self.spec.resample_filter)
+            kw0 = dict(conv0)
+            w0 = self._wino_pick(bd, rsd, cin, cin, n, Ho, w[f'{nm}.conv0.w'], w.get(f'{nm}.conv0.wwino'), cout, ws.hbuf, kw0)
+            bd.conv(rsd, cin, cin, n, Ho, Ho, w0, cout, ws.hbuf, cout, 9, nm + '.conv0', **kw0)
+        elif wup is not None and bd.up2_ok(ws.act, cin, cin, n, Ho, Ho, wup, cout, ws.hbuf, cout, **conv0):
             # up block: the pass activates at the input resolution and the convolution reads it through the x2 upsampling (four 2x2 phase
             # convolutions on the low-res rows); the launches are those of the other route, the upsampled tensor is never written
             bd.norm('stats', x0, c0, c0, n, Hin, Hin, nm + '.norm0.stats', groups=G_in, eps=b.eps, **src)
@@ -393,13 +428,42 @@ class UNetEngine:
             c1_in, kw = ws.act, {}
         # skip path: raw (resampled) input, projected by a 1x1 that is fused into conv1 as extra K columns
         s0, sc0, s1, sc1 = x0, c0, x1, c1
-        if rs != DS_RESAMPLE_NONE:
+        if self.fir and rs != DS_RESAMPLE_NONE:
+            bd.fir_resample(x0, c0, n, Hin, Hin, cin, ws.sres, cin, nm + '.skip.fir', up=b.up, taps=self.spec.resample_filter)
+            s0, sc0, s1, sc1 = ws.sres, cin, None, 0
+        elif rs != DS_RESAMPLE_NONE:
             bd.norm('apply', x0, c0, c0, n, Hin, Hin, nm + '.skip.resample', use_stats=False, resample=rs, out=ws.sres, out_ld=cin, **src)
             s0, sc0, s1, sc1 = ws.sres, cin, None, 0
         if b.skip_conv:
             return c1_in, w[f'{nm}.conv1s.w'], dict(kw, bias=w[f'{nm}.conv1s.b'], e0=s0, ec0=sc0, e1=s1, ec1=sc1)
         assert s1 is None and sc0 == cout
         return c1_in, w[f'{nm}.conv1.w'], dict(kw, bias=w[f'{nm}.conv1.b'], res=s0, res_ld=cout)
+
+    def _aux_residual(self, bd, ws, b, aux, x):
+        """enc.RxR_aux_residual (networks_edm.py:283, :335; Conv2d.forward's fused down form, :70-72): conv2d(aux, w, padding=2) as the padding-1
+        3x3 convolution on the zero-ringed input (its ring of outputs is computed, not zero), then ONE launch for the stride-2 [1,3,3,1]
+        filter, the layer's bias, the down block's output `x` and the 1/sqrt(2).  aux None: the network input c_in x (channel-planar), read
+        through ds_stem_im2col like the stem; else (tensor, channels) of the previous level's aux in NHWC rows."""
+        spec, w, nm, n, R, cout = self.spec, self.w, b.name, ws.B, b.res_in, b.cout
+        Rp, bufs = R + 2, bd.P.bufs
+        conv = bd.new(n * Rp * Rp, cout)
+        if aux is None:
+            kpad = -(-9 * spec.in_channels // 32) * 32
+            ring, cols = bd.new(n, spec.in_channels, Rp, Rp), bd.new(n * Rp * Rp, kpad)
+            bd.zero_border(bufs['x'], ring, n * spec.in_channels, R, R, 1, 1, nm + '.ring')
+            bd.add(self.lib.ds_stem_im2col, (_ptr(ring), _ptr(bufs['sigma']), ws.Bs, spec.sigma_data, n, spec.in_channels, Rp, Rp, _ptr(cols), kpad),
+                   nm + '.im2col')
+            bd.conv(cols, kpad, kpad, n, Rp, Rp, w[f'{nm}.w'], cout, conv, cout, 1, nm + '.conv')
+        else:
+            t, caux = aux
+            assert caux == b.cin
+            ring = bd.new(n * Rp * Rp, caux)
+            bd.zero_border(t, ring, n, R, R, caux, 1, nm + '.ring')
+            bd.conv(ring, caux, caux, n, Rp, Rp, w[f'{nm}.w'], cout, conv, cout, 9, nm + '.conv')
+        out = bd.new(n * b.res_out ** 2, cout)
+        bd.fir_resample(conv, cout, n, Rp, Rp, cout, out, cout, nm + '.fir', pad=0, taps=spec.resample_filter, bias=w[f'{nm}.b'], res=x, res_ld=cout,
+                        scale=b.skip_scale)
+        return out
 
     def _block_out(self, bd, ws, b, f16):
         """Output buffer of a block (and of its attention): encoder outputs are kept for the skip stack, decoder outputs ping-pong between two
@@ -640,6 +704,22 @@ def spec_from_module(net) -> arch.UNetSpec:
     levels = sorted({int(k.split('x')[0]) for k in names}, reverse=True)
     num_blocks = sum(1 for k in blocks if k.startswith(f'{res0}x{res0}_block'))
     if song:
+        # the three NCSN++ options are recovered from what they leave in the tree (networks_edm.py:261, :279-284, :56-58); the encoder /
+        # decoder variants the engine does not evaluate are refused here -- their layers would otherwise be dropped without a word
+        every = [f'enc.{k}' for k in names] + [f'dec.{k}' for k in model.dec.keys()]
+        odd = [k for k in every if any(t in k for t in ('aux_down', 'aux_skip', 'aux_up'))]
+        if odd:
+            raise NotImplementedError(f'SongUNet with encoder_type / decoder_type "skip" is not supported (layers {odd[:3]} ...)')
+        fourier = getattr(getattr(model, 'map_noise', None), 'freqs', None) is not None
+        residual = any('aux_residual' in k for k in names)
+        taps = [1, 1]
+        for k in names:
+            f = getattr(getattr(model.enc[k], 'conv0', None), 'resample_filter', None) if k.endswith('_down') else None
+            if f is not None:
+                if f.shape[-1] not in (2, 4):
+                    raise NotImplementedError(f'resample_filter of {tuple(f.shape)} in enc.{k}: only [1,1] and [1,3,3,1] are supported')
+                taps = [1, 1] if f.shape[-1] == 2 else [1, 3, 3, 1]
+                break
         model_channels = first.out_channels
         mult = [model.enc[f'{r}x{r}_block0'].out_channels // model_channels for r in levels]
         attn = [r for r in levels if getattr(model.enc[f'{r}x{r}_block0'], 'num_heads', 0)]
@@ -647,7 +727,9 @@ def spec_from_module(net) -> arch.UNetSpec:
                                    augment_dim=(model.map_augment.weight.shape[1] if getattr(model, 'map_augment', None) is not None else 0),
                                    model_channels=model_channels, channel_mult=mult, channel_mult_emb=mc_emb // model_channels,
                                    num_blocks=num_blocks, attn_resolutions=attn,
-                                   channel_mult_noise=model.map_layer0.weight.shape[1] // model_channels)
+                                   channel_mult_noise=model.map_layer0.weight.shape[1] // model_channels,
+                                   embedding_type='fourier' if fourier else 'positional', encoder_type='residual' if residual else 'standard',
+                                   resample_filter=taps)
     else:
         model_channels = model.map_layer0.weight.shape[1]
         mult = [model.enc[f'{r}x{r}_block0'].out_channels // model_channels for r in levels]

@@ -2,7 +2,8 @@
 
 A plan is compiled once per (network, batch size); running it is a tight ctypes loop, and because no pointer changes
 between runs it can be captured into a hipGraph (``graph.py``).  ``Builder`` is the small DSL the engines use to emit
-launches; it only marshals arguments -- every operation is a libdsamd kernel.  Two levels: one launch (``conv``, ``norm``,
+launches; it only marshals arguments -- every operation is a libdsamd kernel (or, for the NCSN++ networks, one of the two libdsmetrics
+launches of ``fir_resample`` / ``zero_border``: such a plan is ``foreign`` and runs through ``run_python``).  Two levels: one launch (``conv``, ``norm``,
 ``attention``, ...) and the blocks more than one network is made of (``gn_conv3x3``, ``upsample_conv``, ``widen``), which decide WHICH
 launches a block becomes and take their temporaries from the builder's recycling allocator (``alloc`` / ``free``); ``finish`` ends
 every plan build.
@@ -176,6 +177,7 @@ class Plan:
         self.bufs: Dict[str, torch.Tensor] = {}
         self.keep: List[torch.Tensor] = []      # every workspace tensor the launch arguments point into
         self._native = None                     # (ds_plan*, number of ops it was built from)
+        self.foreign = False                    # launches outside libdsamd in the list (Builder.fir_resample / zero_border): no native walk
 
     def run_python(self, stream):
         for op in self.ops:
@@ -191,6 +193,8 @@ class Plan:
         return self._native[0]
 
     def run(self, stream):
+        if self.foreign:                        # ds_plan_run walks libdsamd's own launches only (the NCSN++ plans; the CLIP-score towers do the same)
+            return self.run_python(stream)
         h = self.native()
         lib = _lib.load()
         rc = lib.ds_plan_run(h, stream)
@@ -200,6 +204,8 @@ class Plan:
 
     def graph_capture(self, stream):
         """Record one run into a hipGraph owned by the native plan (ds_plan_graph_capture; `stream` must not be the default stream)."""
+        if self.foreign:
+            raise _lib.DsError('a plan with launches outside libdsamd has no native hipGraph: capture the call through graph.GraphedSampler')
         _lib.check(_lib.load().ds_plan_graph_capture(self.native(), stream), 'ds_plan_graph_capture')
 
     def graph_launch(self, stream):
@@ -706,6 +712,29 @@ class Builder:
             raise NotImplementedError(f'{name}: no causal attention kernel for head size {d} over {s} tokens')
         a = AttnArgs(ptr(q), ptr(k), ptr(v), ptr(out), ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, batch, heads, s, s, d, scale)
         self.add(self.lib.ds_attention_causal, (C.byref(a),), name, keep=(a,))
+
+    # ---- launches of libdsmetrics (csrc/metrics/fir_resample.hip): the plan then runs through Plan.run_python -----------------------------
+    def fir_resample(self, x, ld_x, n, h, w, c, out, out_ld, name, up=False, pad=1, taps=(1, 3, 3, 1), bias=None, res=None, res_ld=0, scale=1.0):
+        """out = (fir(x) + bias + res) * scale over fp32 NHWC rows: the depthwise 4-tap filter `taps` as a stride-2 down (padding `pad`) or a
+        x2 up (dsm_fir_args; h, w = the INPUT size)."""
+        from . import _metrics_lib as ML
+        assert len(taps) == 4 and all(t.dtype == torch.float32 for t in (x, out)), name
+        a = ML.DsmFirArgs(ptr(x), ld_x, n, h, w, c, 1 if up else 0, pad, (C.c_float * 4)(*[float(t) for t in taps]), ptr(bias), ptr(res), res_ld,
+                          scale, ptr(out), out_ld)
+        mlib = ML.load()
+        if not mlib.dsm_fir_resample_supported(a.up, a.pad, h, w, c):
+            raise NotImplementedError(f'{name}: no FIR resampling kernel for up={a.up} pad={pad} on {h} x {w} x {c}')
+        self.stats_of.pop(out.data_ptr(), None)
+        self.P.foreign = True
+        self.add(mlib.dsm_fir_resample, (C.byref(a),), name, keep=(a,))
+
+    def zero_border(self, x, out, outer, h, w, inner, p, name):
+        """out [outer][h + 2p][w + 2p][inner] = x [outer][h][w][inner] inside a ring of zeros (dsm_zero_border)."""
+        from . import _metrics_lib as ML
+        assert x.dtype == out.dtype == torch.float32 and out.numel() >= outer * (h + 2 * p) * (w + 2 * p) * inner, name
+        self.stats_of.pop(out.data_ptr(), None)
+        self.P.foreign = True
+        self.add(ML.load().dsm_zero_border, (ptr(x), ptr(out), outer, h, w, inner, p), name)
 
     def token_embed(self, tokens, tok_table, pos_table, out, out_ld, batch, seq, width, vocab, name):
         assert tokens.dtype == torch.int32 and tokens.numel() == batch * seq, name

@@ -33,15 +33,16 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import torch  # noqa: E402
 
-from diff_sampler_amd import _lib  # noqa: E402
+from diff_sampler_amd import _lib, _metrics_lib  # noqa: E402
 
 WRITES = {'ds_conv2d_nhwc': ('out', 'stats_out'), 'ds_norm_act': ('out', 'raw_out'), 'ds_gn_stats': ('mean', 'rstd', 'coefs'),
           'ds_gn_finalize': ('mean', 'rstd', 'coefs'), 'ds_attention': ('out',), 'ds_attention_f16': ('out',), 'ds_gemm_nt_batched': ('c',),
           'ds_layernorm_rows': ('y',), 'ds_layernorm_rows_f16': ('y',), 'ds_layernorm_rows_f16io': ('y',), 'ds_geglu': ('y',),
-          'ds_noise_embed': ('out',), 'ds_stem_im2col': ('out',)}
+          'ds_noise_embed': ('out',), 'ds_stem_im2col': ('out',), 'dsm_fir_resample': ('out',), 'dsm_zero_border': ('out',)}
 SCRATCH = ('workspace', 'partial', 'counters', 'update')
 BY_VALUE = {'ds_layernorm_rows': _lib.LayerNormArgs, 'ds_layernorm_rows_f16': _lib.LayerNormArgs, 'ds_layernorm_rows_f16io': _lib.LayerNormArgs,
-            'ds_geglu': _lib.GegluArgs, 'ds_noise_embed': _lib.NoiseEmbedArgs, 'ds_stem_im2col': _lib.StemIm2colArgs}
+            'ds_geglu': _lib.GegluArgs, 'ds_noise_embed': _lib.NoiseEmbedArgs, 'ds_stem_im2col': _lib.StemIm2colArgs,
+            'dsm_zero_border': _metrics_lib.DsmZeroBorderArgs}        # (libdsmetrics launches of the NCSN++ plans)
 
 
 class DumpError(AssertionError):
@@ -109,7 +110,7 @@ def dump(engine, P):
                 if isinstance(v, C.Structure):
                     fields(v, f + '.')
                 elif ty is not C.c_void_p:
-                    row.append([prefix + f, repr(v)])
+                    row.append([prefix + f, repr(list(v) if isinstance(v, C.Array) else v)])
                 elif f in SCRATCH:
                     row.append([f, 'set' if v else 'null'])
                 elif not v:
@@ -205,9 +206,10 @@ def matrix(quick=False):
             jobs += [(v, B) for v in ('nodown', 'qkv32') for B in (1, 2, 16)]          # U-Net batches N = 2, 4, 32
     for kind, named in (('edm', arch.NAMED_CONFIGS), ('ldm', la.NAMED_LDM_CONFIGS)):
         for net in named:
-            for mode in (('fp32', 'fp16', 'split') if kind == 'edm' else ('fp32', 'fp16')):
+            ncsnpp = kind == 'edm' and arch.edm_precond_spec(**named[net]).ncsnpp       # exact fp32 only, no batch-invariant route
+            for mode in (('fp32',) if ncsnpp else ('fp32', 'fp16', 'split') if kind == 'edm' else ('fp32', 'fp16')):
                 if (kind, net, mode) not in m:
-                    m[(kind, net, mode)] = [(v, B) for v in ('-', 'inv') for B in (1, 2, 3, 4, 5)]
+                    m[(kind, net, mode)] = [(v, B) for v in (('-',) if ncsnpp else ('-', 'inv')) for B in (1, 2, 3, 4, 5)]
     for net in va.NAMED_VAE_CONFIGS:
         for mode in ('fp32', 'fp16'):
             m[('vae', net, mode)] = [(v, B) for v in ('-', 'inv') for B in (1, 2, 3, 4, 16)]
