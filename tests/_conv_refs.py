@@ -43,7 +43,7 @@ First order in U, times SECOND.  The selectors of a case visit every tap and eve
 width (32 channels; 64 for the fp16 families), both sources where there are two, and the appended columns (`selector_visits`); the
 thin-output kernel (at most four columns) needs several launches for that (`rounds`).
 The Winograd form has no family B: its input transform B^T d B rounds on real-valued data, so a selector does not isolate one term
-(tests/test_hip_wino*.py keep the randn comparison); DS_ACT_GEGLU stays with its own tests.
+(tests/test_hip_wino.py keeps the randn comparison of tests/_conv_randn.py); DS_ACT_GEGLU stays with its own tests.
 
 ds_gemm_nt_batched: GEMM_CASES with family-A data (exact) and, under SiLU, the family-B bound on integer operands
 (alpha * acc exact; + rowbias, + colbias: two roundings; SiLU).

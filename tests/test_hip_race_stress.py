@@ -64,6 +64,23 @@ def test_kernel_suites_pass_against_the_race_stress_library(tag):
     assert 'passed' in summary and 'failed' not in summary, summary
 
 
+# seconds.  The four children this one replaces took 17.8 s together on a warm box (profiles/wino_tests_merge.txt) under limits that summed
+# to 2700 s: 300 s is 17 times the former and a ninth of the latter, so that a cold box passes and a hung child costs five minutes
+WINO_CHILD_TIMEOUT = 300
+
+
+@pytest.mark.parametrize('tag', ['stress_a', 'stress_b'])
+def test_winograd_suite_passes_against_the_race_stress_library(tag):
+    """The whole of tests/test_hip_wino.py, unchanged, against a library whose LDS-producing waves are delayed (two complementary wave
+    masks): every producer of shared LDS contents in csrc/conv3x3_wino.hip is a DS_RACE_SKEW site."""
+    from diff_sampler_amd import build
+    lib = build.variant_lib(tag)
+    assert os.path.exists(lib), f'{lib} is missing: __graft_entry__.build() / python -m diff_sampler_amd.build --variants builds it'
+    assert ctypes.CDLL(lib).ds_build_experiments() & 2, 'not a DS_RACE_STRESS build'
+    summary = _run_suite(lib, ['tests/test_hip_wino.py'], timeout=WINO_CHILD_TIMEOUT)
+    assert 'passed' in summary and 'failed' not in summary and 'skipped' not in summary, summary
+
+
 def test_the_stress_build_catches_the_round5_race_when_it_is_reintroduced():
     """The detector detects: libdsamd_stress_g5.so = the mask-0x21 stress library with conv3x3_f16dma.hip's prologue barrier compiled OUT
     (-DDS_TEST_DROP_G5_BARRIER: exactly the round-5 bug -- coefficient rows fetched by wave 0, read by every wave).  Round 5's suite passed

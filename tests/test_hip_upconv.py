@@ -16,19 +16,13 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+
+import _conv_randn as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-TOL = 2e-5
-SCALE = 0.7071
-
-
-def _rel(a, b):
-    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-6))
-
-
-def _nhwc(x):      # [B,C,H,W] -> [B*H*W, C]
-    return x.permute(0, 2, 3, 1).reshape(-1, x.shape[1]).contiguous()
+TOL, SCALE, _rel, _nhwc = R.TOL, R.SCALE, R.rel, R.nhwc
 
 
 _CASES = {}
@@ -89,22 +83,10 @@ def test_upsampled_input_conv_matches_fp64(shape, mode, variant, want_kid):
     print(f'in_up2 {shape} kernel {kid}: rel err vs fp64 {err:.3e}')
     assert err < TOL
     # column sums: an image's h w / 64 blocks are contiguous (phase-major inside the image) and add up to the image's own sums
-    nb = H * H // 64
-    st = stats.cpu().reshape(B, nb, 2, cout).double()
-    img = got.double().reshape(B, H * H, cout)
-    assert _rel(st[:, :, 0].sum(1), img.sum(1)) < 1e-5 and _rel(st[:, :, 1].sum(1), (img ** 2).sum(1)) < 1e-5
+    e_s, e_q = R.column_sum_errors(got, stats.cpu(), B, H * H, cout)
+    assert e_s < 1e-5 and e_q < 1e-5
     # ... and ds_gn_finalize makes the consumer's GroupNorm statistics of them
-    G_ = 32
-    mean, rstd = torch.empty(B * G_, device=dev), torch.empty(B * G_, device=dev)
-    coefs = torch.empty(B * 3 * cout, device=dev)
-    gamma, beta = torch.ones(cout, device=dev), torch.zeros(cout, device=dev)
-    f = _lib.GnFinalizeArgs(stats.data_ptr(), None, cout, 0, B, H * H, G_, 1e-5, gamma.data_ptr(), beta.data_ptr(), None, None, 0, 1,
-                            mean.data_ptr(), rstd.data_ptr(), coefs.data_ptr())
-    assert lib.ds_gn_finalize(C.byref(f), _lib.stream_ptr()) == 0
-    torch.cuda.synchronize()
-    r = want.reshape(B, H * H, G_, cout // G_).permute(0, 2, 1, 3).reshape(B, G_, -1)
-    assert torch.allclose(mean.cpu(), r.mean(-1).float().reshape(-1), rtol=1e-4, atol=1e-5)
-    assert torch.allclose(rstd.cpu(), (1.0 / (r.var(-1, unbiased=False) + 1e-5).sqrt()).float().reshape(-1), rtol=1e-4, atol=1e-5)
+    R.finalize_check(lib, stats, want, B, H * H, cout)
 
 
 def test_refused_call_launches_nothing():
