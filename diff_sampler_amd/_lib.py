@@ -197,10 +197,15 @@ class CfgSigmaRowsArgs(C.Structure):
     _fields_ = [('sigma', vp), ('n', C.c_int), ('log_alpha', vp), ('m', C.c_int), ('copies', C.c_int), ('sigma_out', vp), ('c_noise_out', vp)]
 
 
+class AffineComposeArgs(C.Structure):
+    _fields_ = [('aff', vp), ('ld', C.c_int), ('rows', C.c_int), ('width', C.c_int), ('step', vp), ('pairs', vp), ('groups', C.c_int)]
+
+
 # ds_plan_add op codes (include/ds_engine.h)
 DS_OP_CONV2D, DS_OP_GEMM, DS_OP_GN_STATS, DS_OP_NORM_ACT, DS_OP_GN_FINALIZE, DS_OP_ATTENTION, DS_OP_ATTENTION_F16, DS_OP_LAYERNORM, \
     DS_OP_GEGLU, DS_OP_NOISE_EMBED, DS_OP_STEM_IM2COL, DS_OP_LAYERNORM_F16, DS_OP_LAYERNORM_F16IO, DS_OP_TOKEN_EMBED, \
     DS_OP_ATTENTION_CAUSAL, DS_OP_QUICK_GELU, DS_OP_CHANNEL_MEAN_F16, DS_OP_CFG_SIGMA_ROWS = range(1, 19)
+DS_OP_AFFINE_COMPOSE = 20          # (19 stays unassigned: tests/test_amed_ldm_cpu.py pins it as "no such operation")
 
 _SIGNATURES = {
     'ds_version': (C.c_int, []),
@@ -301,17 +306,27 @@ def check(code, what=''):
         raise DsError(f'{what or "libdsamd call"} failed with code {code}: {msg.decode() if msg else "?"}')
 
 
-def run_op(op, args, what):
-    """One launch that exists only as a plan operation (DS_OP_CHANNEL_MEAN_F16, DS_OP_CFG_SIGMA_ROWS): recorded into a one-entry ds_plan,
-    run on the current stream, and the plan dropped again -- host bookkeeping only, the plan owns no device memory."""
+def run_op_rc(op, args, stream):
+    """run_op's launch on `stream`, its return code handed back instead of raised (Plan.run_python; the refusal tests)."""
     lib = load()
     h = vp()
     check(lib.ds_plan_create(C.byref(h)), 'ds_plan_create')
     try:
-        check(lib.ds_plan_add(h, op, C.byref(args), C.sizeof(args)), f'ds_plan_add({what})')
-        check(lib.ds_plan_run(h, stream_ptr()), what)
+        check(lib.ds_plan_add(h, op, C.byref(args), C.sizeof(args)), 'ds_plan_add')
+        return lib.ds_plan_run(h, stream)
     finally:
         lib.ds_plan_destroy(h)
+
+
+def run_op(op, args, what):
+    """One launch that exists only as a plan operation (DS_OP_CHANNEL_MEAN_F16, DS_OP_CFG_SIGMA_ROWS, DS_OP_AFFINE_COMPOSE): recorded into a
+    one-entry ds_plan, run on the current stream, and the plan dropped again -- host bookkeeping only, the plan owns no device memory."""
+    check(run_op_rc(op, args, stream_ptr()), what)
+
+
+def affine_compose(args, stream):
+    """DS_OP_AFFINE_COMPOSE as a callable of the shape Plan.run_python issues (argument struct by reference, stream); returns the code."""
+    return run_op_rc(DS_OP_AFFINE_COMPOSE, args._obj if hasattr(args, '_obj') else args, stream)
 
 
 def stream_ptr():

@@ -70,6 +70,9 @@ class UNetSpec:
     embedding_type: str = 'positional'  # 'positional' | 'fourier' (FourierEmbedding: a `map_noise.freqs` buffer in the state dict)
     encoder_type: str = 'standard'      # 'standard' | 'residual' ('aux' entries in `blocks`)
     resample_filter: Tuple[int, ...] = (1, 1)      # (1, 1) | (1, 3, 3, 1): the 1-D taps of every up / down block (and of the aux layers)
+    # SFD's distilled, step-conditioned nets (sfd-main/models/networks_edm.py:290-292, :438-440, :153): a second embedding path `map_step*` and an
+    # `affine_step` Linear in every block.  False: the key list and the parameters of the spec are those of a plain EDM net.
+    step_condition: bool = False
 
     @property
     def ncsnpp(self) -> bool:
@@ -90,7 +93,7 @@ def song_unet_spec(
     model_channels=128, channel_mult=(1, 2, 2, 2), channel_mult_emb=4, num_blocks=4,
     attn_resolutions=(16,), dropout=0.10, label_dropout=0, embedding_type='positional',
     channel_mult_noise=1, encoder_type='standard', decoder_type='standard',
-    resample_filter=(1, 1),
+    resample_filter=(1, 1), step_condition=False,
 ) -> UNetSpec:
     """DDPM++ / NCSN++ layer list; mirrors the construction order of networks_edm.py:260-310."""
     if embedding_type not in ('positional', 'fourier'):
@@ -109,6 +112,7 @@ def song_unet_spec(
         noise_channels=noise_channels, pos_endpoint=True, pos_max_positions=10000, swap_sincos=True,
         out_norm=f'dec.{img_resolution}x{img_resolution}_aux_norm', out_conv=f'dec.{img_resolution}x{img_resolution}_aux_conv',
         out_eps=1e-6, embedding_type=embedding_type, encoder_type=encoder_type, resample_filter=resample_filter,
+        step_condition=bool(step_condition),
     )
     common = dict(skip_scale=math.sqrt(0.5), eps=1e-6, adaptive_scale=False)
     cout = caux = in_channels
@@ -154,7 +158,7 @@ def song_unet_spec(
 def dhariwal_unet_spec(
     img_resolution, in_channels, out_channels, label_dim=0, augment_dim=0,
     model_channels=192, channel_mult=(1, 2, 3, 4), channel_mult_emb=4, num_blocks=3,
-    attn_resolutions=(32, 16, 8), dropout=0.10, label_dropout=0,
+    attn_resolutions=(32, 16, 8), dropout=0.10, label_dropout=0, step_condition=False,
 ) -> UNetSpec:
     """ADM layer list; mirrors networks_edm.py:387-425."""
     emb_channels = model_channels * channel_mult_emb
@@ -162,7 +166,7 @@ def dhariwal_unet_spec(
         model_type='DhariwalUNet', img_resolution=img_resolution, in_channels=in_channels, out_channels=out_channels,
         label_dim=label_dim, augment_dim=augment_dim, model_channels=model_channels, emb_channels=emb_channels,
         noise_channels=model_channels, pos_endpoint=False, pos_max_positions=10000, swap_sincos=False,
-        out_norm='out_norm', out_conv='out_conv', out_eps=1e-5,
+        out_norm='out_norm', out_conv='out_conv', out_eps=1e-5, step_condition=bool(step_condition),
     )
     common = dict(skip_scale=1.0, eps=1e-5, adaptive_scale=True)
 
@@ -296,6 +300,11 @@ def param_table(spec: UNetSpec) -> List[Tuple[str, Tuple[int, ...], tuple]]:
             _linear(keys, f'{m}.map_augment', spec.augment_dim, spec.noise_channels, bias=False)
         _linear(keys, f'{m}.map_layer0', spec.noise_channels, spec.emb_channels)
         _linear(keys, f'{m}.map_layer1', spec.emb_channels, spec.emb_channels)
+        if spec.step_condition:
+            if spec.embedding_type == 'fourier':   # map_step is a FourierEmbedding of its own: a second random frequency buffer
+                keys.append((f'{m}.map_step.freqs', (spec.noise_channels // 2,), ('fourier', 16.0)))
+            _linear(keys, f'{m}.map_step_layer0', spec.noise_channels, spec.emb_channels)
+            _linear(keys, f'{m}.map_step_layer1', spec.emb_channels, spec.emb_channels)
     else:
         if spec.augment_dim:
             _linear(keys, f'{m}.map_augment', spec.augment_dim, spec.model_channels, bias=False)
@@ -303,6 +312,9 @@ def param_table(spec: UNetSpec) -> List[Tuple[str, Tuple[int, ...], tuple]]:
         _linear(keys, f'{m}.map_layer1', spec.emb_channels, spec.emb_channels)
         if spec.label_dim:
             _linear(keys, f'{m}.map_label', spec.label_dim, spec.emb_channels, bias=False)
+        if spec.step_condition:
+            _linear(keys, f'{m}.map_step_layer0', spec.model_channels, spec.emb_channels)
+            _linear(keys, f'{m}.map_step_layer1', spec.emb_channels, spec.emb_channels)
     for b in spec.blocks:
         p = f'{m}.{b.name}'
         if b.kind in ('conv', 'aux'):
@@ -313,6 +325,8 @@ def param_table(spec: UNetSpec) -> List[Tuple[str, Tuple[int, ...], tuple]]:
         _linear(keys, f'{p}.affine', spec.emb_channels, b.cout * (2 if b.adaptive_scale else 1))
         _gn(keys, f'{p}.norm1', b.cout)
         _conv(keys, f'{p}.conv1', b.cout, b.cout, 3)
+        if spec.step_condition:
+            _linear(keys, f'{p}.affine_step', spec.emb_channels, b.cout * (2 if b.adaptive_scale else 1))
         if b.skip_conv:
             _conv(keys, f'{p}.skip', b.cin, b.cout, 1)
         if b.heads:
@@ -340,10 +354,14 @@ def init_params(spec: UNetSpec, seed: int = 0, mode: str = 'signal') -> Dict[str
     mode='reference': the distributions of the reference initialisers (xavier_uniform / kaiming_uniform with
         the init_weight multipliers) — same statistics, not the same random stream.
     The NCSN++ tensors (``map_noise.freqs`` ~ N(0, 16^2) in both modes, networks_edm.py:207; the ``aux_residual`` layers) are drawn from
-    a generator of their own: every other tensor of a network keeps the bits it has without them.
+    a generator of their own: every other tensor of a network keeps the bits it has without them.  So are the step-condition tensors
+    (``map_step*``, every ``affine_step``) of a spec with ``step_condition``: the other tensors are those of the plain spec, bit for bit.  They
+    follow the same rules as their noise-path twins (weights ~ N(0, 1/fan_in) in 'signal' mode: the step embedding moves the output by
+    percents of its scale, tools/gen_sfd_golden.py asserts it).
     """
     g_main = torch.Generator(device='cpu').manual_seed(int(seed))
     g_ncsnpp = torch.Generator(device='cpu').manual_seed(int(seed) + 0x4e43534e)
+    g_step = torch.Generator(device='cpu').manual_seed(int(seed) + 0x53544550)
     out: Dict[str, torch.Tensor] = {}
     song = spec.model_type == 'SongUNet'
     if mode not in ('signal', 'reference'):
@@ -351,6 +369,8 @@ def init_params(spec: UNetSpec, seed: int = 0, mode: str = 'signal') -> Dict[str
     for key, shape, rule in param_table(spec):
         kind = rule[0]
         g = g_ncsnpp if (kind == 'fourier' or '_aux_residual.' in key) else g_main
+        if '.map_step' in key or '.affine_step.' in key:
+            g = g_step
         if kind == 'fourier':
             t = torch.randn(shape, generator=g) * rule[1]
         elif mode == 'signal':
@@ -362,6 +382,7 @@ def init_params(spec: UNetSpec, seed: int = 0, mode: str = 'signal') -> Dict[str
                 t = 1.0 + torch.randn(shape, generator=g) * 0.1
         elif mode == 'reference':
             leaf = key.rsplit('.', 2)[-2]
+            leaf = {'affine_step': 'affine', 'map_step_layer0': 'map_layer0', 'map_step_layer1': 'map_layer1'}.get(leaf, leaf)
             zero_init = leaf in ('conv1', 'proj') or key.startswith(f'model.{spec.out_conv}')
             if kind in ('conv', 'linear', 'conv_bias', 'linear_bias'):
                 fin, fout = rule[1], rule[2]

@@ -70,10 +70,11 @@ __device__ __forceinline__ void ds_timeline_mark(float* buf, int abl, int slot, 
 #define DS_TL(buf_, abl_, slot_, tile_) do { } while (0)
 #endif
 
-// Launchers behind plan operations that have no exported entry point (DS_OP_CHANNEL_MEAN_F16: norm_act.hip, DS_OP_CFG_SIGMA_ROWS: solver.hip;
+// Launchers behind plan operations that have no exported entry point (DS_OP_CHANNEL_MEAN_F16, DS_OP_AFFINE_COMPOSE: norm_act.hip, DS_OP_CFG_SIGMA_ROWS: solver.hip;
 // argument structs and semantics in include/ds_engine.h).  Not DS_API: hidden in the shared library, reached through ds_plan_run.
 int ds_channel_mean_f16(const void* x, int ld, int c, long long rows, float* out, void* stream);
 int ds_cfg_sigma_rows(const float* sigma, int n, const float* log_alpha, int m, int copies, float* sigma_out, float* c_noise_out, void* stream);
+int ds_affine_compose(const ds_affine_compose_args* a, void* stream);
 
 static inline bool ds_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 

@@ -974,6 +974,39 @@ int ds_channel_mean_f16(const void* x, int ld, int c, long long rows, float* out
     return DS_OK;
 }
 
+// Step-conditioned adaptive blocks (ds_affine_compose_args, include/ds_engine.h): the step row's (scale, shift) folded into every row's pair,
+// in place, so that gn_coefs and its consumers see ONE affine.  One thread per group of four pairs: two 16-byte loads of the row, two of the
+// step row (shared by all rows: L2), two 16-byte stores.  A table entry that does not name four whole columns inside `width` is skipped.
+__global__ void affine_compose_kernel(float* __restrict__ aff, int ld, int rows, int width, const float* __restrict__ step,
+                                      const int2* __restrict__ pairs, int groups) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;       // 64-bit: the last block of a launch near 2^31 threads must not wrap
+    if (idx >= (long long)rows * groups) return;
+    const int r = (int)(idx / groups), g = (int)(idx - (long long)r * groups);
+    const int2 p = pairs[g];
+    if (((p.x | p.y) & 3) || p.x < 0 || p.y < 0 || p.x > width - 4 || p.y > width - 4) return;
+    float* row = aff + (size_t)r * ld;
+    float4 s = *reinterpret_cast<const float4*>(row + p.x), h = *reinterpret_cast<const float4*>(row + p.y);
+    const float4 ss = *reinterpret_cast<const float4*>(step + p.x), hs = *reinterpret_cast<const float4*>(step + p.y);
+    const float gx = 1.0f + ss.x, gy = 1.0f + ss.y, gz = 1.0f + ss.z, gw = 1.0f + ss.w;
+    s.x = fmaf(1.0f + s.x, gx, -1.0f); s.y = fmaf(1.0f + s.y, gy, -1.0f); s.z = fmaf(1.0f + s.z, gz, -1.0f); s.w = fmaf(1.0f + s.w, gw, -1.0f);
+    h.x = fmaf(h.x, gx, hs.x); h.y = fmaf(h.y, gy, hs.y); h.z = fmaf(h.z, gz, hs.z); h.w = fmaf(h.w, gw, hs.w);
+    *reinterpret_cast<float4*>(row + p.x) = s;
+    *reinterpret_cast<float4*>(row + p.y) = h;
+}
+
+int ds_affine_compose(const ds_affine_compose_args* a, void* stream) {
+    (void)hipGetLastError();   // drop stale errors of unrelated runtime calls
+    if (!a || !a->aff || !a->step || !a->pairs || a->rows <= 0 || a->groups <= 0) return DS_E_ARG;
+    if (a->width <= 0 || (a->width & 3) || a->width > a->ld) return DS_E_SHAPE;
+    if ((a->ld & 3) || !ds_aligned16(a->aff) || !ds_aligned16(a->step) || (reinterpret_cast<uintptr_t>(a->pairs) & 7u)) return DS_E_ALIGN;
+    const long long total = (long long)a->rows * a->groups;
+    if (total > 0x7fffffffLL) return DS_E_SHAPE;
+    hipLaunchKernelGGL(affine_compose_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a->aff, a->ld, a->rows,
+                       a->width, a->step, reinterpret_cast<const int2*>(a->pairs), a->groups);
+    DS_CHECK_LAUNCH();
+    return DS_OK;
+}
+
 extern "C" int ds_layernorm_rows(const float* x, int ldx, const float* gamma, const float* beta, float eps, float* y, int ldy,
                                  long long rows, int cols, void* stream) {
     (void)hipGetLastError();

@@ -12,6 +12,7 @@ union ArgBlob {
     ds_conv_args conv; ds_gemm_args gemm; ds_norm_args norm; ds_gn_finalize_args fin; ds_attn_args attn;
     ds_layernorm_args ln; ds_geglu_args geglu; ds_noise_embed_args ne; ds_stem_im2col_args stem;
     ds_token_embed_args tok; ds_quick_gelu_args qg; ds_channel_mean_f16_args cm16; ds_cfg_sigma_rows_args csr;
+    ds_affine_compose_args acomp;
 };
 
 struct Node { int op; ArgBlob a; };
@@ -31,6 +32,7 @@ size_t arg_size(int op) {
         case DS_OP_QUICK_GELU: return sizeof(ds_quick_gelu_args);
         case DS_OP_CHANNEL_MEAN_F16: return sizeof(ds_channel_mean_f16_args);
         case DS_OP_CFG_SIGMA_ROWS: return sizeof(ds_cfg_sigma_rows_args);
+        case DS_OP_AFFINE_COMPOSE: return sizeof(ds_affine_compose_args);
         default: return 0;
     }
 }
@@ -62,6 +64,7 @@ int issue(const Node& n, void* stream) {
         case DS_OP_CHANNEL_MEAN_F16: { const ds_channel_mean_f16_args& m = n.a.cm16; return ds_channel_mean_f16(m.x, m.ld, m.c, m.rows, m.out, stream); }
         case DS_OP_CFG_SIGMA_ROWS: { const ds_cfg_sigma_rows_args& r = n.a.csr;
             return ds_cfg_sigma_rows(r.sigma, r.n, r.log_alpha, r.m, r.copies, r.sigma_out, r.c_noise_out, stream); }
+        case DS_OP_AFFINE_COMPOSE: return ds_affine_compose(&n.a.acomp, stream);
         default: return DS_E_ARG;
     }
 }

@@ -115,6 +115,8 @@ class UNetEngine:
             off += aff_w[-1].shape[0]
         self.aff_total = off
         w['aff.w'] = pack_linear_weight(torch.cat(aff_w, 0)); w['aff.b'] = torch.cat(aff_b, 0).contiguous()
+        if spec.step_condition:
+            self._pack_step(params, w, g)
         # blocks
         for b in spec.blocks:
             p = f'{m}.{b.name}'
@@ -164,9 +166,42 @@ class UNetEngine:
             w['outc.w16'] = pack_conv_weight_split(g(f'{m}.{spec.out_conv}.weight'))
         self.w = w
 
+    def _pack_step(self, params, w, g):
+        """The step-condition path of SFD's distilled nets (sfd-main/models/networks_edm.py:290-292 / :438-440, :153): its own embedding MLP and
+        every block's `affine_step`, concatenated into one projection of the single step row in the column layout of `aff`.
+        Non-adaptive blocks add the two projections (:188): the row is the BIAS of the affine launch, so its own bias carries both layers'.
+        Adaptive blocks apply them one after the other (:176-179): the row keeps its own bias and DS_OP_AFFINE_COMPOSE folds it into `aff`
+        through `step.pairs`, the table of {scale column, shift column} per four channels of every block."""
+        spec, m = self.spec, 'model'
+        w['freqs_step'] = w['freqs']
+        if spec.embedding_type == 'fourier':                     # map_step is a FourierEmbedding with a buffer of its own
+            fs = (2 * np.pi * params[f'{m}.map_step.freqs'].detach().to(device='cpu', dtype=torch.float32)).to(torch.float32)
+            assert fs.shape == w['freqs'].shape
+            w['freqs_step'] = fs.contiguous().to(self.device)
+        for i in (0, 1):
+            w[f'mstep{i}.w'] = pack_linear_weight(g(f'{m}.map_step_layer{i}.weight')); w[f'mstep{i}.b'] = g(f'{m}.map_step_layer{i}.bias')
+        blocks = [b for b in spec.blocks if b.kind == 'block']
+        w['affs.w'] = pack_linear_weight(torch.cat([g(f'{m}.{b.name}.affine_step.weight') for b in blocks], 0))
+        bias = torch.cat([g(f'{m}.{b.name}.affine_step.bias') for b in blocks], 0)
+        adaptive = {b.adaptive_scale for b in blocks}
+        assert len(adaptive) == 1 and bias.numel() == self.aff_total
+        self.step_adaptive = adaptive.pop()
+        if self.step_adaptive:
+            pairs = [(self.aff_off[b.name] + j, self.aff_off[b.name] + b.cout + j) for b in blocks for j in range(0, b.cout, 4)]
+            assert all(b.cout % 4 == 0 and self.aff_off[b.name] % 4 == 0 for b in blocks) and self.aff_total % 4 == 0
+            w['step.pairs'] = torch.tensor(pairs, dtype=torch.int32).to(self.device).contiguous()
+        else:
+            bias = w['aff.b'] + bias
+        w['affs.b'] = bias.contiguous()
+
     # ------------------------------------------------------------------------------------------ plan
-    def plan(self, B: int, emb_rows: int) -> _Plan:
-        key = (B, emb_rows, self.fuse_norm16)
+    def plan(self, B: int, emb_rows: int, step: bool = False) -> _Plan:
+        """step: the plan of an evaluation with a step condition (a one-float input `bufs['step']` and the launches of _embedding's step path);
+        False is launch for launch the plan of a net without step weights."""
+        step = bool(step)
+        if step and not self.spec.step_condition:
+            raise ValueError('this network was built without step-condition weights (UNetSpec.step_condition)')
+        key = (B, emb_rows, self.fuse_norm16) + ((True,) if step else ())
         if key in self._plans:
             return self._plans[key]
         spec, w, lib = self.spec, self.w, self.lib
@@ -182,7 +217,7 @@ class UNetEngine:
         if spec.label_dim:
             bufs['labels'] = torch.zeros(Bs, -(-spec.label_dim // 32) * 32, dtype=torch.float32, device=self.device)
         ws = self._workspaces(bd, B, Bs, kpad)
-        ws.aff = self._embedding(bd, Bs)
+        ws.aff = self._embedding(bd, Bs, step)
         # ---- fp16 residual stream -------------------------------------------------------------------------------
         # The reference's fp16 mode keeps EVERY activation of the U-Net body in fp16 (networks_edm.py:486 `x.to(dtype)`, :165-179 run in
         # that dtype): when every block of this plan runs on the fp16-activation kernels, block outputs (the residual stream, the skip
@@ -258,10 +293,23 @@ class UNetEngine:
         bd.P.bufs.update(act=ws.act, hbuf=ws.hbuf, sres=ws.sres, sproj=ws.sproj)
         return ws
 
-    def _embedding(self, bd, Bs):
-        """Embedding path (networks_edm.py:314-324 / :429-439) and every block's affine layer in one GEMM; returns its output [Bs, aff_total]."""
+    def _embedding(self, bd, Bs, step=False):
+        """Embedding path (networks_edm.py:314-324 / :429-439) and every block's affine layer in one GEMM; returns its output [Bs, aff_total].
+        step: plus the step path on ONE row -- embedding of the raw value, two Linear + SiLU, every `affine_step` in one projection -- whose
+        result is the affine launch's bias (non-adaptive blocks) or is folded into its output by one more launch (adaptive blocks)."""
         spec, w, new, bufs = self.spec, self.w, bd.new, bd.P.bufs
         E, NC = spec.emb_channels, spec.noise_channels
+        aff_bias = w['aff.b']
+        if step:
+            bufs['step'] = new(1)
+            spos, s0, semb, srow = new(1, NC), new(1, E), new(1, E), new(1, self.aff_total)
+            bd.add(self.lib.ds_noise_embed, (_ptr(bufs['step']), 1, _ptr(w['freqs_step']), NC, int(spec.swap_sincos) | 2, _ptr(spos), NC), 'step_embed')
+            bd.linear(spos, NC, 1, w['mstep0.w'], E, s0, 'map_step_layer0', bias=w['mstep0.b'], act=DS_ACT_SILU, emb=True)
+            bd.linear(s0, E, 1, w['mstep1.w'], E, semb, 'map_step_layer1', bias=w['mstep1.b'], act=DS_ACT_SILU, emb=True)
+            bd.linear(semb, E, 1, w['affs.w'], self.aff_total, srow, 'affine_step_all', bias=w['affs.b'], emb=True)
+            bufs['aff_step'] = srow
+            if not self.step_adaptive:
+                aff_bias = srow
         pos, e0, emb, aff = new(Bs, NC), new(Bs, E), new(Bs, E), new(Bs, self.aff_total)
         lab = bufs.get('labels')
         lpad = lab.shape[1] if lab is not None else 0
@@ -280,7 +328,9 @@ class UNetEngine:
                 lab_e = new(Bs, E)
                 bd.linear(lab, lpad, Bs, w['label.w'], E, lab_e, 'map_label', bias=w['label.b'], emb=True)
             bd.linear(e0, E, Bs, w['map1.w'], E, emb, 'map_layer1', bias=w['map1.b'], res=lab_e, res_ld=E, act=DS_ACT_SILU, emb=True)
-        bd.linear(emb, E, Bs, w['aff.w'], self.aff_total, aff, 'affine_all', bias=w['aff.b'], emb=True)
+        bd.linear(emb, E, Bs, w['aff.w'], self.aff_total, aff, 'affine_all', bias=aff_bias, emb=True)
+        if step and self.step_adaptive:
+            bd.affine_compose(aff, self.aff_total, Bs, self.aff_total, srow, w['step.pairs'], 'affine_compose')
         bufs.update(emb=emb, aff=aff)
         return aff
 
@@ -558,8 +608,11 @@ class EDMDenoiser:
 
     @classmethod
     def from_config(cls, name_or_kwargs, seed=0, mode='signal', device='cuda', use_fp16=False, split_fp16=False, batch_invariant=False,
-                    up_phase=True, winograd=True):
+                    up_phase=True, winograd=True, step_condition=False):
+        """step_condition: the net with SFD's step-condition weights (arch.UNetSpec.step_condition)."""
         kw = arch.NAMED_CONFIGS[name_or_kwargs] if isinstance(name_or_kwargs, str) else name_or_kwargs
+        if step_condition:
+            kw = dict(kw, step_condition=True)
         spec = arch.edm_precond_spec(**kw)
         return cls(spec, arch.init_params(spec, seed=seed, mode=mode), device, use_fp16=use_fp16, split_fp16=split_fp16,
                    batch_invariant=batch_invariant, up_phase=up_phase, winograd=winograd)
@@ -572,8 +625,12 @@ class EDMDenoiser:
         spec = spec_from_module(net)
         if use_fp16 is None:
             use_fp16 = bool(getattr(net, 'use_fp16', False))
-        return cls(spec, {k: v for k, v in net.state_dict().items() if 'resample_filter' not in k}, device, use_fp16=use_fp16,
-                   batch_invariant=batch_invariant)
+        params = {k: v for k, v in net.state_dict().items() if 'resample_filter' not in k}
+        known = {k for k, _, _ in arch.param_table(spec)}
+        extra = sorted(set(params) - known)
+        if extra:               # a layer the engine would not evaluate must not be dropped without a word
+            raise NotImplementedError(f'{len(extra)} state-dict entries of the module have no place in the recovered spec: {extra[:4]} ...')
+        return cls(spec, params, device, use_fp16=use_fp16, batch_invariant=batch_invariant)
 
     def eval(self):
         return self
@@ -582,7 +639,12 @@ class EDMDenoiser:
         return self
 
     # -- raw evaluation: fills plan inputs, runs the plan, returns (F_nhwc4, plan) -----------------------------------
-    def _prepare(self, x, sigma, class_labels):
+    def _step_value(self, step_condition, skip_tuning=False):
+        """ops.step_value for this net: the evaluation's step condition as a host float, or None."""
+        from . import ops
+        return ops.step_value(step_condition, self.spec.step_condition, skip_tuning)
+
+    def _prepare(self, x, sigma, class_labels, step=None):
         B = x.shape[0]
         lib = self.engine.lib
         st = _lib.stream_ptr()
@@ -592,7 +654,9 @@ class EDMDenoiser:
         else:
             sigma = torch.as_tensor(sigma, dtype=torch.float32, device=self.device).reshape(-1).contiguous()
             emb_rows = B if (sigma.numel() > 1 or self.label_dim) else 1
-        plan = self.engine.plan(B, emb_rows)
+        plan = self.engine.plan(B, emb_rows, step is not None)
+        if step is not None:     # written by a kernel, like a host-scalar sigma
+            _lib.check(lib.ds_fill(_ptr(plan.bufs['step']), step, 1, st), 'fill step')
         xb = plan.bufs['x']
         if x.data_ptr() != xb.data_ptr():
             assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
@@ -615,7 +679,7 @@ class EDMDenoiser:
                 _lib.check(lib.ds_copy_rows(_ptr(cl), self.label_dim, _ptr(lb), lb.shape[1], B, self.label_dim, st), 'copy labels')
         return plan, emb_rows
 
-    def raw(self, x, sigma, class_labels=None, update=None):
+    def raw(self, x, sigma, class_labels=None, update=None, step_condition=None):
         """F(c_in x; c_noise), the raw network output, as an NCHW [B, C, H, W] tensor.  Engine-owned, overwritten by the
         next evaluation at the same batch size.
         update: a filled ``_lib.UpdateArgs`` (raw = 1, f ignored): the network head applies that solver update in its epilogue -- no update
@@ -623,7 +687,7 @@ class EDMDenoiser:
         A plan is SINGLE-STREAM state: its workspaces, its input buffers and the one ``head_update`` struct the head launch points at are
         written here and read by the launches that follow, so two threads / streams must not evaluate the same (denoiser, batch) plan
         concurrently -- build one denoiser per stream (the reference's module has the same contract: one process, one stream per rank)."""
-        plan, _ = self._prepare(x, sigma, class_labels)
+        plan, _ = self._prepare(x, sigma, class_labels, self._step_value(step_condition))
         if update is None:
             plan.run(_lib.stream_ptr())
             return plan.bufs['out'], plan
@@ -637,17 +701,18 @@ class EDMDenoiser:
             hu.x_out, hu.m_out = None, None                      # the next plain evaluation must not update anything
         return plan.bufs['out'], plan
 
-    def head_update_ok(self, B, sigma, class_labels=None):
+    def head_update_ok(self, B, sigma, class_labels=None, step_condition=None):
         """True when an evaluation at this batch / sigma form can carry a fused solver update (solvers._Run asks before it defers)."""
         host_scalar = isinstance(sigma, (int, float))
         emb_rows = (B if self.label_dim else 1) if host_scalar else (B if (torch.as_tensor(sigma).numel() > 1 or self.label_dim) else 1)
-        return bool(self.engine.plan(B, emb_rows).head_fusable)
+        return bool(self.engine.plan(B, emb_rows, self._step_value(step_condition) is not None).head_fusable)
 
-    def __call__(self, x, sigma, class_labels=None, force_fp32=False, **kwargs):
+    def __call__(self, x, sigma, class_labels=None, force_fp32=False, step_condition=None, skip_tuning=False, **kwargs):
+        """step_condition: None (the plain evaluation, also on a step-capable net) or the one value of this evaluation (_step_value)."""
         from . import ops
         B, Cc, H, W = x.shape
         x = x.to(torch.float32).contiguous()
-        plan, emb_rows = self._prepare(x, sigma, class_labels)
+        plan, emb_rows = self._prepare(x, sigma, class_labels, self._step_value(step_condition, skip_tuning))
         plan.run(_lib.stream_ptr())
         self._last = (plan, B)
         out = torch.empty_like(x)
@@ -699,6 +764,13 @@ def spec_from_module(net) -> arch.UNetSpec:
     song = any('aux' in k for k in model.dec.keys())
     first = model.enc[names[0]]
     res0 = int(net.img_resolution)
+    # SFD's step-conditioned nets carry map_step_layer{0,1} and an affine_step in every block (sfd-main/models/networks_edm.py:291, :153)
+    every_block = [blk for part in (model.enc, model.dec) for blk in part.values() if getattr(blk, 'affine', None) is not None]
+    with_step = [getattr(blk, 'affine_step', None) is not None for blk in every_block]
+    step = getattr(model, 'map_step_layer0', None) is not None
+    if any(with_step) != step or (any(with_step) and not all(with_step)):
+        raise ValueError(f'inconsistent step-condition layers: map_step_layer0 {"present" if step else "absent"}, affine_step in '
+                         f'{sum(with_step)} of {len(with_step)} blocks')
     mc_emb = model.map_layer0.weight.shape[0]
     blocks = [k for k in names if 'block' in k]
     levels = sorted({int(k.split('x')[0]) for k in names}, reverse=True)
@@ -729,7 +801,7 @@ def spec_from_module(net) -> arch.UNetSpec:
                                    num_blocks=num_blocks, attn_resolutions=attn,
                                    channel_mult_noise=model.map_layer0.weight.shape[1] // model_channels,
                                    embedding_type='fourier' if fourier else 'positional', encoder_type='residual' if residual else 'standard',
-                                   resample_filter=taps)
+                                   resample_filter=taps, step_condition=step)
     else:
         model_channels = model.map_layer0.weight.shape[1]
         mult = [model.enc[f'{r}x{r}_block0'].out_channels // model_channels for r in levels]
@@ -737,7 +809,7 @@ def spec_from_module(net) -> arch.UNetSpec:
         spec = arch.dhariwal_unet_spec(res0, net.img_channels, net.img_channels, label_dim=net.label_dim,
                                        augment_dim=(model.map_augment.weight.shape[1] if getattr(model, 'map_augment', None) is not None else 0),
                                        model_channels=model_channels, channel_mult=mult, channel_mult_emb=mc_emb // model_channels,
-                                       num_blocks=num_blocks, attn_resolutions=attn)
+                                       num_blocks=num_blocks, attn_resolutions=attn, step_condition=step)
     spec.sigma_data = float(getattr(net, 'sigma_data', 0.5))
     spec.sigma_min = float(getattr(net, 'sigma_min', 0.002))
     spec.sigma_max = float(getattr(net, 'sigma_max', 80.0))

@@ -59,6 +59,9 @@ class LDMUNetSpec:
     epsilon_t: float = 1e-3
     guidance_rate: float = 7.5
     guidance_type: str = 'classifier-free'
+    # SFD's distilled, step-conditioned U-Net (sfd-main/models/ldm/modules/diffusionmodules/openaimodel.py:563, :234): an `nfe_embed` MLP next to
+    # `time_embed` and an `emb_nfe_layers` Linear in every ResBlock.  False: the key list and the parameters of the spec are those of before.
+    step_condition: bool = False
 
     def res_layers(self):
         return [l for b in self.blocks for l in b.layers if l.kind == 'res']
@@ -156,6 +159,9 @@ def ldm_param_table(spec: LDMUNetSpec) -> List[Tuple[str, Tuple[int, ...], tuple
     E = spec.time_embed_dim
     _lin(keys, 'time_embed.0', spec.model_channels, E)
     _lin(keys, 'time_embed.2', E, E)
+    if spec.step_condition:
+        _lin(keys, 'nfe_embed.0', spec.model_channels, E)
+        _lin(keys, 'nfe_embed.2', E, E)
     for b in spec.blocks:
         for l in b.layers:
             p = l.key
@@ -167,6 +173,8 @@ def ldm_param_table(spec: LDMUNetSpec) -> List[Tuple[str, Tuple[int, ...], tuple
                 _lin(keys, f'{p}.emb_layers.1', E, l.cout)
                 _norm(keys, f'{p}.out_layers.0', l.cout)
                 _conv(keys, f'{p}.out_layers.3', l.cout, l.cout, 3)
+                if spec.step_condition:
+                    _lin(keys, f'{p}.emb_nfe_layers.1', E, l.cout)
                 if l.skip_conv:
                     _conv(keys, f'{p}.skip_connection', l.cin, l.cout, 1)
             elif l.kind == 'st':
@@ -196,10 +204,13 @@ def ldm_param_table(spec: LDMUNetSpec) -> List[Tuple[str, Tuple[int, ...], tuple
 def init_ldm_params(spec: LDMUNetSpec, seed: int = 0) -> Dict[str, torch.Tensor]:
     """Deterministic CPU-generated weights, every tensor carrying signal (weights ~ N(0, 1/fan_in), biases ~ N(0, 0.1^2),
     norm gains 1 + N(0, 0.1^2)).  The reference zero-initialises ``out_layers.3``, ``proj_out`` and ``out.2``
-    (``zero_module``), which would make random-init parity vacuous."""
-    g = torch.Generator(device='cpu').manual_seed(int(seed))
+    (``zero_module``), which would make random-init parity vacuous.  The step-condition tensors (``nfe_embed``,
+    ``emb_nfe_layers``) are drawn from a generator of their own: every other tensor keeps the bits it has without them."""
+    g_main = torch.Generator(device='cpu').manual_seed(int(seed))
+    g_step = torch.Generator(device='cpu').manual_seed(int(seed) + 0x53544550)
     out: Dict[str, torch.Tensor] = {}
     for key, shape, rule in ldm_param_table(spec):
+        g = g_step if (key.startswith('nfe_embed.') or '.emb_nfe_layers.' in key) else g_main
         if rule[0] == 'w':
             t = torch.randn(shape, generator=g) * (1.0 / math.sqrt(rule[1]))
         elif rule[0] == 'b':

@@ -75,6 +75,14 @@ class LDMUNetEngine:
             off += l.cout
         self.aff_total = off
         w['aff.w'], w['aff.b'] = pack_linear_weight(torch.cat(aff_w, 0)), torch.cat(aff_b, 0).contiguous()
+        if spec.step_condition:
+            # SFD's step condition (sfd-main/.../openaimodel.py:563, :234, :298-316): `nfe_embed` next to `time_embed`, and every ResBlock adds
+            # emb_nfe_layers(emb_nfe) to emb_layers(emb) (no scale-shift norm in this U-Net) -- one projection of the single step row over the
+            # concatenated weights, whose bias carries both layers' and whose output row is the BIAS of the emb_layers launch
+            w['ne0.w'], w['ne0.b'] = pack_linear_weight(g('nfe_embed.0.weight')), g('nfe_embed.0.bias')
+            w['ne2.w'], w['ne2.b'] = pack_linear_weight(g('nfe_embed.2.weight')), g('nfe_embed.2.bias')
+            w['affs.w'] = pack_linear_weight(torch.cat([g(f'{l.key}.emb_nfe_layers.1.weight') for l in spec.res_layers()], 0))
+            w['affs.b'] = (w['aff.b'] + torch.cat([g(f'{l.key}.emb_nfe_layers.1.bias') for l in spec.res_layers()], 0)).contiguous()
         for b in spec.blocks:
             for l in b.layers:
                 p = l.key
@@ -129,9 +137,13 @@ class LDMUNetEngine:
         self.w = w
 
     # ------------------------------------------------------------------------------------------ plan
-    def plan(self, N: int, emb_rows: int, ctx_len: int) -> Plan:
-        """N = images in the U-Net batch (2B under classifier-free guidance); emb_rows = 1 (shared sigma) or N."""
-        key = (N, emb_rows, ctx_len, self.fuse_norm16)
+    def plan(self, N: int, emb_rows: int, ctx_len: int, step: bool = False) -> Plan:
+        """N = images in the U-Net batch (2B under classifier-free guidance); emb_rows = 1 (shared sigma) or N.  step: the plan of an
+        evaluation with a step condition (a one-float input `bufs['step']`, four more launches); False is the plan of a net without step weights."""
+        step = bool(step)
+        if step and not self.spec.step_condition:
+            raise ValueError('this network was built without step-condition weights (LDMUNetSpec.step_condition)')
+        key = (N, emb_rows, ctx_len, self.fuse_norm16) + ((True,) if step else ())
         if key in self._plans:
             return self._plans[key]
         spec, w, lib = self.spec, self.w, self.lib
@@ -154,7 +166,16 @@ class LDMUNetEngine:
         bd.add(lib.ds_noise_embed, (ptr(bufs['c_noise']), emb_rows, ptr(w['freqs']), MC, 2, ptr(pos), MC), 'timestep_embedding')
         bd.linear(pos, MC, emb_rows, w['te0.w'], E, e0, 'time_embed.0', bias=w['te0.b'], act=DS_ACT_SILU, emb=True)
         bd.linear(e0, E, emb_rows, w['te2.w'], E, emb, 'time_embed.2', bias=w['te2.b'], act=DS_ACT_SILU, emb=True)   # SiLU of emb_layers[0]
-        bd.linear(emb, E, emb_rows, w['aff.w'], self.aff_total, aff, 'emb_layers_all', bias=w['aff.b'], emb=True)
+        aff_bias = w['aff.b']
+        if step:         # one row serves every image (both halves of a classifier-free evaluation): openaimodel.py:783-786 on the raw step value
+            bufs['step'] = new(1)
+            spos, s0, semb, srow = new(1, MC), new(1, E), new(1, E), new(1, self.aff_total)
+            bd.add(lib.ds_noise_embed, (ptr(bufs['step']), 1, ptr(w['freqs']), MC, 2, ptr(spos), MC), 'step_embedding')
+            bd.linear(spos, MC, 1, w['ne0.w'], E, s0, 'nfe_embed.0', bias=w['ne0.b'], act=DS_ACT_SILU, emb=True)
+            bd.linear(s0, E, 1, w['ne2.w'], E, semb, 'nfe_embed.2', bias=w['ne2.b'], act=DS_ACT_SILU, emb=True)   # SiLU of emb_nfe_layers[0]
+            bd.linear(semb, E, 1, w['affs.w'], self.aff_total, srow, 'emb_nfe_layers_all', bias=w['affs.b'], emb=True)
+            bufs['aff_step'] = aff_bias = srow
+        bd.linear(emb, E, emb_rows, w['aff.w'], self.aff_total, aff, 'emb_layers_all', bias=aff_bias, emb=True)
 
         # ---- fp16 residual stream: under torch.autocast (sample.py:293-297) the reference's convolutions and Linear layers emit fp16
         # tensors, so every activation between layers is fp16.  Every ResBlock / SpatialTransformer / upsampling convolution that runs on
@@ -317,6 +338,32 @@ def _interp(x, xp, yp):
     return yp[i] + (x - xp[i]) * (yp[i + 1] - yp[i]) / (xp[i + 1] - xp[i])
 
 
+def ldm_spec_from_module(unet, img_resolution, params=None):
+    """Recover the LDMUNetSpec of a live reference ``UNetModel`` (duck-typed) from the constructor arguments it keeps as attributes
+    (openaimodel.py:540-553) and from its state dict `params` (default: ``unet.state_dict()``): the context width is ``attn2.to_k``'s, and
+    ``step_condition`` is read off ``nfe_embed`` / ``emb_nfe_layers`` (SFD's distilled U-Net) -- one group without the other raises, and so does
+    a state dict that is not the spec's key list: nothing is dropped or left unset without a word."""
+    params = dict(unet.state_dict()) if params is None else params
+    ctx = [v.shape[1] for k, v in params.items() if k.endswith('.attn2.to_k.weight')]
+    if not ctx:
+        raise NotImplementedError('UNetModel without cross-attention (use_spatial_transformer=False) is not supported')
+    has_embed = any(k.startswith('nfe_embed.') for k in params)
+    has_layers = any('.emb_nfe_layers.' in k for k in params)
+    if has_embed != has_layers:
+        raise ValueError(f'inconsistent step-condition layers: nfe_embed {"present" if has_embed else "absent"}, emb_nfe_layers '
+                         f'{"present" if has_layers else "absent"}')
+    spec = ldm_arch.ldm_unet_spec(img_resolution=int(img_resolution), in_channels=int(unet.in_channels), out_channels=int(unet.out_channels),
+                                  model_channels=int(unet.model_channels), attention_resolutions=tuple(int(v) for v in unet.attention_resolutions),
+                                  num_res_blocks=int(unet.num_res_blocks), channel_mult=tuple(int(v) for v in unet.channel_mult),
+                                  num_heads=int(unet.num_heads), context_dim=int(ctx[0]), step_condition=has_embed)
+    want = {k: tuple(shape) for k, shape, _ in ldm_arch.ldm_param_table(spec)}
+    got = {k: tuple(v.shape) for k, v in params.items()}
+    if want != got:
+        odd = sorted(set(want) ^ set(got)) or sorted(k for k in want if want[k] != got[k])
+        raise NotImplementedError(f'the U-Net\'s state dict is not that of the recovered spec ({len(odd)} entries differ: {odd[:4]} ...)')
+    return spec
+
+
 class CFGSchedule:
     """The host side of ``CFGPrecond`` (networks_edm.py:654-661, 692-714): sigma(t), its inverse and the schedule end points,
     piecewise-linear over the ``alphas_cumprod`` table, evaluated in fp32 with the reference's formulas.  Pure host code."""
@@ -377,8 +424,10 @@ class CFGDenoiser(CFGSchedule):
         self._log_alpha_dev = None          # the log_alpha table on the device (DS_OP_CFG_SIGMA_ROWS), uploaded on first use
 
     @classmethod
-    def from_config(cls, name_or_kwargs, seed=0, device='cuda', **kw):
+    def from_config(cls, name_or_kwargs, seed=0, device='cuda', step_condition=False, **kw):
         cfg = ldm_arch.NAMED_LDM_CONFIGS[name_or_kwargs] if isinstance(name_or_kwargs, str) else name_or_kwargs
+        if step_condition:       # SFD's step-conditioned U-Net: nfe_embed + emb_nfe_layers (LDMUNetSpec.step_condition)
+            cfg = dict(cfg, step_condition=True)
         spec = ldm_arch.ldm_unet_spec(**cfg)
         return cls(spec, ldm_arch.init_ldm_params(spec, seed=seed), device, **kw)
 
@@ -396,11 +445,17 @@ class CFGDenoiser(CFGSchedule):
             P.ctx_capture_key = None
 
     # -- evaluation ----------------------------------------------------------------------------------------------------------
-    def raw(self, x, sigma, condition=None, unconditional_condition=None, device_sigma=False):
+    def _step_value(self, step_condition, skip_tuning=False):
+        """ops.step_value for this net: the evaluation's step condition as a host float, or None."""
+        from . import ops
+        return ops.step_value(step_condition, self.spec.step_condition, skip_tuning)
+
+    def raw(self, x, sigma, condition=None, unconditional_condition=None, device_sigma=False, step_condition=None, skip_tuning=False):
         """Runs the plan; returns (F rows NHWC [N*H*W, 4], plan, doubled).
         device_sigma: `sigma` is an fp32 device tensor [B] and stays there -- sigma and c_noise rows of both halves are written by one
         DS_OP_CFG_SIGMA_ROWS launch instead of the host interpolation of ``sigma_inv`` (a D2H copy, CPU math and an H2D copy per evaluation:
         the AMED samplers evaluate at per-sample device sigmas in every step).  Off (the default) keeps the host path and its bits."""
+        step = self._step_value(step_condition, skip_tuning)          # (refused before anything touches the device)
         lib = self.engine.lib
         st = _lib.stream_ptr()
         B = x.shape[0]
@@ -417,8 +472,10 @@ class CFGDenoiser(CFGSchedule):
         emb_rows = 1 if host_scalar else N
         cond = condition if condition is not None else torch.zeros(B, 1, self.spec.context_dim, device=self.device)
         L = cond.shape[1]
-        plan = self.engine.plan(N, emb_rows, L)
+        plan = self.engine.plan(N, emb_rows, L, step is not None)
         bufs = plan.bufs
+        if step is not None:
+            _lib.check(lib.ds_fill(ptr(bufs['step']), step, 1, st), 'fill step')
         x = x.to(torch.float32).contiguous()
         per = x[0].numel()
         for half in range(2 if doubled else 1):
@@ -477,9 +534,11 @@ class CFGDenoiser(CFGSchedule):
         self._last = (plan, B, doubled)
         return bufs['out'], plan, doubled
 
-    def __call__(self, x, sigma, condition=None, unconditional_condition=None, force_fp32=False, device_sigma=False, **kwargs):
+    def __call__(self, x, sigma, condition=None, unconditional_condition=None, force_fp32=False, device_sigma=False, step_condition=None,
+                 skip_tuning=False, **kwargs):
         B, Cc, H, W = x.shape
-        f, plan, doubled = self.raw(x, sigma, condition, unconditional_condition, device_sigma=device_sigma)
+        f, plan, doubled = self.raw(x, sigma, condition, unconditional_condition, device_sigma=device_sigma, step_condition=step_condition,
+                                    skip_tuning=skip_tuning)
         out = torch.empty(B, Cc, H, W, dtype=torch.float32, device=self.device)
         rows = plan.bufs['sigma'].numel()
         ops.cfg_denoise(plan.bufs['x'], f, 4, plan.bufs['sigma'], 1 if rows == 1 else B, self.guidance_rate, doubled, B, Cc, H, W, out)

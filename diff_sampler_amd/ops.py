@@ -368,3 +368,23 @@ def philox_randn(seeds, offset, out, n):
 def philox_randint(seeds, offset, high, out):
     _lib.check(_lib.load().ds_philox_randint(_p(seeds), int(offset), int(high), _p(out), seeds.numel(), _lib.stream_ptr()), 'ds_philox_randint')
     return 4
+
+
+def step_value(step_condition, supported, skip_tuning=False):
+    """The step condition of one evaluation of an SFD-distilled net as a host float, or None (the denoisers' ``_step_value``).  An int, a
+    float or a tensor whose elements all agree: the reference makes it a one-element tensor and expands it to the batch
+    (sfd-main/models/networks_edm.py:553-554, :612-613), so one value serves every image.  A device tensor is read back -- a host
+    synchronisation; the samplers convert once per call (solvers._Run), not per evaluation.  `supported`: the net has step weights."""
+    import torch
+    if skip_tuning:
+        raise NotImplementedError('skip_tuning is not supported (sfd-main/sample.py never sets it)')
+    if step_condition is None:
+        return None
+    if not supported:
+        raise ValueError('step_condition was given to a network built without step-condition weights')
+    if isinstance(step_condition, (int, float)):
+        return float(step_condition)
+    t = torch.as_tensor(step_condition).detach().reshape(-1).to(device='cpu', dtype=torch.float32)
+    if t.numel() == 0 or bool((t != t[0]).any()):
+        raise ValueError('step_condition must be one value for the whole batch')
+    return float(t[0])

@@ -17,8 +17,10 @@ the module's own weights on the first call and cached on the instance).  Nothing
 still the reference's ``solvers.py``; for the fused update kernels and the one-launch DPM-Solver++ step import
 ``diff_sampler_amd.solvers`` instead of ``solvers``.
 
+An SFD-distilled snapshot (a module with ``map_step_layer0``) is routed with its ``step_condition`` keyword too.
+
 What the route does NOT do, on purpose: it computes nothing itself, and it is INFERENCE-ONLY.  Calls with CPU tensors, with
-``augment_labels`` / other ``model_kwargs``, or that autograd would record (grad mode on and an input or a parameter of the module
+``augment_labels`` / other ``model_kwargs`` (``skip_tuning=True`` among them), or that autograd would record (grad mode on and an input or a parameter of the module
 requires grad: amed-solver-main's training path, ``solvers_amed.py:141-143`` with ``train=True``) go to the module's ORIGINAL
 ``forward`` -- the reference's own code, not a fallback of this package -- so gradients are never silently dropped; a GPU call
 whose HIP library is missing (``_lib.DsError``) or whose module ``engine.spec_from_module`` does not recognise raises, like every
@@ -136,8 +138,15 @@ def route_class(cls):
     reference_forward = cls.forward
 
     def forward(self, x, sigma, class_labels=None, force_fp32=False, **model_kwargs):
+        # an SFD-distilled net (it has map_step_layer0) takes `step_condition` -- and the `skip_tuning=False` sfd-main's sampler always
+        # passes -- on the engine; every other keyword, and these two on a module without step layers, stay the reference's business
+        step_kw = {}
+        if getattr(getattr(self, 'model', None), 'map_step_layer0', None) is not None and not model_kwargs.get('skip_tuning', False):
+            rest = {k: v for k, v in model_kwargs.items() if k not in ('step_condition', 'skip_tuning')}
+            if not rest:
+                step_kw, model_kwargs = dict(step_condition=model_kwargs.get('step_condition')), {}
         if not getattr(x, 'is_cuda', False) or model_kwargs or _needs_autograd(self, x, sigma, class_labels):
-            return reference_forward(self, x, sigma, class_labels, force_fp32=force_fp32, **model_kwargs)
+            return reference_forward(self, x, sigma, class_labels, force_fp32=force_fp32, **model_kwargs, **step_kw)
         # networks_edm.py:486: fp16 body only when the module asks for it and the caller does not force fp32
         use_fp16 = bool(getattr(self, 'use_fp16', False)) and not force_fp32
         engines = self.__dict__.setdefault(_ENGINES, {})
@@ -145,7 +154,7 @@ def route_class(cls):
         eng = engines.get(key)
         if eng is None:
             eng = engines[key] = make_engine(self, x.device, use_fp16)
-        out = eng(x, sigma, class_labels=class_labels)
+        out = eng(x, sigma, class_labels=class_labels, **step_kw)
         _fire_bottleneck_hooks(self, eng)
         return out
 

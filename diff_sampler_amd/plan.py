@@ -229,7 +229,7 @@ def _native_plan(ops):
     by_ref = {id(lib.ds_conv2d_nhwc): _lib.DS_OP_CONV2D, id(lib.ds_gemm_nt_batched): _lib.DS_OP_GEMM, id(lib.ds_gn_stats): _lib.DS_OP_GN_STATS,
               id(lib.ds_norm_act): _lib.DS_OP_NORM_ACT, id(lib.ds_gn_finalize): _lib.DS_OP_GN_FINALIZE,
               id(lib.ds_attention): _lib.DS_OP_ATTENTION, id(lib.ds_attention_f16): _lib.DS_OP_ATTENTION_F16,
-              id(lib.ds_attention_causal): _lib.DS_OP_ATTENTION_CAUSAL}
+              id(lib.ds_attention_causal): _lib.DS_OP_ATTENTION_CAUSAL, id(_lib.affine_compose): _lib.DS_OP_AFFINE_COMPOSE}
     by_val = {id(lib.ds_layernorm_rows): (_lib.DS_OP_LAYERNORM, _lib.LayerNormArgs), id(lib.ds_geglu): (_lib.DS_OP_GEGLU, _lib.GegluArgs),
               id(lib.ds_noise_embed): (_lib.DS_OP_NOISE_EMBED, _lib.NoiseEmbedArgs), id(lib.ds_stem_im2col): (_lib.DS_OP_STEM_IM2COL, _lib.StemIm2colArgs),
               id(lib.ds_layernorm_rows_f16): (_lib.DS_OP_LAYERNORM_F16, _lib.LayerNormArgs),
@@ -712,6 +712,13 @@ class Builder:
             raise NotImplementedError(f'{name}: no causal attention kernel for head size {d} over {s} tokens')
         a = AttnArgs(ptr(q), ptr(k), ptr(v), ptr(out), ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, batch, heads, s, s, d, scale)
         self.add(self.lib.ds_attention_causal, (C.byref(a),), name, keep=(a,))
+
+    def affine_compose(self, aff, ld, rows, width, step, pairs, name):
+        """Step-conditioned adaptive blocks: the step row's (scale, shift) folded in place into every row's pairs of `aff` [rows][ld]
+        (ds_affine_compose_args; `pairs` = int32 [groups][2] device table of four-column groups).  A plan operation of the library."""
+        assert aff.dtype == step.dtype == torch.float32 and pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2, name
+        a = _lib.AffineComposeArgs(ptr(aff), ld, rows, width, ptr(step), ptr(pairs), pairs.shape[0])
+        self.add(_lib.affine_compose, (C.byref(a),), name, keep=(a,))
 
     # ---- launches of libdsmetrics (csrc/metrics/fir_resample.hip): the plan then runs through Plan.run_python -----------------------------
     def fir_resample(self, x, ld_x, n, h, w, c, out, out_ld, name, up=False, pad=1, taps=(1, 3, 3, 1), bias=None, res=None, res_ld=0, scale=1.0):

@@ -232,6 +232,65 @@ SOLVER_FNS = dict(euler='euler_sampler', heun='heun_sampler', dpm='dpm_2_sampler
 
 
 # ------------------------------------------------------------------------------------------------------------------
+def load_sfd(sfd_path, device, dataset_name=None, use_fp16=False, batch_invariant=False, decode_latents=False, text_encoder=False, **cli):
+    """An SFD-distilled, step-conditioned denoiser and the sampler settings that travel with it (sfd-main/sample.py:93-139) -> (net, settings).
+      *.pkl          the reference's snapshot: ``pickle.load(f)['model']`` (duck-typed).  An EDM net goes through
+                     ``EDMDenoiser.from_reference_module``; for ms_coco the object is a ``CFGPrecond`` whose ``.model`` is the LatentDiffusion:
+                     its state dict is read like a Stable Diffusion checkpoint's (``model.diffusion_model.*`` -> ``CFGDenoiser``, first stage and
+                     text encoder for --decode_latents / --tokenizer_path) and the U-Net's spec is recovered from the module
+                     (``ldm_engine.ldm_spec_from_module``).  ``training_kwargs`` decide guidance, afs, schedule and the sigma range, and --
+                     unless ``use_step_condition`` -- num_steps; a ``dataset_name`` other than the CLI's raises (:122)
+      random:<seed>  ``EDMDenoiser.from_config(dataset_name, step_condition=True, seed=<seed>)`` (ms_coco: the SD-1.5 U-Net of create_model with
+                     step weights); every setting is the CLI's.
+    ``settings['step_condition']`` is num_steps for a step-conditioned snapshot, else None (:135); ``settings['model_source']`` 'edm' | 'ldm'."""
+    from .engine import EDMDenoiser
+    ldm = dataset_name == 'ms_coco'
+    keys = ('guidance_type', 'guidance_rate', 'afs', 'schedule_type', 'schedule_rho')
+    if sfd_path.startswith('random:'):
+        if dataset_name is None:
+            raise ValueError('--sfd_path random:<seed> needs --dataset_name')
+        seed = int(sfd_path.split(':', 1)[1])
+        if ldm:
+            from . import ldm_arch
+            assert cli.get('guidance_type') == 'cfg', 'ms_coco samples with classifier-free guidance (sample.py:112)'
+            spec = ldm_arch.ldm_unet_spec(**ldm_arch.NAMED_LDM_CONFIGS['sd15'], step_condition=True)
+            net = _cfg_denoiser(spec, ldm_arch.init_ldm_params(spec, seed=seed), None, None, True, sfd_path, seed, device, cli.get('guidance_rate'),
+                                use_fp16, batch_invariant, decode_latents, text_encoder)
+        else:
+            net = EDMDenoiser.from_config(dataset_name, seed=seed, device=device, use_fp16=bool(use_fp16),
+                                          batch_invariant=bool(batch_invariant), step_condition=True)
+        settings = {k: cli[k] for k in keys if cli.get(k) is not None}
+        settings['num_steps'] = 6 if cli.get('num_steps') is None else int(cli['num_steps'])
+        settings['step_condition'] = settings['num_steps']
+        settings['model_source'] = 'ldm' if ldm else 'edm'
+        return net, settings
+    with open(sfd_path, 'rb') as f:
+        model = pickle.load(f)['model']
+    tk = dict(model.training_kwargs)
+    if tk['dataset_name'] != dataset_name:
+        raise ValueError(f"--sfd_path: the snapshot was distilled on {tk['dataset_name']!r}, --dataset_name is {dataset_name!r}")
+    if ldm:
+        from .ldm_engine import ldm_spec_from_module
+        sd = model.model.state_dict()               # the LatentDiffusion: keyed like an SD checkpoint (ddpm.py:1399)
+        params, vae_params = split_sd_checkpoint(sd)
+        spec = ldm_spec_from_module(model.model.model.diffusion_model, int(model.img_resolution), params)
+        clip_sd = None
+        if text_encoder:
+            from . import clip_arch
+            clip_sd = clip_arch.split_cond_stage(sd)
+        net = _cfg_denoiser(spec, params, vae_params, clip_sd, False, sfd_path, 0, device, tk['guidance_rate'], use_fp16, batch_invariant,
+                            decode_latents, text_encoder)
+    else:
+        net = EDMDenoiser.from_reference_module(model, device=device, use_fp16=(True if use_fp16 else None), batch_invariant=bool(batch_invariant))
+    net.sigma_min, net.sigma_max = float(tk['sigma_min']), float(tk['sigma_max'])
+    settings = {k: tk[k] for k in keys}
+    use_step = bool(tk['use_step_condition'])
+    settings['num_steps'] = int(cli['num_steps'] if (use_step and cli.get('num_steps') is not None) else tk['num_steps'])
+    settings['step_condition'] = settings['num_steps'] if use_step else None
+    settings['model_source'] = 'ldm' if ldm else 'edm'
+    return net, settings
+
+
 def create_model(dataset_name=None, model_path=None, random_init=False, device=None, seed=0, guidance_type=None, guidance_rate=None,
                  use_fp16=False, batch_invariant=False, decode_latents=False, text_encoder=False):
     """text_encoder (ms_coco): also build the CLIP text encoder (clip_engine.ClipTextEncoder: the reference's get_learned_conditioning,
@@ -270,29 +329,9 @@ def create_model(dataset_name=None, model_path=None, random_init=False, device=N
             if text_encoder:
                 from . import clip_arch
                 clip_sd = clip_arch.split_cond_stage(sd)
-        encoder = None
-        if text_encoder:
-            from .clip_engine import ClipTextEncoder
-            if random_init or model_path is None:
-                encoder = ClipTextEncoder.from_config('sd15', seed=seed, device=device, batch_invariant=bool(batch_invariant))
-            elif not clip_sd:
-                raise ValueError(f'--tokenizer_path: {model_path} holds no cond_stage_model.transformer.* tensors')
-            else:
-                encoder = ClipTextEncoder.from_state_dict(clip_sd, device=device, batch_invariant=bool(batch_invariant))
-        decoder = None
-        if decode_latents:
-            from . import vae_arch
-            from .vae_engine import VAEDecoder
-            vspec = vae_arch.vae_decoder_spec(**vae_arch.NAMED_VAE_CONFIGS['sd15'])
-            if random_init or model_path is None:
-                vae_params = vae_arch.init_vae_params(vspec, seed=seed)
-            elif not vae_params:
-                raise ValueError(f'--decode_latents: {model_path} holds no first_stage_model.decoder.* tensors')
-            else:
-                vae_params = vae_arch.vae_params_from_state_dict(vspec, vae_params)
-            decoder = VAEDecoder(vspec, vae_params, device, use_fp16=bool(use_fp16), batch_invariant=bool(batch_invariant))
-        return CFGDenoiser(spec, params, device, guidance_rate=(7.5 if guidance_rate is None else guidance_rate), use_fp16=bool(use_fp16),
-                           batch_invariant=bool(batch_invariant), decoder=decoder, text_encoder=encoder), 'ldm'
+        random = bool(random_init or model_path is None)
+        return _cfg_denoiser(spec, params, vae_params, clip_sd, random, model_path, seed, device, guidance_rate, use_fp16, batch_invariant,
+                             decode_latents, text_encoder), 'ldm'
     if dataset_name not in arch.NAMED_CONFIGS:
         raise ValueError(f'dataset {dataset_name!r}: only the EDM networks are in scope of the HIP engine '
                          f'({sorted(k for k in arch.NAMED_CONFIGS if not k.startswith("tiny"))} and ms_coco); CM / ADM-classifier-guided / LSUN-LDM models run on the reference')
@@ -304,6 +343,36 @@ def create_model(dataset_name=None, model_path=None, random_init=False, device=N
         net = EDMDenoiser.from_reference_module(ref, device=device, use_fp16=(True if use_fp16 else None), batch_invariant=bool(batch_invariant))
     net.sigma_min, net.sigma_max = 0.002, 80.0
     return net, 'edm'
+
+
+def _cfg_denoiser(spec, params, vae_params, clip_sd, random, source, seed, device, guidance_rate, use_fp16, batch_invariant, decode_latents,
+                  text_encoder):
+    """CFGDenoiser on U-Net weights `params`, with the CLIP text encoder / the AutoencoderKL decoder of create_model's docstring when asked for:
+    from `clip_sd` / `vae_params` (the tensors of `source`), or seeded random-init ones when `random`."""
+    from .ldm_engine import CFGDenoiser
+    encoder = None
+    if text_encoder:
+        from .clip_engine import ClipTextEncoder
+        if random:
+            encoder = ClipTextEncoder.from_config('sd15', seed=seed, device=device, batch_invariant=bool(batch_invariant))
+        elif not clip_sd:
+            raise ValueError(f'--tokenizer_path: {source} holds no cond_stage_model.transformer.* tensors')
+        else:
+            encoder = ClipTextEncoder.from_state_dict(clip_sd, device=device, batch_invariant=bool(batch_invariant))
+    decoder = None
+    if decode_latents:
+        from . import vae_arch
+        from .vae_engine import VAEDecoder
+        vspec = vae_arch.vae_decoder_spec(**vae_arch.NAMED_VAE_CONFIGS['sd15'])
+        if random:
+            vae_params = vae_arch.init_vae_params(vspec, seed=seed)
+        elif not vae_params:
+            raise ValueError(f'--decode_latents: {source} holds no first_stage_model.decoder.* tensors')
+        else:
+            vae_params = vae_arch.vae_params_from_state_dict(vspec, vae_params)
+        decoder = VAEDecoder(vspec, vae_params, device, use_fp16=bool(use_fp16), batch_invariant=bool(batch_invariant))
+    return CFGDenoiser(spec, params, device, guidance_rate=(7.5 if guidance_rate is None else guidance_rate), use_fp16=bool(use_fp16),
+                       batch_invariant=bool(batch_invariant), decoder=decoder, text_encoder=encoder)
 
 
 def split_sd_checkpoint(sd):
@@ -426,7 +495,7 @@ def _dist():
 
 
 def run(dataset_name=None, max_batch_size=64, seeds='0-63', grid=False, outdir=None, subdirs=True, t_steps=None, model_path=None,
-        random_init=False, device=None, predictor_path=None, **solver_kwargs):
+        random_init=False, device=None, predictor_path=None, sfd_path=None, **solver_kwargs):
     """Body of the CLI, importable (the tests call it directly)."""
     from . import solvers, solver_utils
     seeds = parse_int_list(seeds)
@@ -468,10 +537,24 @@ def run(dataset_name=None, max_batch_size=64, seeds='0-63', grid=False, outdir=N
         t_steps = None
     if dataset_name is None:
         raise ValueError('--dataset_name is required (or --predictor_path, which carries it)')
+    sfd = None
+    if sfd_path is not None:
+        # SFD (sfd-main/sample.py:93-143): the distilled net decides its sampler settings; the solver is always Euler
+        if predictor_path is not None or stub:
+            raise ValueError('--sfd_path does not combine with --predictor_path')
+        log(f'Loading distilled model from "{sfd_path}"...')
+        sfd_net, sfd = load_sfd(sfd_path, device, dataset_name=dataset_name, batch_invariant=batch_invariant, decode_latents=decode_latents,
+                                text_encoder=bool(tokenizer_path and dataset_name == 'ms_coco'), **solver_kwargs)
+        solver_kwargs = {k: v for k, v in solver_kwargs.items() if v is not None}
+        solver_kwargs.update(sfd, solver='euler', denoise_to_zero=False)
+        solver_kwargs.pop('dp', None)
+        t_steps = None
     if stub:
         import types
         net = types.SimpleNamespace(img_channels=3, img_resolution=8, label_dim=0, sigma_min=0.002, sigma_max=80.)
         solver_kwargs['model_source'] = 'stub'
+    elif sfd is not None:
+        net = sfd_net                               # (load_sfd's settings carry model_source)
     else:
         net, solver_kwargs['model_source'] = create_model(dataset_name, model_path, random_init, device,
                                                           guidance_type=solver_kwargs.get('guidance_type'),
@@ -549,8 +632,13 @@ def run(dataset_name=None, max_batch_size=64, seeds='0-63', grid=False, outdir=N
         if solver == 'deis':
             solver_kwargs['coeff_list'] = solver_utils.get_deis_coeff_list(t_steps, solver_kwargs['max_order'],
                                                                            deis_mode=solver_kwargs['deis_mode'])
+    tag = f'{solver}_nfe{nfe}'
+    if sfd is not None:         # sfd-main/sample.py:137-139, :159
+        nfe = solver_kwargs['num_steps'] - 2 if solver_kwargs['afs'] else solver_kwargs['num_steps'] - 1
+        nfe = solver_kwargs['nfe'] = 2 * nfe if dataset_name in ['ms_coco'] else nfe        # classifier-free guidance doubles it
+        tag = f"{solver}_step{solver_kwargs['num_steps']}_nfe{nfe}"
     if outdir is None:
-        outdir = os.path.join(f'./samples/grids/{dataset_name}' if grid else f'./samples/{dataset_name}', f'{solver}_nfe{nfe}')
+        outdir = os.path.join(f'./samples/grids/{dataset_name}' if grid else f'./samples/{dataset_name}', tag)
     log(f'Generating {len(seeds)} images to "{outdir}"...')
 
     n_done = 0
@@ -625,6 +713,7 @@ if click is not None:
     @click.option('--scale_dir', help='AMED random:<seed> predictor: scale_dir', type=float, default=None)
     @click.option('--scale_time', help='AMED random:<seed> predictor: scale_time', type=float, default=None)
     @click.option('--model_path', help='Network filepath', metavar='PATH|URL', type=str)
+    @click.option('--sfd_path', help='SFD-distilled step-conditioned network: snapshot (.pkl, its training_kwargs decide the sampler settings) or random:<seed>', metavar='PATH', type=str, default=None)
     @click.option('--batch', 'max_batch_size', help='Maximum batch size', metavar='INT', type=click.IntRange(min=1), default=64, show_default=True)
     @click.option('--seeds', help='Random seeds (e.g. 1,2,5-10)', metavar='LIST', type=parse_int_list, default='0-63', show_default=True)
     @click.option('--prompt', help='Prompt for Stable Diffusion sampling', metavar='STR', type=str)

@@ -29,11 +29,13 @@ __all__ = ['get_denoised', 'euler_sampler', 'heun_sampler', 'dpm_2_sampler', 'ip
            'deis_sampler', 'dpm_pp_sampler', 'unipc_sampler']
 
 
-def get_denoised(net, x, t, class_labels=None, condition=None, unconditional_condition=None):
-    """Same dispatch as the reference (solvers.py:9-14)."""
+def get_denoised(net, x, t, class_labels=None, condition=None, unconditional_condition=None, step_condition=None):
+    """Same dispatch as the reference (solvers.py:9-14; sfd-main/solvers.py:9-16 hands `step_condition` to the net -- here only when one is
+    given, so that a net of the plain protocol never sees the keyword)."""
+    kw = {} if step_condition is None else dict(step_condition=step_condition)
     if hasattr(net, 'guidance_type'):
-        return net(x, t, condition=condition, unconditional_condition=unconditional_condition)
-    return net(x, t, class_labels=class_labels)
+        return net(x, t, condition=condition, unconditional_condition=unconditional_condition, **kw)
+    return net(x, t, class_labels=class_labels, **kw)
 
 
 # The solver update of the linear solvers runs in the network head's epilogue (engine.EDMDenoiser.raw(update=...), csrc/conv3x3_thin.hip)
@@ -46,7 +48,7 @@ FUSED_UPDATES = [0]        # process-wide count of updates that ran inside a net
 class _Run:
     """State of one sampler call: evaluation, fused update, history ring, trajectory capture."""
 
-    def __init__(self, net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps):
+    def __init__(self, net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition=None):
         if not latents.is_cuda:
             raise RuntimeError('diff-sampler_amd runs on the MI355X only: latents must be a CUDA/HIP tensor '
                                '(there is no CPU fallback; use the reference for CPU runs)')
@@ -56,6 +58,12 @@ class _Run:
         self.B, self.C, self.H, self.W = self.latents.shape
         self.per_sample = self.C * self.H * self.W
         self.cl, self.cond, self.ucond = class_labels, condition, unconditional_condition
+        # SFD's step condition (sfd-main/solvers.py:84-85): handed to every evaluation of the loop, not to denoise_to_zero's (:95)
+        # An engine denoiser gets the value as ONE host float, converted here once per sampler call: a device tensor would otherwise be read
+        # back in every evaluation (a synchronisation, and not capturable); any other callable gets what the caller passed.
+        if step_condition is not None and hasattr(net, '_step_value'):
+            step_condition = net._step_value(step_condition)
+        self.skw = {} if step_condition is None else dict(step_condition=step_condition)
         self.ts = host_times(t_steps)
         self.sigma_data = float(getattr(net, 'sigma_data', 0.5))
         self.return_inters, self.return_eps = return_inters, return_eps
@@ -78,7 +86,7 @@ class _Run:
         if self._pending is not None:
             x, sigma = self._pending
             self._pending = None
-            self._f, self._plan = self.net.raw(x, sigma, self.cl)
+            self._f, self._plan = self.net.raw(x, sigma, self.cl, **self.skw)
             self._raw = True
 
     def new(self):
@@ -89,18 +97,18 @@ class _Run:
         if self.fused:
             # sigma: Python float (uniform) or a device tensor [B] (per-sample, AMED second stage)
             self._flush()
-            if self.fuse_head and self.net.head_update_ok(self.B, sigma, self.cl):
+            if self.fuse_head and self.net.head_update_ok(self.B, sigma, self.cl, **self.skw):
                 self._pending = (x, sigma)                       # deferred: see update()
                 self._f, self._raw = None, True
                 return
-            self._f, self._plan = self.net.raw(x, sigma, self.cl)
+            self._f, self._plan = self.net.raw(x, sigma, self.cl, **self.skw)
             self._raw = True
         else:
             # a denoiser that takes sigma as a host float (ldm_engine.CFGDenoiser) gets it as such: no H2D copy, no sync,
             # capturable into a hipGraph; any other callable gets the reference's 0-dim device tensor
             t = sigma if getattr(self.net, 'host_sigma_ok', False) else torch.tensor(sigma, dtype=torch.float32, device=x.device)
             self._f = get_denoised(self.net, x, t, class_labels=self.cl, condition=self.cond,
-                                   unconditional_condition=self.ucond).to(torch.float32).contiguous()
+                                   unconditional_condition=self.ucond, **self.skw).to(torch.float32).contiguous()
             self._raw = False
 
     def denoised(self, x, sigma: float) -> torch.Tensor:
@@ -128,7 +136,7 @@ class _Run:
                                          afs=False, sigma_data=self.sigma_data, m_out=m_out, store_d=store_d, coefs=coefs,
                                          coef_rows=(self.B if coefs is not None else 1))
                 self._pending = None
-                self._f, self._plan = self.net.raw(px, ps, self.cl, update=a)
+                self._f, self._plan = self.net.raw(px, ps, self.cl, update=a, **self.skw)
                 self._raw = True
                 self.fused_updates += 1
                 FUSED_UPDATES[0] += 1
@@ -160,6 +168,8 @@ class _Run:
 
     def finish(self, x, denoise_to_zero):
         if denoise_to_zero:
+            self._flush()
+            self.skw = {}
             x = self.denoised(x, self.ts[-1])
             if self.return_inters:
                 self.inters.append(x.clone())
@@ -218,10 +228,10 @@ class _Ring:
 @torch.no_grad()
 def euler_sampler(net, latents, class_labels=None, condition=None, unconditional_condition=None, num_steps=None,
                   sigma_min=0.002, sigma_max=80, schedule_type='polynomial', schedule_rho=7, afs=False,
-                  denoise_to_zero=False, return_inters=False, return_eps=False, t_steps=None, **kwargs):
+                  denoise_to_zero=False, return_inters=False, return_eps=False, t_steps=None, step_condition=None, **kwargs):
     """Euler / DDIM (solvers.py:19-96): x' = x + (t' - t) d, one launch per step."""
     t_steps = _schedule(t_steps, num_steps, sigma_min, sigma_max, latents, schedule_type, schedule_rho, net)
-    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps)
+    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition)
     ts, x = run.ts, run.x
     for i in range(len(ts) - 1):
         t, tn = ts[i], ts[i + 1]
@@ -239,10 +249,10 @@ def euler_sampler(net, latents, class_labels=None, condition=None, unconditional
 @torch.no_grad()
 def heun_sampler(net, latents, class_labels=None, condition=None, unconditional_condition=None, num_steps=None,
                  sigma_min=0.002, sigma_max=80, schedule_type='polynomial', schedule_rho=7, afs=False,
-                 denoise_to_zero=False, return_inters=False, return_eps=False, t_steps=None, **kwargs):
+                 denoise_to_zero=False, return_inters=False, return_eps=False, t_steps=None, step_condition=None, **kwargs):
     """Heun (solvers.py:101-183): Euler predictor + trapezoid corrector, two launches per step."""
     t_steps = _schedule(t_steps, num_steps, sigma_min, sigma_max, latents, schedule_type, schedule_rho, net)
-    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps)
+    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition)
     ts, x = run.ts, run.x
     d1, xt = run.new(), run.new()
     for i in range(len(ts) - 1):
@@ -262,10 +272,10 @@ def heun_sampler(net, latents, class_labels=None, condition=None, unconditional_
 @torch.no_grad()
 def dpm_2_sampler(net, latents, class_labels=None, condition=None, unconditional_condition=None, num_steps=None,
                   sigma_min=0.002, sigma_max=80, schedule_type='polynomial', schedule_rho=7, afs=False,
-                  denoise_to_zero=False, return_inters=False, return_eps=False, r=0.5, t_steps=None, **kwargs):
+                  denoise_to_zero=False, return_inters=False, return_eps=False, r=0.5, t_steps=None, step_condition=None, **kwargs):
     """DPM-Solver-2 (solvers.py:188-273): midpoint at t_mid = t'^r t^(1-r)."""
     t_steps = _schedule(t_steps, num_steps, sigma_min, sigma_max, latents, schedule_type, schedule_rho, net)
-    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps)
+    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition)
     ts, x = run.ts, run.x
     d1, xt = run.new(), run.new()
     for i in range(len(ts) - 1):
@@ -308,11 +318,11 @@ def _multistep_d(run, afs_rule, order_coeffs, max_order, denoise_to_zero, return
 @torch.no_grad()
 def ipndm_sampler(net, latents, class_labels=None, condition=None, unconditional_condition=None, num_steps=None,
                   sigma_min=0.002, sigma_max=80, schedule_type='polynomial', schedule_rho=7, afs=False,
-                  denoise_to_zero=False, return_inters=False, return_eps=False, max_order=4, t_steps=None, **kwargs):
+                  denoise_to_zero=False, return_inters=False, return_eps=False, max_order=4, t_steps=None, step_condition=None, **kwargs):
     """Improved PNDM (solvers.py:278-374): fixed-step Adams-Bashforth on d, order <= 4."""
     assert max_order >= 1 and max_order <= 4
     t_steps = _schedule(t_steps, num_steps, sigma_min, sigma_max, latents, schedule_type, schedule_rho, net)
-    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps)
+    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition)
     ts = run.ts
     return _multistep_d(run, lambda i, nh: afs and i == 0, lambda i, order: ipndm_coeffs(order, ts[i + 1] - ts[i]),
                         max_order, denoise_to_zero, return_inters, return_eps)
@@ -321,11 +331,11 @@ def ipndm_sampler(net, latents, class_labels=None, condition=None, unconditional
 @torch.no_grad()
 def ipndm_v_sampler(net, latents, class_labels=None, condition=None, unconditional_condition=None, num_steps=None,
                     sigma_min=0.002, sigma_max=80, schedule_type='polynomial', schedule_rho=7, afs=False,
-                    denoise_to_zero=False, return_inters=False, return_eps=False, max_order=4, t_steps=None, **kwargs):
+                    denoise_to_zero=False, return_inters=False, return_eps=False, max_order=4, t_steps=None, step_condition=None, **kwargs):
     """Variable-step Adams-Bashforth (solvers.py:379-499)."""
     assert max_order >= 1 and max_order <= 4
     t_steps = _schedule(t_steps, num_steps, sigma_min, sigma_max, latents, schedule_type, schedule_rho, net)
-    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps)
+    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition)
     ts = run.ts
     return _multistep_d(run, lambda i, nh: afs and nh == 0, lambda i, order: ipndm_v_coeffs(order, ts, i),
                         max_order, denoise_to_zero, return_inters, return_eps)
@@ -335,12 +345,12 @@ def ipndm_v_sampler(net, latents, class_labels=None, condition=None, uncondition
 def deis_sampler(net, latents, class_labels=None, condition=None, unconditional_condition=None, num_steps=None,
                  sigma_min=0.002, sigma_max=80, schedule_type='polynomial', schedule_rho=7, afs=False,
                  denoise_to_zero=False, return_inters=False, return_eps=False, max_order=4, coeff_list=None, t_steps=None,
-                 **kwargs):
+                 step_condition=None, **kwargs):
     """DEIS (solvers.py:504-607): x' = x + sum_j C[i][j] d_{n-j}; C from ``get_deis_coeff_list``."""
     assert max_order >= 1 and max_order <= 4
     assert coeff_list is not None
     t_steps = _schedule(t_steps, num_steps, sigma_min, sigma_max, latents, schedule_type, schedule_rho, net)
-    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps)
+    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition)
     ts = run.ts
 
     def coeffs(i, order):
@@ -359,12 +369,12 @@ def deis_sampler(net, latents, class_labels=None, condition=None, unconditional_
 def dpm_pp_sampler(net, latents, class_labels=None, condition=None, unconditional_condition=None, num_steps=None,
                    sigma_min=0.002, sigma_max=80, schedule_type='polynomial', schedule_rho=7, afs=False,
                    denoise_to_zero=False, return_inters=False, return_eps=False, max_order=3, predict_x0=True,
-                   lower_order_final=True, t_steps=None, **kwargs):
+                   lower_order_final=True, t_steps=None, step_condition=None, **kwargs):
     """Multistep DPM-Solver++ (solvers.py:613-713).  One launch per step in both modes: x0-prediction fuses D -> dynamic
     threshold -> 1/2M/3M update per sample (ds_dpmpp_x0_step; three launches only for samples too large for one workgroup's LDS)."""
     assert max_order >= 1 and max_order <= 3
     t_steps = _schedule(t_steps, num_steps, sigma_min, sigma_max, latents, schedule_type, schedule_rho, net)
-    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps)
+    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition)
     ts, x = run.ts, run.x
     ring = _Ring(run, 3)
     t_hist: List[float] = []
@@ -414,11 +424,11 @@ def dpm_pp_sampler(net, latents, class_labels=None, condition=None, unconditiona
 def unipc_sampler(net, latents, class_labels=None, condition=None, unconditional_condition=None, num_steps=None,
                   sigma_min=0.002, sigma_max=80, schedule_type='polynomial', schedule_rho=7, afs=False,
                   denoise_to_zero=False, return_inters=False, return_eps=False, max_order=3, predict_x0=True,
-                  lower_order_final=True, variant='bh2', t_steps=None, **kwargs):
+                  lower_order_final=True, variant='bh2', t_steps=None, step_condition=None, **kwargs):
     """UniPC predictor-corrector (solvers.py:718-821; update rule solver_utils.py:174-287)."""
     assert max_order > 0 and max_order < 4
     t_steps = _schedule(t_steps, num_steps, sigma_min, sigma_max, latents, schedule_type, schedule_rho, net)
-    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, False)
+    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, False, step_condition)
     ts, x = run.ts, run.x
 
     def model_out(xq, tq, use_afs=False):

@@ -685,6 +685,17 @@ typedef struct ds_quick_gelu_args { const float* x; int ldx; float* y; int ldy; 
 typedef struct ds_channel_mean_f16_args { const void* x; int ld; int c; long long rows; float* out; } ds_channel_mean_f16_args;
 typedef struct ds_cfg_sigma_rows_args { const float* sigma; int n; const float* log_alpha; int m; int copies; float* sigma_out;
                                         float* c_noise_out; } ds_cfg_sigma_rows_args;
+/* Step-conditioned adaptive blocks (sfd-main networks_edm.py:174-179: silu(shift_step + (shift + norm1(x) (scale + 1)) (scale_step + 1))).  A plan
+ * operation like the two above.  `aff` = the affine launch's output [rows][ld], `step` = ONE row in the same column layout (the step
+ * embedding's projection), `pairs` = a device table of `groups` int2 {scale column, shift column}, each the first of FOUR consecutive
+ * columns (both multiples of 4, both + 4 <= width; an entry that is not is skipped).  For r < rows and every column c of every group, in place:
+ *     aff[r][scale + c] = fmaf(1 + s, 1 + ss, -1)      aff[r][shift + c] = fmaf(h, 1 + ss, hs)
+ * (s, h = the row's pair, ss, hs = the step row's), so that the consumers' (1 + scale') n + shift' is the two-stage expression: ds_gn_finalize,
+ * ds_norm_act and the convolutions' halo planes are untouched.  One thread per group, 16-byte accesses only (there is no scalar form).
+ * DS_E_ARG: a NULL pointer, rows <= 0, groups <= 0.  DS_E_SHAPE: width <= 0, width % 4, width > ld.  DS_E_ALIGN: ld % 4, aff / step off 16
+ * bytes, pairs off 8 bytes.  Nothing is launched then.  No column outside the table's groups is read or written. */
+typedef struct ds_affine_compose_args { float* aff; int ld; int rows; int width; const float* step; const int* pairs; int groups;
+                                        } ds_affine_compose_args;
 
 enum { DS_OP_CONV2D = 1,        /* ds_conv_args        -> ds_conv2d_nhwc      */
        DS_OP_GEMM = 2,          /* ds_gemm_args        -> ds_gemm_nt_batched  */
@@ -703,7 +714,9 @@ enum { DS_OP_CONV2D = 1,        /* ds_conv_args        -> ds_conv2d_nhwc      */
        DS_OP_ATTENTION_CAUSAL = 15, /* ds_attn_args    -> ds_attention_causal */
        DS_OP_QUICK_GELU = 16,   /* ds_quick_gelu_args  -> ds_quick_gelu       */
        DS_OP_CHANNEL_MEAN_F16 = 17, /* ds_channel_mean_f16_args -> channel mean of fp16 rows (norm_act.hip) */
-       DS_OP_CFG_SIGMA_ROWS = 18    /* ds_cfg_sigma_rows_args -> sigma and c_noise rows from device sigmas (solver.hip) */ };
+       DS_OP_CFG_SIGMA_ROWS = 18,   /* ds_cfg_sigma_rows_args -> sigma and c_noise rows from device sigmas (solver.hip) */
+       /* 19 is not assigned: the suite pins it as "no such operation" (tests/test_amed_ldm_cpu.py) */
+       DS_OP_AFFINE_COMPOSE = 20    /* ds_affine_compose_args -> step scale / shift folded into the affine rows (norm_act.hip) */ };
 
 typedef struct ds_plan ds_plan;
 DS_API int ds_plan_create(ds_plan** out);

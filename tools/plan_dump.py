@@ -38,7 +38,8 @@ from diff_sampler_amd import _lib, _metrics_lib  # noqa: E402
 WRITES = {'ds_conv2d_nhwc': ('out', 'stats_out'), 'ds_norm_act': ('out', 'raw_out'), 'ds_gn_stats': ('mean', 'rstd', 'coefs'),
           'ds_gn_finalize': ('mean', 'rstd', 'coefs'), 'ds_attention': ('out',), 'ds_attention_f16': ('out',), 'ds_gemm_nt_batched': ('c',),
           'ds_layernorm_rows': ('y',), 'ds_layernorm_rows_f16': ('y',), 'ds_layernorm_rows_f16io': ('y',), 'ds_geglu': ('y',),
-          'ds_noise_embed': ('out',), 'ds_stem_im2col': ('out',), 'dsm_fir_resample': ('out',), 'dsm_zero_border': ('out',)}
+          'ds_noise_embed': ('out',), 'ds_stem_im2col': ('out',), 'dsm_fir_resample': ('out',), 'dsm_zero_border': ('out',),
+          'affine_compose': ('aff',)}         # (in place: _lib.affine_compose, the DS_OP_AFFINE_COMPOSE launch of the step-conditioned ADM plans)
 SCRATCH = ('workspace', 'partial', 'counters', 'update')
 BY_VALUE = {'ds_layernorm_rows': _lib.LayerNormArgs, 'ds_layernorm_rows_f16': _lib.LayerNormArgs, 'ds_layernorm_rows_f16io': _lib.LayerNormArgs,
             'ds_geglu': _lib.GegluArgs, 'ds_noise_embed': _lib.NoiseEmbedArgs, 'ds_stem_im2col': _lib.StemIm2colArgs,
