@@ -193,6 +193,28 @@ DSM_API int dsm_fir_resample_supported(int up, int pad, int h, int w, int c);
  * pointer, x == out, a non-positive size, p < 0;  DS_E_SHAPE: a side or p above 32768, more than 2^31 - 1 output pixels. */
 DSM_API int dsm_zero_border(const float* x, float* out, long long outer, int h, int w, int inner, int p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------------
+ * Trajectory analysis (diff-analyzer-main; csrc/metrics/traj.hip; added without a version step: nothing existing changed).
+ *
+ * dsm_traj_gram: traj is a sampler's stacked fp32 trajectory [n_pts][batch][per], contiguous and read in place (point t of sample b at
+ * (t * batch + b) * per).  For the samples b in [b0, b0 + nb):
+ *     gram[b - b0][t][s] = sum_e (x[t,b,e] - x[n_pts-1,b,e]) (x[s,b,e] - x[n_pts-1,b,e])          [nb][n_pts][n_pts] fp64
+ * with the differences formed in fp64 (exact) and products and sums on v_mfma_f64_16x16x4_f64.  Tiles on and below the diagonal are computed
+ * and mirrored: gram[t][s] and gram[s][t] are the same bits.  The contraction over `per` is split over dsm_traj_gram_splits(n_pts, per)
+ * workgroups per tile -- a function of these two sizes only -- whose partials go to the workspace and are added in a fixed order: a sample's
+ * matrix is the same bits for any batch, b0 and nb, and from run to run.  Any n_pts >= 2, per >= 1, batch >= 1.
+ * workspace: dsm_traj_gram_workspace_bytes(n_pts, per, nb) bytes, 8-byte aligned (DS_E_ALIGN); where that is 0 (no split) it is not read and
+ * may be NULL.  DS_E_ARG: NULL traj / gram, n_pts < 2, a non-positive size, [b0, b0 + nb) outside the batch, workspace missing or too small;
+ * DS_E_SHAPE: n_pts > 32768, nb > 65535, more than 2^39 output elements (the workspace and split queries answer the same codes). */
+DSM_API int dsm_traj_gram(const float* traj, int n_pts, int batch, long long per, int b0, int nb, double* gram, void* workspace,
+                          long long workspace_bytes, void* stream);
+DSM_API long long dsm_traj_gram_workspace_bytes(int n_pts, long long per, int nb);
+DSM_API int dsm_traj_gram_splits(int n_pts, long long per);
+
+/* out[r] = sum_e (a[r,e] - b[r,e])^2 for r < rows, or sum_e a[r,e]^2 with b_or_null == NULL; rows of `per` contiguous floats.  Differences and
+ * sums in fp64, one workgroup per row, a fixed order.  DS_E_ARG: NULL a / out, rows or per < 1;  DS_E_SHAPE: rows > 2^31 - 1. */
+DSM_API int dsm_row_sqdist(const float* a, const float* b_or_null, long long rows, long long per, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

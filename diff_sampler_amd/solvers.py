@@ -12,6 +12,10 @@ protocol: ``net(x, t, class_labels=...)`` / ``condition=...``) its denoised outp
 Contract kept from the reference: signatures and defaults, ``**kwargs`` swallowing, returns
 (tensor | trajectory | (trajectory, eps)), ``latents`` not mutated, asserts on ``max_order`` ranges, quirks such as
 ``ipndm_sampler(max_order=1)`` raising ``IndexError`` and ``dpm_pp_sampler`` needing ``num_steps``.
+
+``return_denoised`` (diff-analyzer-main/solvers.py; the seven samplers it has, default False): with ``return_inters=True`` the call returns
+``(inter_xt, inter_denoised, inter_eps)`` -- the denoised output the reference appends at every step (``_Run.capture``), ``inter_eps``
+None unless ``return_eps`` is set.  Capturing is not a timed path: the captured evaluation leaves the head-fused form.
 """
 from __future__ import annotations
 
@@ -48,7 +52,8 @@ FUSED_UPDATES = [0]        # process-wide count of updates that ran inside a net
 class _Run:
     """State of one sampler call: evaluation, fused update, history ring, trajectory capture."""
 
-    def __init__(self, net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition=None):
+    def __init__(self, net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition=None,
+                 return_denoised=False):
         if not latents.is_cuda:
             raise RuntimeError('diff-sampler_amd runs on the MI355X only: latents must be a CUDA/HIP tensor '
                                '(there is no CPU fallback; use the reference for CPU runs)')
@@ -66,9 +71,10 @@ class _Run:
         self.skw = {} if step_condition is None else dict(step_condition=step_condition)
         self.ts = host_times(t_steps)
         self.sigma_data = float(getattr(net, 'sigma_data', 0.5))
-        self.return_inters, self.return_eps = return_inters, return_eps
+        self.return_inters, self.return_eps, self.return_denoised = return_inters, return_eps, return_denoised
         self.inters: List[torch.Tensor] = []
         self.eps: List[torch.Tensor] = []
+        self.den: List[torch.Tensor] = []
         self.x = torch.empty_like(self.latents)
         ops.scale(self.latents, self.ts[0], self.x)                # x_0 = latents * t_0 (solvers.py:68)
         if return_inters:
@@ -160,6 +166,23 @@ class _Run:
                                  f_ld=0, hist=list(hist), hcoefs=hc, afs=afs, sigma_data=self.sigma_data, m_out=m_out, store_d=False)
         ops.dpmpp_x0_step(a)
 
+    def capture(self, x, sigma: float, afs=False):
+        """return_denoised: keep D(x; sigma) of the evaluation just made (diff-analyzer-main/solvers.py appends `denoised` once per step); with
+        afs, the x - t d that its dpm_pp_sampler forms instead (:729-731).  D needs F in memory, so a noted evaluation runs on its own here and
+        its update becomes a launch of its own: the same arithmetic (ds_upd_element), so the trajectory's bits do not change."""
+        if not self.return_denoised:
+            return
+        if afs:
+            out = self.new()
+            self.update(xe=x, xb=x, t=sigma, sigma=sigma, cx=0.0, cm=1.0, x_out=None, m_out=out, store_d=False, afs=True)
+        elif self._raw:
+            self._flush()
+            out = self.new()
+            self.update(xe=x, xb=x, t=1.0, sigma=sigma, cx=0.0, cm=1.0, x_out=None, m_out=out, store_d=False)
+        else:
+            out = self._f.clone()
+        self.den.append(out)
+
     def record(self, x, d=None):
         if self.return_inters:
             self.inters.append(x.clone())
@@ -173,13 +196,30 @@ class _Run:
             x = self.denoised(x, self.ts[-1])
             if self.return_inters:
                 self.inters.append(x.clone())
+            if self.return_denoised:
+                self.den.append(x.clone())
         dev = self.latents.device
         if self.return_inters:
             tr = torch.stack(self.inters, dim=0).to(dev)
+            if self.return_denoised:         # the reference's triple; inter_eps is None unless return_eps asked for it
+                return tr, torch.stack(self.den, dim=0).to(dev), (torch.stack(self.eps, dim=0).to(dev) if self.return_eps else None)
             if self.return_eps:
                 return tr, torch.stack(self.eps, dim=0).to(dev)
             return tr
         return x
+
+
+def _check_capture(return_inters, return_denoised, afs, afs_has_denoised=False):
+    """The rules of return_denoised, answered before anything touches the device.  With afs the reference's first step makes no evaluation:
+    its dpm_pp_sampler records x - t d (:729-731), heun and dpm_2 record their second evaluation as in every step, and euler, ipndm, ipndm_v
+    and deis read a name that was never bound."""
+    if not return_denoised:
+        return
+    if not return_inters:
+        raise ValueError('return_denoised=True needs return_inters=True: the denoised outputs are returned next to the trajectory')
+    if afs and not afs_has_denoised:
+        raise ValueError('return_denoised=True with afs=True: the analytical first step evaluates no network, this solver has no denoised '
+                         'output to record for it')
 
 
 _FUSED_X0_MAX = 37000      # elements per sample the one-launch data-prediction step holds in LDS (ds_dpmpp_x0_step)
@@ -228,16 +268,18 @@ class _Ring:
 @torch.no_grad()
 def euler_sampler(net, latents, class_labels=None, condition=None, unconditional_condition=None, num_steps=None,
                   sigma_min=0.002, sigma_max=80, schedule_type='polynomial', schedule_rho=7, afs=False,
-                  denoise_to_zero=False, return_inters=False, return_eps=False, t_steps=None, step_condition=None, **kwargs):
+                  denoise_to_zero=False, return_inters=False, return_eps=False, return_denoised=False, t_steps=None, step_condition=None, **kwargs):
     """Euler / DDIM (solvers.py:19-96): x' = x + (t' - t) d, one launch per step."""
+    _check_capture(return_inters, return_denoised, afs)
     t_steps = _schedule(t_steps, num_steps, sigma_min, sigma_max, latents, schedule_type, schedule_rho, net)
-    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition)
+    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition, return_denoised)
     ts, x = run.ts, run.x
     for i in range(len(ts) - 1):
         t, tn = ts[i], ts[i + 1]
         use_afs = afs and i == 0
         if not use_afs:
             run.evaluate(x, t)
+            run.capture(x, t)
         xn = run.new() if return_inters else x
         d = run.new() if return_eps else None
         run.update(xe=x, xb=x, t=t, sigma=t, cx=1.0, cm=(tn - t), x_out=xn, m_out=d, afs=use_afs)
@@ -249,10 +291,11 @@ def euler_sampler(net, latents, class_labels=None, condition=None, unconditional
 @torch.no_grad()
 def heun_sampler(net, latents, class_labels=None, condition=None, unconditional_condition=None, num_steps=None,
                  sigma_min=0.002, sigma_max=80, schedule_type='polynomial', schedule_rho=7, afs=False,
-                 denoise_to_zero=False, return_inters=False, return_eps=False, t_steps=None, step_condition=None, **kwargs):
+                 denoise_to_zero=False, return_inters=False, return_eps=False, return_denoised=False, t_steps=None, step_condition=None, **kwargs):
     """Heun (solvers.py:101-183): Euler predictor + trapezoid corrector, two launches per step."""
+    _check_capture(return_inters, return_denoised, afs, afs_has_denoised=True)
     t_steps = _schedule(t_steps, num_steps, sigma_min, sigma_max, latents, schedule_type, schedule_rho, net)
-    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition)
+    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition, return_denoised)
     ts, x = run.ts, run.x
     d1, xt = run.new(), run.new()
     for i in range(len(ts) - 1):
@@ -262,6 +305,7 @@ def heun_sampler(net, latents, class_labels=None, condition=None, unconditional_
             run.evaluate(x, t)
         run.update(xe=x, xb=x, t=t, sigma=t, cx=1.0, cm=(tn - t), x_out=xt, m_out=d1, afs=use_afs)
         run.evaluate(xt, tn)
+        run.capture(xt, tn)                 # the corrector's evaluation (diff-analyzer-main/solvers.py:187-193)
         xn = run.new() if return_inters else x
         run.update(xe=xt, xb=x, t=tn, sigma=tn, cx=1.0, cm=0.5 * (tn - t), x_out=xn, hist=[d1], ch=[0.5 * (tn - t)])
         x = xn
@@ -272,10 +316,11 @@ def heun_sampler(net, latents, class_labels=None, condition=None, unconditional_
 @torch.no_grad()
 def dpm_2_sampler(net, latents, class_labels=None, condition=None, unconditional_condition=None, num_steps=None,
                   sigma_min=0.002, sigma_max=80, schedule_type='polynomial', schedule_rho=7, afs=False,
-                  denoise_to_zero=False, return_inters=False, return_eps=False, r=0.5, t_steps=None, step_condition=None, **kwargs):
+                  denoise_to_zero=False, return_inters=False, return_eps=False, return_denoised=False, r=0.5, t_steps=None, step_condition=None, **kwargs):
     """DPM-Solver-2 (solvers.py:188-273): midpoint at t_mid = t'^r t^(1-r)."""
+    _check_capture(return_inters, return_denoised, afs, afs_has_denoised=True)
     t_steps = _schedule(t_steps, num_steps, sigma_min, sigma_max, latents, schedule_type, schedule_rho, net)
-    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition)
+    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition, return_denoised)
     ts, x = run.ts, run.x
     d1, xt = run.new(), run.new()
     for i in range(len(ts) - 1):
@@ -286,6 +331,7 @@ def dpm_2_sampler(net, latents, class_labels=None, condition=None, unconditional
         tm = (tn ** r) * (t ** (1 - r))
         run.update(xe=x, xb=x, t=t, sigma=t, cx=1.0, cm=(tm - t), x_out=xt, m_out=d1, afs=use_afs)
         run.evaluate(xt, tm)
+        run.capture(xt, tm)                 # the midpoint evaluation (diff-analyzer-main/solvers.py:283-289)
         xn = run.new() if return_inters else x
         run.update(xe=xt, xb=x, t=tm, sigma=tm, cx=1.0, cm=(tn - t) * (1 / (2 * r)), x_out=xn, hist=[d1],
                    ch=[(tn - t) * (1 - 1 / (2 * r))])
@@ -303,6 +349,7 @@ def _multistep_d(run, afs_rule, order_coeffs, max_order, denoise_to_zero, return
         use_afs = afs_rule(i, len(ring))
         if not use_afs:
             run.evaluate(x, t)
+            run.capture(x, t)
         order = min(max_order, i + 1)
         cs = order_coeffs(i, order)
         hist = ring.newest_first()[:order - 1]
@@ -318,11 +365,12 @@ def _multistep_d(run, afs_rule, order_coeffs, max_order, denoise_to_zero, return
 @torch.no_grad()
 def ipndm_sampler(net, latents, class_labels=None, condition=None, unconditional_condition=None, num_steps=None,
                   sigma_min=0.002, sigma_max=80, schedule_type='polynomial', schedule_rho=7, afs=False,
-                  denoise_to_zero=False, return_inters=False, return_eps=False, max_order=4, t_steps=None, step_condition=None, **kwargs):
+                  denoise_to_zero=False, return_inters=False, return_eps=False, return_denoised=False, max_order=4, t_steps=None, step_condition=None, **kwargs):
     """Improved PNDM (solvers.py:278-374): fixed-step Adams-Bashforth on d, order <= 4."""
     assert max_order >= 1 and max_order <= 4
+    _check_capture(return_inters, return_denoised, afs)
     t_steps = _schedule(t_steps, num_steps, sigma_min, sigma_max, latents, schedule_type, schedule_rho, net)
-    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition)
+    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition, return_denoised)
     ts = run.ts
     return _multistep_d(run, lambda i, nh: afs and i == 0, lambda i, order: ipndm_coeffs(order, ts[i + 1] - ts[i]),
                         max_order, denoise_to_zero, return_inters, return_eps)
@@ -331,11 +379,12 @@ def ipndm_sampler(net, latents, class_labels=None, condition=None, unconditional
 @torch.no_grad()
 def ipndm_v_sampler(net, latents, class_labels=None, condition=None, unconditional_condition=None, num_steps=None,
                     sigma_min=0.002, sigma_max=80, schedule_type='polynomial', schedule_rho=7, afs=False,
-                    denoise_to_zero=False, return_inters=False, return_eps=False, max_order=4, t_steps=None, step_condition=None, **kwargs):
+                    denoise_to_zero=False, return_inters=False, return_eps=False, return_denoised=False, max_order=4, t_steps=None, step_condition=None, **kwargs):
     """Variable-step Adams-Bashforth (solvers.py:379-499)."""
     assert max_order >= 1 and max_order <= 4
+    _check_capture(return_inters, return_denoised, afs)
     t_steps = _schedule(t_steps, num_steps, sigma_min, sigma_max, latents, schedule_type, schedule_rho, net)
-    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition)
+    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition, return_denoised)
     ts = run.ts
     return _multistep_d(run, lambda i, nh: afs and nh == 0, lambda i, order: ipndm_v_coeffs(order, ts, i),
                         max_order, denoise_to_zero, return_inters, return_eps)
@@ -344,13 +393,14 @@ def ipndm_v_sampler(net, latents, class_labels=None, condition=None, uncondition
 @torch.no_grad()
 def deis_sampler(net, latents, class_labels=None, condition=None, unconditional_condition=None, num_steps=None,
                  sigma_min=0.002, sigma_max=80, schedule_type='polynomial', schedule_rho=7, afs=False,
-                 denoise_to_zero=False, return_inters=False, return_eps=False, max_order=4, coeff_list=None, t_steps=None,
+                 denoise_to_zero=False, return_inters=False, return_eps=False, return_denoised=False, max_order=4, coeff_list=None, t_steps=None,
                  step_condition=None, **kwargs):
     """DEIS (solvers.py:504-607): x' = x + sum_j C[i][j] d_{n-j}; C from ``get_deis_coeff_list``."""
     assert max_order >= 1 and max_order <= 4
     assert coeff_list is not None
+    _check_capture(return_inters, return_denoised, afs)
     t_steps = _schedule(t_steps, num_steps, sigma_min, sigma_max, latents, schedule_type, schedule_rho, net)
-    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition)
+    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition, return_denoised)
     ts = run.ts
 
     def coeffs(i, order):
@@ -368,13 +418,14 @@ def deis_sampler(net, latents, class_labels=None, condition=None, unconditional_
 @torch.no_grad()
 def dpm_pp_sampler(net, latents, class_labels=None, condition=None, unconditional_condition=None, num_steps=None,
                    sigma_min=0.002, sigma_max=80, schedule_type='polynomial', schedule_rho=7, afs=False,
-                   denoise_to_zero=False, return_inters=False, return_eps=False, max_order=3, predict_x0=True,
+                   denoise_to_zero=False, return_inters=False, return_eps=False, return_denoised=False, max_order=3, predict_x0=True,
                    lower_order_final=True, t_steps=None, step_condition=None, **kwargs):
     """Multistep DPM-Solver++ (solvers.py:613-713).  One launch per step in both modes: x0-prediction fuses D -> dynamic
     threshold -> 1/2M/3M update per sample (ds_dpmpp_x0_step; three launches only for samples too large for one workgroup's LDS)."""
     assert max_order >= 1 and max_order <= 3
+    _check_capture(return_inters, return_denoised, afs, afs_has_denoised=True)
     t_steps = _schedule(t_steps, num_steps, sigma_min, sigma_max, latents, schedule_type, schedule_rho, net)
-    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition)
+    run = _Run(net, latents, class_labels, condition, unconditional_condition, t_steps, return_inters, return_eps, step_condition, return_denoised)
     ts, x = run.ts, run.x
     ring = _Ring(run, 3)
     t_hist: List[float] = []
@@ -383,6 +434,7 @@ def dpm_pp_sampler(net, latents, class_labels=None, condition=None, unconditiona
         use_afs = afs and i == 0
         if not use_afs:
             run.evaluate(x, t)
+        run.capture(x, t, afs=use_afs)      # before the dynamic threshold, as the reference records it
         t_hist = (t_hist + [t])[-3:]
         if lower_order_final:
             order = i + 1 if i + 1 < max_order else min(max_order, num_steps - (i + 1))
