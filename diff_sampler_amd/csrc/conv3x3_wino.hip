@@ -6,6 +6,12 @@
 //     Y = A^T [ sum_c (G g_c G^T) . (B^T d_c B) ] A          (. = elementwise over the 16 positions; entries of A, B: 0, +-1; of G: 0, +-1, +-1/2)
 // i.e. 16 independent [tiles x channels] x [channels x cout] products, one per position of the 4 x 4 transformed patch.
 //
+// TILE SHAPES.  Two kernels, bit-identical in `out` and in the statistics (tests/test_hip_wino_n128.py); launch_conv3x3_wino chooses:
+//   wino_n128_kernel     32 tiles x 128 channels, the DEFAULT at every image width (profiles/wino_n128_ab.txt: - 4.3 ... - 5.1 % per layer at
+//                        16 and 32 columns, - 10 % at 64).  Described under "The 32 x 128 shape" below, in terms of the first kernel.
+//   conv3x3_wino_kernel  64 tiles x 64 channels, the first kernel, described next.  ds_conv_tune.variant bit 10 (1024) selects it: A/B
+//                        timing in one process, the bit comparison of the tests, and the timing ablations (-DDS_CONV_ABLATIONS).
+//
 //   workgroup = 64 tiles (256 output pixels of ONE image: TH = 256 / W rows x W columns, the 256-pixel M tile of the direct kernel) x 64
 //               output channels, four waves (2 x 2), one per SIMD; a wave holds ALL 16 positions of its 32 tiles x 32 channels
 //               (16 x f32x16 = 256 accumulator registers), so the output transform is lane-local
@@ -65,6 +71,39 @@
 // halo and weight requests in front of the epilogue and its halo stores in the epilogue's middle, epilogue staging moved to Vs[1]) was
 // built bit-identical and measured: + 1 % per layer by itself, nothing gained by the look-ahead (profiles/wino_persist_ab.txt).  It is
 // in no committed source.
+//
+// THE 32 x 128 SHAPE (wino_n128_kernel).  Every layer on this route has cout % 256 == 0, so on 64-column workgroups FOUR workgroups load the
+// same halo, apply the same GroupNorm affine + SiLU to it and run the same input transform: the input side of every slab is computed four
+// times, in vector instructions that add their cycles to the MFMAs' (profiles/wino_kloop_ab.txt).  This shape computes it twice:
+//   workgroup = 32 tiles (128 output pixels of ONE image: 128 / W rows x W columns) x 128 output channels, four waves laid out 1 x 4, one
+//               per SIMD: every wave takes the SAME 32 tiles and owns 32 of the 128 channels, all 16 positions (256 accumulators, the
+//               output transform lane-local as before).  The workgroup count of a layer is unchanged (M / 128 x N / 128).
+//   halo      = (128 / W + 2) x (W + 2) pixels: 204 at 32 columns (340 on the first shape), 180 at 16 (324), 264 at 64 (396), i.e. 2 active
+//               float4 slots per thread and slab at 16 and 32 columns and 3 at 64 (first kernel: 3 and 4).  The chain is the first kernel's.
+//   transform = 32 tiles x 4 channel pairs = 128 items, each split over TWO threads by rows of B^T d B: a thread reads three rows of d
+//               (12 ds_read_b64), makes rows {0, 1} or {2, 3} of B^T d and their eight positions (16 packed adds, 8 ds_write_b64; the
+//               first kernel: 16 reads, 32 adds, 16 writes).  Which row pair is uniform per wave -- a scalar branch -- and every wave does
+//               the same amount: the barrier waits for the slowest.  Each value is made by the first kernel's operations on its operands.
+//   weights   = NOT through the LDS.  In the 1 x 4 layout a wave's 32 columns of U belong to that wave alone, so LDS staging would share
+//               nothing (and two doubled 64 KiB images would not fit beside V and the halo).  ops.pack_conv_weight_wino stores each
+//               (position, kh) as 64 rows x 16 bytes per 64-column image: a wave's B fragment of a position is ONE global_load_dwordx4 per
+//               lane, 512 contiguous bytes per kh, from image 2 nt + (wave >> 1), rows 32 (wave & 1) .. + 31 -- no repacking.  The four
+//               loads of position group g+1 are issued in the first four slots of group g (group 0 of slab s+1 in group 3 of slab s),
+//               16 MFMAs ~ 1 000 cycles ahead of their use, scalar base + 32-bit lane offset.  U is read from L2 at twice the first
+//               kernel's rate; the workgroups of an XCD walk the slabs together.
+//   LDS       = Vs doubled (2 x 16 KiB) and Hs doubled: 44 320 ... 49 696 bytes.  A fragment reads as before, one ds_read_b128 per position.
+//   order     = the first kernel's "who orders what" without Us: ONE barrier per slab and NO `vmcnt(0)` in the loop -- every global load
+//               targets registers of the wave that uses them, and the compiler's counted waits stand in front of the first use (after the
+//               prologue's single `vmcnt(0)` the loop's waits follow from its own order of loads).  Slots: 16 g + 0 .. 3 the B fragments,
+//               4 .. 9 the halo and coefficient loads of slab s+3, 16 g + 10 .. 13 the A fragments of group g+1.
+//   skip loop = the same tile: 128 pixels x 32 raw channels per slab (four float4 per thread through the swizzled V buffers, which are
+//               Vs[0] and Vs[1]), the wave's 32 weight columns from global memory into the fragment registers one group ahead.
+//   epilogue  = the first kernel's per wave.  A wave's 32 tiles x one patch row are the 64-pixel statistics block (m0 >> 6) + a -- the
+//               block the first kernel's wave row wr gives the same pixels ((m0_256 >> 6) + 2 wr + a), summed in the same order.
+// Kept from the first kernel, which makes the two bit-identical: slab order, K step r = 0 .. 3 per position and slab, the skip loop's order
+// (group, r, patch pixel), the halo chain's operations, the epilogue's order and the column-sum shuffles.
+// What remains redundant: TWO workgroups per M tile (cout = 256: N tiles 0 and 1) still stage and transform the same halo.  A 32 x 256
+// workgroup would need 512 accumulators per wave.
 #include <type_traits>
 
 #include "igemm_common.h"
@@ -574,6 +613,478 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
     }
 }
 
+// ---- the second tile shape: 32 tiles x 128 output channels (header comment, "Tile shapes") ----------------------------------------------------
+constexpr int WN_POS = 2 * 32 * 4;                // floats per position of a V image of 32 tiles
+constexpr int WN_IMG = 16 * WN_POS;               // floats per V image (4096)
+constexpr int WN_NSH = 3;                         // halo float4 slots per thread: NP * 2 <= 768
+
+// NORM: as above.  NSL: ceil(2 NP / 256) -- 2 for 16- and 32-column images (NP = 180, 204), 3 for 64-column ones (NP = 264)
+template <int NORM, int NSL>
+__global__ void __launch_bounds__(256, 1) wino_n128_kernel(const KParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* Vs = smem;                              // [2][16][2][32][4]
+    float* Hs = smem + 2 * WN_IMG;                 // [2] x { [2][2][HP][WP / 2][4], and one spare 16-byte cell behind it }
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int mt, nt;
+    if (!decode_tile(blockIdx.x, p.mtiles, p.ntiles, mt, nt)) return;
+    const int m0 = mt * 128, n0 = nt * 128;
+    const int img0 = m0 / p.HW;
+    const int r0 = (m0 - img0 * p.HW) / p.W;
+    const int WPH = p.WP >> 1, Wt = p.W >> 1;
+    const int Ctot = p.c0 + p.c1;
+    const int nslabs = Ctot / WINO_K;
+
+    // ---- halo slots of this thread: as in the first kernel, on the (128 / W + 2) x (W + 2) halo ----------------------------------------
+    const int kh_h = tid & 1;
+    const int h_buf = p.NP * WINO_K + 4;           // floats per buffer of Hs, its spare cell included
+    unsigned h_off0[WN_NSH], h_off1[WN_NSH];
+    int h_lds[WN_NSH];
+#pragma unroll
+    for (int j = 0; j < WN_NSH; ++j) {
+        const int hp = (tid + j * 256) >> 1;
+        const int hr = hp / p.WP, hc = hp - hr * p.WP;
+        const int y = r0 + hr - 1, x = hc - 1;
+        const bool in = hp < p.NP;
+        const bool ok = in && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
+        const int pix = min(max(y, 0), p.H - 1) * p.W + min(max(x, 0), p.W - 1);
+        h_off0[j] = (unsigned)(pix * p.lda0 + kh_h * 4) * 4u;
+        h_off1[j] = (unsigned)(pix * p.lda1 + kh_h * 4) * 4u;
+        const int cell = (((kh_h * 2 + (hc & 1)) * p.HP + hr) * WPH + (hc >> 1)) * 4;
+        h_lds[j] = ok ? cell : p.NP * WINO_K;
+        if (in && !ok) {                           // an out-of-image cell: zeros, once, in both buffers (published by the prologue's first barrier)
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<f32x4*>(Hs + cell) = z;
+            *reinterpret_cast<f32x4*>(Hs + h_buf + cell) = z;
+        }
+    }
+    const float* a0i = p.a0 + (size_t)img0 * p.HW * p.lda0;
+    const float* a1i = p.a1 + (size_t)img0 * p.HW * p.lda1;
+    const float* cpi = p.norm + (size_t)img0 * 3 * Ctot;
+    unsigned c_lane = (unsigned)(kh_h * 16);
+    struct HaloRegs {
+        f32x4 h[WN_NSH];
+        f32x4 mu = {0.f, 0.f, 0.f, 0.f}, ga = {1.f, 1.f, 1.f, 1.f}, be = {0.f, 0.f, 0.f, 0.f};
+    };
+    HaloRegs hreg;
+    float h_t[4 * WN_NSH], h_u[4 * WN_NSH];
+    const float* h_src = nullptr;
+    unsigned h_sel = 0;
+    auto halo_src = [&](int s) {
+        const int c = s * WINO_K;
+        const bool first = c < p.c0;
+        h_src = first ? a0i + c : a1i + (c - p.c0);
+        h_sel = (unsigned)__builtin_amdgcn_readfirstlane(first ? -1 : 0);
+        asm volatile("" : "+s"(h_sel));
+    };
+    auto halo_load1 = [&](HaloRegs& R, auto J) {
+        constexpr int j = decltype(J)::value;
+        if constexpr (j < NSL) {
+            const unsigned off = (h_off0[j] & h_sel) | (h_off1[j] & ~h_sel);
+            R.h[j] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(h_src) + off);
+        }
+    };
+    auto coef_load1 = [&](HaloRegs& R, int s, auto I) {
+        constexpr int i = decltype(I)::value;
+        if constexpr (NORM != 0) {
+            const char* cs = reinterpret_cast<const char*>(cpi + (size_t)i * Ctot + s * WINO_K);
+            asm volatile("" : "+v"(c_lane));
+            const f32x4 v = *reinterpret_cast<const f32x4*>(cs + c_lane);
+            if constexpr (i == 0) R.mu = v; else if constexpr (i == 1) R.ga = v; else R.be = v;
+        }
+    };
+    // the first kernel's element chain, operation for operation
+    auto halo_chain = [&](HaloRegs& R, float* hs, auto C, auto ST) {
+        constexpr int c = decltype(C)::value, st = decltype(ST)::value, j = c >> 2, e = c & 3;
+        if constexpr (j < NSL) {
+            if constexpr (st == 0 && NORM != 0) {
+                h_t[c] = __builtin_fmaf(R.h[j][e] - R.mu[e], R.ga[e], R.be[e]);
+                if constexpr (NORM == 2) h_u[c] = __expf(-h_t[c]);
+            }
+            if constexpr (st == 1 && NORM == 2) h_u[c] = __builtin_amdgcn_rcpf(1.0f + h_u[c]);
+            if constexpr (st == 2) {
+                float v = R.h[j][e];
+                if constexpr (NORM == 1) v = h_t[c];
+                if constexpr (NORM == 2) v = h_t[c] * h_u[c];
+                R.h[j][e] = v;
+                if constexpr (e == 3) *reinterpret_cast<f32x4*>(hs + h_lds[j]) = R.h[j];
+            }
+        }
+    };
+
+    // ---- input transform: 32 tiles x 4 channel pairs, each split over two threads by rows of B^T d B.  A thread owns (tile t_t, channels
+    // 4 kh_t + 2 cpl .. + 1, rows 2 half, 2 half + 1): it reads the rows half .. half + 2 of d and writes eight positions.  kh_t and half
+    // are uniform per wave (wave = kh_t + 2 half), so the choice between the two row pairs is a scalar branch and every wave issues the
+    // same count of instructions.  Every value is made by the first kernel's operations on the same operands.
+    const int t_t = (tid >> 1) & 31, cpl = tid & 1, kh_t = wave & 1, half = wave >> 1;
+    const int t_ty = t_t / Wt, t_tx = t_t - t_ty * Wt;
+    const int h_rd = ((kh_t * 2 * p.HP + 2 * t_ty + half) * WPH + t_tx) * 4 + cpl * 2;
+    const int h_par = p.HP * WPH * 4;              // odd-column plane
+    const int v_wr = (kh_t * 32 + t_t) * 4 + cpl * 2 + half * 8 * WN_POS;
+    f32x2 t_e[3][4];
+    auto tr_read1 = [&](const float* hs, auto I) {             // piece I = row I / 4 (of this thread's three), column I % 4
+        constexpr int i = decltype(I)::value >> 2, j = decltype(I)::value & 3;
+        t_e[i][j] = *reinterpret_cast<const f32x2*>(hs + h_rd + (j & 1) * h_par + i * WPH * 4 + (j >> 1) * 4);
+    };
+    auto tr_write = [&](float* vs) {
+        f32x2 ra[4], rb[4];
+        if (half == 0) {                           // rows 0, 1 of B^T d: d0 - d2, d1 + d2
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { ra[q] = t_e[0][q] - t_e[2][q]; rb[q] = t_e[1][q] + t_e[2][q]; }
+        } else {                                   // rows 2, 3: d2 - d1, d1 - d3
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { ra[q] = t_e[1][q] - t_e[0][q]; rb[q] = t_e[0][q] - t_e[2][q]; }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const f32x2* t_r = i == 0 ? ra : rb;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f32x2 v = j == 0 ? t_r[0] - t_r[2] : j == 1 ? t_r[1] + t_r[2] : j == 2 ? t_r[2] - t_r[1] : t_r[1] - t_r[3];     // (B^T d) B
+                *reinterpret_cast<f32x2*>(vs + v_wr + (i * 4 + j) * WN_POS) = v;
+            }
+        }
+    };
+
+    // ---- transformed weights: global -> the B fragment registers.  The wave's 32 columns are rows 32 (wave & 1) .. + 31 of the 64-column
+    // image 2 nt + (wave >> 1) of ops.pack_conv_weight_wino: per (position, kh) one contiguous 512-byte run, which no other wave of the
+    // workgroup reads.  Scalar base, 32-bit lane offset.
+    const float* u_src = p.b + (size_t)(2 * nt + (wave >> 1)) * nslabs * WINO_IMG;
+    unsigned b_lane = (unsigned)(((lane >> 5) * 64 + (wave & 1) * 32 + (lane & 31)) * 16);
+    f32x4 fa[2][4], fb[2][4];
+    typedef const __attribute__((address_space(1))) f32x4* gf4_t;     // global, not flat: the opaque scalar base has lost its address space
+    auto b_load1 = [&](const float* src, auto G, auto I) {     // src: u_src + slab * WINO_IMG
+        constexpr int g = decltype(G)::value, i = decltype(I)::value;
+        const char* us = reinterpret_cast<const char*>(src + (g * 4 + i) * WINO_POS);
+        asm volatile("" : "+s"(us));
+        asm volatile("" : "+v"(b_lane));
+        fb[g & 1][i] = *(gf4_t)(us + b_lane);
+    };
+
+    f32x16 acc[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+    const int a_off = ((lane >> 5) * 32 + (lane & 31)) * 4;
+
+#define DS_WINO_I(n) std::integral_constant<int, (n)>{}
+#define DS_WINO_EACH4(F) F(0) F(1) F(2) F(3)
+#define DS_WINO_EACH12(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7) F(8) F(9) F(10) F(11)
+#define DS_WINO_EACH16(F, b) F((b) + 0) F((b) + 1) F((b) + 2) F((b) + 3) F((b) + 4) F((b) + 5) F((b) + 6) F((b) + 7)                \
+                             F((b) + 8) F((b) + 9) F((b) + 10) F((b) + 11) F((b) + 12) F((b) + 13) F((b) + 14) F((b) + 15)
+#define DS_WINO_LOADS(R, sl)                                                                                                           \
+    halo_load1(R, DS_WINO_I(0)); halo_load1(R, DS_WINO_I(1)); halo_load1(R, DS_WINO_I(2));                                             \
+    coef_load1(R, sl, DS_WINO_I(0)); coef_load1(R, sl, DS_WINO_I(1)); coef_load1(R, sl, DS_WINO_I(2));
+
+    // ---- prologue: halo 0 and 1 and transform 0 staged, halo 2 and the weights of (slab 0, group 0) requested (two barriers) -----------
+    halo_src(0);
+    DS_WINO_LOADS(hreg, 0)
+    {
+        HaloRegs hreg1;
+        const int s1 = min(1, nslabs - 1);
+        halo_src(s1);
+        DS_WINO_LOADS(hreg1, s1)
+#define DS_WINO_F(i) b_load1(u_src, DS_WINO_I(0), DS_WINO_I(i));
+        DS_WINO_EACH4(DS_WINO_F)
+#undef DS_WINO_F
+        DS_RACE_SKEW(wave);
+#define DS_WINO_CHAIN1(c) halo_chain(hreg, Hs, DS_WINO_I(c), DS_WINO_I(0)); halo_chain(hreg, Hs, DS_WINO_I(c), DS_WINO_I(1));          \
+                          halo_chain(hreg, Hs, DS_WINO_I(c), DS_WINO_I(2));
+        DS_WINO_EACH12(DS_WINO_CHAIN1)
+#undef DS_WINO_CHAIN1
+        DS_RACE_SKEW(wave);
+#define DS_WINO_CHAIN1(c) halo_chain(hreg1, Hs + h_buf, DS_WINO_I(c), DS_WINO_I(0)); halo_chain(hreg1, Hs + h_buf, DS_WINO_I(c), DS_WINO_I(1)); \
+                          halo_chain(hreg1, Hs + h_buf, DS_WINO_I(c), DS_WINO_I(2));
+        DS_WINO_EACH12(DS_WINO_CHAIN1)
+#undef DS_WINO_CHAIN1
+    }
+    {
+        const int s2 = min(2, nslabs - 1);
+        halo_src(s2);
+        DS_WINO_LOADS(hreg, s2)
+    }
+    __syncthreads();                                   // Hs[0], Hs[1] published
+#define DS_WINO_TR1(i) tr_read1(Hs, DS_WINO_I(i));
+    DS_WINO_EACH12(DS_WINO_TR1)
+#undef DS_WINO_TR1
+    DS_RACE_SKEW(wave);
+    tr_write(Vs);
+    DS_WINO_WAIT_VM0();                                // nothing in flight on entry: the loop's counted waits then follow from its own order of loads alone
+    __syncthreads();                                   // Vs[0] published
+
+    // ---- K loop: ONE barrier per slab, no LDS-DMA and hence no vmcnt(0): every global load goes to registers of the wave that uses them,
+    // and the compiler's counted waits stand in front of the first use (the halo store of the next slab; the MFMAs of the next group)
+    int s = 0;
+    do {                                               // nslabs >= 1 (conv3x3_wino_applicable)
+        const int par = s & 1;
+        const float* vb = Vs + par * WN_IMG;
+        float* vbn = Vs + (par ^ 1) * WN_IMG;          // last read by the MFMAs of slab s-1 (barrier s-1 passed)
+        float* hb = Hs + par * h_buf;                  // last read by the transform of slab s, in front of barrier s-1
+        const float* hbn = Hs + (par ^ 1) * h_buf;     // the halo of slab s+1, published at barrier s-1
+        const int s1 = min(s + 1, nslabs - 1), s3 = min(s + 3, nslabs - 1);
+        const float* uc = u_src + (size_t)s * WINO_IMG;
+        const float* un = u_src + (size_t)s1 * WINO_IMG;
+        auto a_read = [&](auto G, auto I) {
+            constexpr int g = decltype(G)::value, i = decltype(I)::value;
+            fa[g & 1][i] = *reinterpret_cast<const f32x4*>(vb + (g * 4 + i) * WN_POS + a_off);
+        };
+#define DS_WINO_TR1(i) tr_read1(hbn, DS_WINO_I(i));       // transform of slab s+1, first half: Hs[par ^ 1] -> registers
+        DS_WINO_EACH12(DS_WINO_TR1)
+#undef DS_WINO_TR1
+        DS_RACE_SKEW(wave);                            // halo of slab s+2 (its loads were issued a slab ago)
+#define DS_WINO_CHAIN1(c) halo_chain(hreg, hb, DS_WINO_I(c), DS_WINO_I(0)); halo_chain(hreg, hb, DS_WINO_I(c), DS_WINO_I(1));          \
+                          halo_chain(hreg, hb, DS_WINO_I(c), DS_WINO_I(2));
+        DS_WINO_EACH12(DS_WINO_CHAIN1)
+#undef DS_WINO_CHAIN1
+        halo_src(s3);
+        DS_RACE_SKEW(wave);
+        tr_write(vbn);                                 // second half: its adds, registers -> Vs[par ^ 1]
+        // micro-slot k of group g = k >> 4, one memory instruction at most:
+        //     16 g + 0 .. 3    the B fragments of group g+1 -- of group 0 of slab s+1 in group 3: a whole group (16 MFMAs) ahead of their use
+        //     4 .. 9           (group 0) the halo loads and the 3 coefficient loads of slab s+3
+        //     16 g + 10 .. 13  the A fragment reads of group g+1
+        auto fill = [&](auto K) {
+            constexpr int k = decltype(K)::value, g = k >> 4, q = k & 15;
+            if constexpr (q < 4) {
+                if constexpr (g < 3) b_load1(uc, DS_WINO_I(g + 1), DS_WINO_I(q));
+                else b_load1(un, DS_WINO_I(0), DS_WINO_I(q));
+            } else if constexpr (k < 7) {
+                halo_load1(hreg, DS_WINO_I(k - 4));
+            } else if constexpr (k < 10) {
+                coef_load1(hreg, s3, DS_WINO_I(k - 7));
+            } else if constexpr (q >= 10 && q < 14 && g < 3) {
+                a_read(DS_WINO_I(g + 1), DS_WINO_I(q - 10));
+            }
+        };
+        // micro-slot k: K step r = (k >> 2) & 3 of position 4 (k >> 4) + (k & 3), then its filler, pinned
+#define DS_WINO_STEP(k)                                                                                                                \
+        acc[((k) >> 4) * 4 + ((k) & 3)] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[((k) >> 4) & 1][(k) & 3][((k) >> 2) & 3],            \
+                                                                               fb[((k) >> 4) & 1][(k) & 3][((k) >> 2) & 3],            \
+                                                                               acc[((k) >> 4) * 4 + ((k) & 3)], 0, 0, 0);              \
+        fill(DS_WINO_I(k));                                                                                                            \
+        __builtin_amdgcn_sched_barrier(0);
+#define DS_WINO_F(i) a_read(DS_WINO_I(0), DS_WINO_I(i));
+        DS_WINO_EACH4(DS_WINO_F)
+#undef DS_WINO_F
+        __builtin_amdgcn_sched_barrier(0);
+        DS_WINO_EACH16(DS_WINO_STEP, 0)
+        DS_WINO_EACH16(DS_WINO_STEP, 16)
+        DS_WINO_EACH16(DS_WINO_STEP, 32)
+        DS_WINO_EACH16(DS_WINO_STEP, 48)
+#undef DS_WINO_STEP
+        __syncthreads();                               // slab s done: Vs[par] dead; Vs and Hs [par ^ 1] published
+    } while (++s < nslabs);
+#undef DS_WINO_LOADS
+
+    // ---- output transform Y = A^T M A (lane-local): Y[a * 2 + b] = the wave's 32 tiles x 32 channels at patch pixel (a, b) ---------------
+    f32x16 Y[4];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        f32x16 t[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) t[j] = a == 0 ? acc[j] + acc[4 + j] + acc[8 + j] : acc[4 + j] - acc[8 + j] - acc[12 + j];
+        Y[a * 2 + 0] = t[0] + t[1] + t[2];
+        Y[a * 2 + 1] = t[1] - t[2] - t[3];
+    }
+
+    // ---- appended 1x1 slabs: the first kernel's loop on 128 pixels x 32 raw channels per slab.  The pixels go global -> registers -> a V
+    // buffer [patch pixel][8-channel group][kh][tile ^ chunk][4] (V[0] = Vs[0], V[1] = Vs[1]: dead behind the K loop's last barrier), four
+    // float4 per thread; the wave's 32 weight columns go global -> fragment registers like U, one group ahead.  ONE barrier per slab:
+    //     slot 16 g        the weight fragment of group g+1 (of group 0 of slab es+1 in group 3)
+    //     slots 16 g + 1 .. 4   the four pixel fragment reads of group g+1
+    //     slots 5 .. 8     the four ds_write_b128 of the pixels of slab es+1 -> V[(es+1) & 1]
+    //     slots 9 .. 12    the four global loads of slab es+2 into the registers just stored
+    // es+1 / es+2 clamped to the last slab.  MFMA order: group, K step r, patch pixel.
+    const int nextra = (p.ec0 + p.ec1) / 32;
+    if (nextra > 0) {
+        const float* wsk = p.b + (size_t)(p.N / 64) * nslabs * WINO_IMG + (size_t)(2 * nt + (wave >> 1)) * nextra * 2048;
+        const int e_chunk = tid & 7;                   // channels 4 e_chunk .. + 3 of the slab: group e_chunk >> 1, kh = e_chunk & 1
+        int e_lds[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int lp = (tid >> 3) + 32 * j;        // pixel of the tile
+            const int yl = lp / p.W, x = lp - yl * p.W;
+            const int ph = (yl & 1) * 2 + (x & 1), t = (yl >> 1) * Wt + (x >> 1);
+            e_lds[j] = (((ph * 4 + (e_chunk >> 1)) * 2 + (e_chunk & 1)) * 32 + (t ^ e_chunk)) * 4;
+        }
+        int ea_off[4];                                 // a_off of group g, swizzled: row ^ (2 g + kh)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) ea_off[g] = ((lane >> 5) * 32 + ((lane & 31) ^ (2 * g + (lane >> 5)))) * 4;
+        const unsigned e_t0 = (unsigned)((tid >> 3) * p.elda0 + e_chunk * 4), e_t1 = (unsigned)((tid >> 3) * p.elda1 + e_chunk * 4);
+        const float* e_src = nullptr;
+        unsigned e_off = 0;
+        int e_step = 0;
+        auto e_sel = [&](int es) {
+            const int c = es * 32;
+            const bool first = c < p.ec0;
+            const int ld = first ? p.elda0 : p.elda1;
+            e_src = (first ? p.e0 + c : p.e1 + (c - p.ec0)) + (size_t)m0 * ld;
+            e_step = 32 * ld;
+            e_off = first ? e_t0 : e_t1;
+        };
+        auto e_load1 = [&](f32x4* dst, auto J) {
+            constexpr int j = decltype(J)::value;
+            dst[j] = *reinterpret_cast<const f32x4*>(e_src + (size_t)(j * e_step) + e_off);
+        };
+        f32x4 ga[2][4], gb[2];                         // fragments of group g: the four patch pixels' pixels and the weights
+        auto w_load1 = [&](int es, auto G) {
+            constexpr int g = decltype(G)::value;
+            const char* ws = reinterpret_cast<const char*>(wsk + (size_t)es * 2048 + g * WINO_POS);
+            asm volatile("" : "+s"(ws));
+            asm volatile("" : "+v"(b_lane));
+            gb[g & 1] = *(gf4_t)(ws + b_lane);
+        };
+
+        // prologue: weights of (slab 0, group 0) requested, pixels of slab 0 staged, pixels of slab 1 requested behind them
+        f32x4 ereg[4];
+        {
+            f32x4 ereg0[4];
+            w_load1(0, DS_WINO_I(0));
+            e_sel(0);
+#define DS_WINO_F(j) e_load1(ereg0, DS_WINO_I(j));
+            DS_WINO_EACH4(DS_WINO_F)
+#undef DS_WINO_F
+            e_sel(min(1, nextra - 1));
+#define DS_WINO_F(j) e_load1(ereg, DS_WINO_I(j));
+            DS_WINO_EACH4(DS_WINO_F)
+#undef DS_WINO_F
+            DS_RACE_SKEW(wave);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(Vs + e_lds[j]) = ereg0[j];
+        }
+        __syncthreads();
+
+        int es = 0;
+        do {
+            const float* vb = smem + (es & 1) * WN_IMG;
+            float* vn = smem + ((es + 1) & 1) * WN_IMG;
+            const int es1 = min(es + 1, nextra - 1);
+            e_sel(min(es + 2, nextra - 1));
+            auto a_read = [&](auto G, auto I) {
+                constexpr int g = decltype(G)::value, i = decltype(I)::value;
+                ga[g & 1][i] = *reinterpret_cast<const f32x4*>(vb + (i * 4 + g) * WN_POS + ea_off[g]);
+            };
+            auto fill = [&](auto K) {
+                constexpr int k = decltype(K)::value, g = k >> 4, q = k & 15;
+                if constexpr (q == 0) {
+                    if constexpr (g < 3) w_load1(es, DS_WINO_I(g + 1));
+                    else w_load1(es1, DS_WINO_I(0));
+                } else if constexpr (q < 5) {
+                    if constexpr (g < 3) a_read(DS_WINO_I(g + 1), DS_WINO_I(q - 1));
+                } else if constexpr (k < 9) {          // pixels of slab es+1
+                    if constexpr (k == 5) DS_RACE_SKEW(wave);
+                    *reinterpret_cast<f32x4*>(vn + e_lds[k - 5]) = ereg[k - 5];
+                } else if constexpr (k < 13) {         // loads of slab es+2
+                    e_load1(ereg, DS_WINO_I(k - 9));
+                }
+            };
+            // micro-slot k: K step r = (k >> 2) & 3 of group k >> 4 into patch pixel k & 3, then its filler, pinned
+#define DS_WINO_STEP(k)                                                                                                                \
+            Y[(k) & 3] = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[((k) >> 4) & 1][(k) & 3][((k) >> 2) & 3], gb[((k) >> 4) & 1][((k) >> 2) & 3], \
+                                                              Y[(k) & 3], 0, 0, 0);                                                    \
+            fill(DS_WINO_I(k));                                                                                                        \
+            __builtin_amdgcn_sched_barrier(0);
+#define DS_WINO_F(i) a_read(DS_WINO_I(0), DS_WINO_I(i));
+            DS_WINO_EACH4(DS_WINO_F)
+#undef DS_WINO_F
+            __builtin_amdgcn_sched_barrier(0);
+            DS_WINO_EACH16(DS_WINO_STEP, 0)
+            DS_WINO_EACH16(DS_WINO_STEP, 16)
+            DS_WINO_EACH16(DS_WINO_STEP, 32)
+            DS_WINO_EACH16(DS_WINO_STEP, 48)
+#undef DS_WINO_STEP
+            __syncthreads();                           // V[es & 1] dead; V[(es+1) & 1] published
+        } while (++es < nextra);
+    }
+#undef DS_WINO_EACH16
+#undef DS_WINO_EACH12
+#undef DS_WINO_EACH4
+#undef DS_WINO_I
+
+    // ---- the fused epilogue, one patch pixel (a, b) at a time: the first kernel's, on this wave's 32 tiles x 32 channels ------------------
+    float* stage = smem + wave * 32 * WINO_EPI_LD;     // wave-private rows; every LDS buffer died at the last barrier
+    const int c4 = (lane & 7) * 4;
+    const int col = n0 + wave * 32 + c4;
+    f32x4 cb = {0.f, 0.f, 0.f, 0.f}, cvu = {0.f, 0.f, 0.f, 0.f};
+    if (p.colbias) cb = *reinterpret_cast<const f32x4*>(p.colbias + col);
+    if (p.cbias) cvu = *reinterpret_cast<const f32x4*>(p.cbias + (size_t)(p.cbias_bcast ? 0 : img0) * p.cbias_ld + col);
+    const float acc_scale = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.acc_scale)));
+    const float scale = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.scale)));
+    int e_row[4];                                      // output row of (pass, patch pixel (0, 0)) of this lane
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {
+        const int tl = pass * 8 + (lane >> 3);
+        const int ty = tl / Wt, tx = tl - ty * Wt;
+        e_row[pass] = m0 + 2 * ty * p.W + 2 * tx;
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        f32x4 st_s = {0.f, 0.f, 0.f, 0.f}, st_q = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const f32x16 y = Y[a * 2 + b];
+            f32x4 rv[4];
+            if (p.res) {
+#pragma unroll
+                for (int pass = 0; pass < 4; ++pass)
+                    rv[pass] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p.res + (size_t)(e_row[pass] + a * p.W + b) * p.res_ld + col));
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) stage[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * WINO_EPI_LD + (lane & 31)] = y[r];
+#pragma unroll
+            for (int pass = 0; pass < 4; ++pass) {
+                f32x4 v = *reinterpret_cast<const f32x4*>(stage + (pass * 8 + (lane >> 3)) * WINO_EPI_LD + c4);
+                v *= acc_scale;
+                v += cb;
+                if (p.cbias) v += cvu;
+                if (p.res) v += rv[pass];
+                v *= scale;
+                if (p.act == DS_ACT_SILU) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[q] = ds_silu(v[q]);
+                }
+                __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p.out + (size_t)(e_row[pass] + a * p.W + b) * p.ldo + col));
+                st_s += v; st_q += v * v;
+            }
+        }
+        if (p.stats) {
+            // column sums of the 64 pixels of patch row a of the 32 tiles: block (m0 >> 6) + a, the block the first kernel's wave row gives it
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                st_s[q] += __shfl_xor(st_s[q], 8); st_s[q] += __shfl_xor(st_s[q], 16); st_s[q] += __shfl_xor(st_s[q], 32);
+                st_q[q] += __shfl_xor(st_q[q], 8); st_q[q] += __shfl_xor(st_q[q], 16); st_q[q] += __shfl_xor(st_q[q], 32);
+            }
+            if (lane < 8) {
+                float* sp = p.stats + (size_t)((m0 >> 6) + a) * 2 * p.N + col;
+                *reinterpret_cast<f32x4*>(sp) = st_s;
+                *reinterpret_cast<f32x4*>(sp + p.N) = st_q;
+            }
+        }
+    }
+}
+
+template <int NORM, int NSL>
+int launch_wino_n128_ns(KParams& p, hipStream_t stream) {
+    const int smem = (2 * WN_IMG + 2 * (p.NP * WINO_K + 4)) * (int)sizeof(float);    // Vs and Hs doubled; + a spare halo cell each
+    DS_ENSURE_DYN_LDS((&wino_n128_kernel<NORM, NSL>), 64 * 1024);
+    hipLaunchKernelGGL((wino_n128_kernel<NORM, NSL>), dim3(grid_1d(p.mtiles, p.ntiles)), dim3(256), smem, stream, p);
+    DS_CHECK_LAUNCH();
+    return DS_OK;
+}
+
+template <int NORM>
+int launch_wino_n128_n(KParams& p, hipStream_t stream) {
+    return p.NP * 2 <= 2 * 256 ? launch_wino_n128_ns<NORM, 2>(p, stream) : launch_wino_n128_ns<NORM, 3>(p, stream);
+}
+
+int launch_wino_n128(KParams& p, hipStream_t stream) {
+    if (!p.norm) return launch_wino_n128_n<0>(p, stream);
+    return p.norm_act == DS_ACT_SILU ? launch_wino_n128_n<2>(p, stream) : launch_wino_n128_n<1>(p, stream);
+}
+
+
 template <int VAR, int NORM, int NSL>
 int launch_wino_ns(KParams& p, hipStream_t stream) {
     const int smem = (4 * WINO_IMG + 2 * (p.NP * WINO_K + 4)) * (int)sizeof(float);  // Us, Vs and Hs doubled; + a spare halo cell each
@@ -624,6 +1135,14 @@ int launch_conv3x3_wino(KParams& p, hipStream_t stream) {
         }
     }
 #endif
+    // Tile shape: 32 tiles x 128 channels unless ds_conv_tune.variant bit 10 asks for the first kernel's 64 x 64 (A/B timing, the bit
+    // comparison of tests/test_hip_wino_n128.py).  Every accepted shape fits it: 128 / W is even for W in 4 .. 64, and the route gives
+    // this file only layers whose columns all lie on 256-column tiles.
+    if (!(p.t_variant & 1024) && p.N % 128 == 0) {
+        p.TH = 128 / p.W; p.HP = p.TH + 2; p.NP = p.HP * p.WP;
+        p.mtiles = p.M / 128; p.ntiles = p.N / 128;
+        return launch_wino_n128(p, stream);
+    }
     return launch_wino<0>(p, stream);
 }
 

@@ -86,7 +86,9 @@ typedef struct ds_conv_tune {
      * tiles, 3 = no kernel of its own any more (once the fp32 twin of conv3x3_halo2.hip), 6 / 7 = 256 x 256 tiles forced (tests at small sizes)
      * / switched off, other values = timing ablations compiled only with -DDS_CONV_ABLATIONS (wrong results on purpose; + 0x10000:
      * ablations of the 256 x 256 tile).  Bit 8 (256): the 256 x 256 tile's plain kernel instead of its default (scalar-addressed weight
-     * DMA + non-temporal epilogue); bit 9 (512): multi-image tiles read their GroupNorm coefficient planes from global memory instead of
+     * DMA + non-temporal epilogue); bit 10 (1024): a Winograd launch (`wino`) on its first tile shape, 64 tiles x 64 channels per workgroup,
+     * instead of 32 tiles x 128 channels -- the same bits of output and column sums (csrc/conv3x3_wino.hip; A/B runs, tests); the direct
+     * kernels ignore it; bit 9 (512): multi-image tiles read their GroupNorm coefficient planes from global memory instead of
      * LDS; bit 11 (2048): the four-wave 128 x 128 tile also where the default is eight half-size waves; bit 12 (4096): the 128-column
      * tiles without the scalar-addressed weight DMA / non-temporal epilogue; bit 13 (8192): no 256 x 192 tiles for the 192-multiples
      * (ADM channel counts); bit 14 (16384): force them regardless of the tile count (tests). */
