@@ -6,9 +6,15 @@
 //     Y = A^T [ sum_c (G g_c G^T) . (B^T d_c B) ] A          (. = elementwise over the 16 positions; entries of A, B: 0, +-1; of G: 0, +-1, +-1/2)
 // i.e. 16 independent [tiles x channels] x [channels x cout] products, one per position of the 4 x 4 transformed patch.
 //
-// TILE SHAPES.  Two kernels, bit-identical in `out` and in the statistics (tests/test_hip_wino_n128.py); launch_conv3x3_wino chooses:
-//   wino_n128_kernel     32 tiles x 128 channels, the DEFAULT at every image width (profiles/wino_n128_ab.txt: - 4.3 ... - 5.1 % per layer at
-//                        16 and 32 columns, - 10 % at 64).  Described under "The 32 x 128 shape" below, in terms of the first kernel.
+// TILE SHAPES.  Three kernels, bit-identical in `out` and in the statistics (tests/test_hip_wino_w8.py, tests/test_hip_wino_n128.py);
+// launch_conv3x3_wino chooses:
+//   wino_w8_kernel       32 tiles x 128 channels on EIGHT waves, two per SIMD: the DEFAULT at 16 and 32 columns (profiles/wino_w8_ab.txt:
+//                        - 3.0 ... - 3.8 % per layer against wino_n128_kernel; nothing gained at 64 columns, where it is not built).
+//                        Described under "Two waves per SIMD" below, in terms of wino_n128_kernel.
+//   wino_n128_kernel     32 tiles x 128 channels on four waves, one per SIMD (profiles/wino_n128_ab.txt: - 4.3 ... - 5.1 % per layer at 16 and
+//                        32 columns, - 10 % at 64, against the first kernel): the default at every other width, and ds_conv_tune.variant
+//                        bit 15 (32768) selects it at 16 and 32 columns.  Described under "The 32 x 128 shape" below, in terms of the
+//                        first kernel.
 //   conv3x3_wino_kernel  64 tiles x 64 channels, the first kernel, described next.  ds_conv_tune.variant bit 10 (1024) selects it: A/B
 //                        timing in one process, the bit comparison of the tests, and the timing ablations (-DDS_CONV_ABLATIONS).
 //
@@ -104,6 +110,28 @@
 // (group, r, patch pixel), the halo chain's operations, the epilogue's order and the column-sum shuffles.
 // What remains redundant: TWO workgroups per M tile (cout = 256: N tiles 0 and 1) still stage and transform the same halo.  A 32 x 256
 // workgroup would need 512 accumulators per wave.
+//
+// TWO WAVES PER SIMD (wino_w8_kernel).  The fp32 MFMA shares the VALU: one wave per SIMD issues v_mfma_f32_32x32x2_f32 every 68.7 cycles
+// and pays ~ 5 cycles for every vector instruction beside it; two waves per SIMD issue it every 64.8 cycles and pay 3.0 - 3.4
+// (profiles/r2_probe_mfma_valu.txt).  Same tile, same packed weights, same mtiles x ntiles as wino_n128_kernel; what changes is who holds what:
+//   workgroup = 512 threads, eight waves of at most 256 registers.  Wave w owns channel group w & 3 (32 columns, wino_n128_kernel's weight
+//               run) and half w >> 2 of the 16 positions: rows i = 2 (w >> 2), + 1 of position 4 i + j, i.e. 8 positions x one 32 x 32 block
+//               = 128 accumulators.  Per slab and wave 32 MFMAs in two groups of four positions, 8 ds_read_b128 of V and 8
+//               global_load_dwordx4 of U one group ahead; per SIMD the MFMA, LDS-read and weight traffic is wino_n128_kernel's.
+//   halo      = one float4 slot per thread (NP x 2 <= 512 at 16 and 32 columns; 64 columns would need a second slot for 16 threads).
+//   transform = the 128 items split over FOUR threads each, by rows of B^T d: a thread reads the two rows of d its row is made of (8
+//               ds_read_b64), and makes its row (4 packed adds) and that row's four positions (4 packed adds, 4 ds_write_b64).  Which
+//               row is uniform per wave.  Each value is made by the first kernel's operations on its operands.
+//   slots     = 16 g + 0 .. 3 the B fragments of the next group (group 0 of slab s+1 in group 1), 4 .. 7 the halo and coefficient loads
+//               of slab s+3, 10 .. 13 the A fragments of group 1.  ONE barrier per slab, every wait a counted one.
+//   exchange  = behind the last barrier the output transform's first sums run over the row index i, which the pair splits: half 0 finishes
+//               patch row 0 = (M[j] + M[4 + j]) + M[8 + j] and needs row 2 of its partner, half 1 finishes patch row 1 = (M[4 + j] -
+//               M[8 + j]) - M[12 + j] and needs row 1.  Each wave writes those four accumulators (64 registers per lane, 16 KiB) into
+//               its own cells of the LDS -- every K-loop buffer is dead -- and reads its partner's behind ONE barrier: 128 KiB in one
+//               round, which is what the launch asks for.  The association of every sum is the other kernels'.
+//   skip loop = each wave on the two pixel accumulators of its patch row, in the order group, K step r, patch pixel: 32 MFMAs per slab.
+//   epilogue  = each wave writes its patch row; the 64-pixel statistics block (m0 >> 6) + (w >> 2) lies wholly in one wave, summed and
+//               shuffled in the other kernels' order.  Its staging rows lie in the cells the wave itself read in the exchange.
 #include <type_traits>
 
 #include "igemm_common.h"
@@ -1084,6 +1112,490 @@ int launch_wino_n128(KParams& p, hipStream_t stream) {
     return p.norm_act == DS_ACT_SILU ? launch_wino_n128_n<2>(p, stream) : launch_wino_n128_n<1>(p, stream);
 }
 
+// ---- the 32 x 128 tile on eight waves, two per SIMD (header comment, "Two waves per SIMD") ---------------------------------------------------
+constexpr int W8_NSH = 1;                         // halo float4 slots per thread: NP * 2 <= 512, i.e. 16- and 32-column images (NP = 180, 204)
+constexpr int W8_XCH = 4 * 16 * 64;               // floats a wave passes to its partner: four accumulators x 16 registers x 64 lanes (16 KiB)
+
+// NORM: as above
+template <int NORM>
+__global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* Vs = smem;                              // [2][16][2][32][4]
+    float* Hs = smem + 2 * WN_IMG;                 // [2] x { [2][2][HP][WP / 2][4], and one spare 16-byte cell behind it }
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int cg = wave & 3, ph = wave >> 2;       // channel group (32 columns) and half of the 16 positions (rows 2 ph, 2 ph + 1 of the patch)
+    int mt, nt;
+    if (!decode_tile(blockIdx.x, p.mtiles, p.ntiles, mt, nt)) return;
+    const int m0 = mt * 128, n0 = nt * 128;
+    const int img0 = m0 / p.HW;
+    const int r0 = (m0 - img0 * p.HW) / p.W;
+    const int WPH = p.WP >> 1, Wt = p.W >> 1;
+    const int Ctot = p.c0 + p.c1;
+    const int nslabs = Ctot / WINO_K;
+
+    // ---- halo slots of this thread: as in the other kernels, the (128 / W + 2) x (W + 2) halo over 512 threads ----------------------------
+    const int kh_h = tid & 1;
+    const int h_buf = p.NP * WINO_K + 4;           // floats per buffer of Hs, its spare cell included
+    unsigned h_off0[W8_NSH], h_off1[W8_NSH];
+    int h_lds[W8_NSH];
+#pragma unroll
+    for (int j = 0; j < W8_NSH; ++j) {
+        const int hp = (tid + j * 512) >> 1;
+        const int hr = hp / p.WP, hc = hp - hr * p.WP;
+        const int y = r0 + hr - 1, x = hc - 1;
+        const bool in = hp < p.NP;
+        const bool ok = in && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
+        const int pix = min(max(y, 0), p.H - 1) * p.W + min(max(x, 0), p.W - 1);
+        h_off0[j] = (unsigned)(pix * p.lda0 + kh_h * 4) * 4u;
+        h_off1[j] = (unsigned)(pix * p.lda1 + kh_h * 4) * 4u;
+        const int cell = (((kh_h * 2 + (hc & 1)) * p.HP + hr) * WPH + (hc >> 1)) * 4;
+        h_lds[j] = ok ? cell : p.NP * WINO_K;
+        if (in && !ok) {                           // an out-of-image cell: zeros, once, in both buffers (published by the prologue's first barrier)
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<f32x4*>(Hs + cell) = z;
+            *reinterpret_cast<f32x4*>(Hs + h_buf + cell) = z;
+        }
+    }
+    const float* a0i = p.a0 + (size_t)img0 * p.HW * p.lda0;
+    const float* a1i = p.a1 + (size_t)img0 * p.HW * p.lda1;
+    const float* cpi = p.norm + (size_t)img0 * 3 * Ctot;
+    unsigned c_lane = (unsigned)(kh_h * 16);
+    struct HaloRegs {
+        f32x4 h[W8_NSH];
+        f32x4 mu = {0.f, 0.f, 0.f, 0.f}, ga = {1.f, 1.f, 1.f, 1.f}, be = {0.f, 0.f, 0.f, 0.f};
+    };
+    HaloRegs hreg;
+    float h_t[4 * W8_NSH], h_u[4 * W8_NSH];
+    const float* h_src = nullptr;
+    unsigned h_sel = 0;
+    auto halo_src = [&](int s) {
+        const int c = s * WINO_K;
+        const bool first = c < p.c0;
+        h_src = first ? a0i + c : a1i + (c - p.c0);
+        h_sel = (unsigned)__builtin_amdgcn_readfirstlane(first ? -1 : 0);
+        asm volatile("" : "+s"(h_sel));
+    };
+    auto halo_load1 = [&](HaloRegs& R, auto J) {
+        constexpr int j = decltype(J)::value;
+        if constexpr (j < W8_NSH) {
+            const unsigned off = (h_off0[j] & h_sel) | (h_off1[j] & ~h_sel);
+            R.h[j] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(h_src) + off);
+        }
+    };
+    auto coef_load1 = [&](HaloRegs& R, int s, auto I) {
+        constexpr int i = decltype(I)::value;
+        if constexpr (NORM != 0) {
+            const char* cs = reinterpret_cast<const char*>(cpi + (size_t)i * Ctot + s * WINO_K);
+            asm volatile("" : "+v"(c_lane));
+            const f32x4 v = *reinterpret_cast<const f32x4*>(cs + c_lane);
+            if constexpr (i == 0) R.mu = v; else if constexpr (i == 1) R.ga = v; else R.be = v;
+        }
+    };
+    // the first kernel's element chain, operation for operation
+    auto halo_chain = [&](HaloRegs& R, float* hs, auto C, auto ST) {
+        constexpr int c = decltype(C)::value, st = decltype(ST)::value, j = c >> 2, e = c & 3;
+        if constexpr (j < W8_NSH) {
+            if constexpr (st == 0 && NORM != 0) {
+                h_t[c] = __builtin_fmaf(R.h[j][e] - R.mu[e], R.ga[e], R.be[e]);
+                if constexpr (NORM == 2) h_u[c] = __expf(-h_t[c]);
+            }
+            if constexpr (st == 1 && NORM == 2) h_u[c] = __builtin_amdgcn_rcpf(1.0f + h_u[c]);
+            if constexpr (st == 2) {
+                float v = R.h[j][e];
+                if constexpr (NORM == 1) v = h_t[c];
+                if constexpr (NORM == 2) v = h_t[c] * h_u[c];
+                R.h[j][e] = v;
+                if constexpr (e == 3) *reinterpret_cast<f32x4*>(hs + h_lds[j]) = R.h[j];
+            }
+        }
+    };
+
+    // ---- input transform: 32 tiles x 4 channel pairs, each split over FOUR threads by rows of B^T d B.  A thread owns (tile t_t, channels
+    // 4 kh_t + 2 cpl .. + 1, row t_row): it reads the two rows of d its row of B^T d is made of (d0 - d2, d1 + d2, d2 - d1, d1 - d3) and
+    // writes four positions.  kh_t and t_row are uniform per wave (wave = kh_t + 2 t_row): scalar branches, the same instruction count in
+    // every wave.  Every value is made by the first kernel's operations on the same operands.
+    const int t_t = (tid >> 1) & 31, cpl = tid & 1, kh_t = wave & 1, t_row = wave >> 1;
+    const int t_ty = t_t / Wt, t_tx = t_t - t_ty * Wt;
+    const int h_rd0 = ((kh_t * 2 * p.HP + 2 * t_ty + (t_row == 0 ? 0 : 1)) * WPH + t_tx) * 4 + cpl * 2;     // row 0 | 1 | 1 | 1 of d
+    const int h_rd1 = ((kh_t * 2 * p.HP + 2 * t_ty + (t_row == 3 ? 3 : 2)) * WPH + t_tx) * 4 + cpl * 2;     // row 2 | 2 | 2 | 3
+    const int h_par = p.HP * WPH * 4;              // odd-column plane
+    const int v_wr = (kh_t * 32 + t_t) * 4 + cpl * 2 + t_row * 4 * WN_POS;
+    f32x2 t_e[2][4];
+    auto tr_read1 = [&](const float* hs, auto I) {             // piece I = row I / 4 (of this thread's two), column I % 4
+        constexpr int i = decltype(I)::value >> 2, j = decltype(I)::value & 3;
+        t_e[i][j] = *reinterpret_cast<const f32x2*>(hs + (i == 0 ? h_rd0 : h_rd1) + (j & 1) * h_par + (j >> 1) * 4);
+    };
+    auto tr_write = [&](float* vs) {
+        f32x2 t_r[4];
+        if (t_row == 1) {                          // d1 + d2
+#pragma unroll
+            for (int q = 0; q < 4; ++q) t_r[q] = t_e[0][q] + t_e[1][q];
+        } else if (t_row == 2) {                   // d2 - d1
+#pragma unroll
+            for (int q = 0; q < 4; ++q) t_r[q] = t_e[1][q] - t_e[0][q];
+        } else {                                   // d0 - d2, d1 - d3
+#pragma unroll
+            for (int q = 0; q < 4; ++q) t_r[q] = t_e[0][q] - t_e[1][q];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const f32x2 v = j == 0 ? t_r[0] - t_r[2] : j == 1 ? t_r[1] + t_r[2] : j == 2 ? t_r[2] - t_r[1] : t_r[1] - t_r[3];     // (B^T d) B
+            *reinterpret_cast<f32x2*>(vs + v_wr + j * WN_POS) = v;
+        }
+    };
+
+    // ---- transformed weights: global -> the B fragment registers, as in wino_n128_kernel: the 32 columns of channel group cg are rows
+    // 32 (cg & 1) .. + 31 of the 64-column image 2 nt + (cg >> 1); this wave reads the positions 8 ph .. 8 ph + 7 of them.  The two waves
+    // of a pair read disjoint halves of the run: per SIMD the weight traffic is wino_n128_kernel's.
+    const float* u_src = p.b + (size_t)(2 * nt + (cg >> 1)) * nslabs * WINO_IMG + ph * 8 * WINO_POS;
+    unsigned b_lane = (unsigned)(((lane >> 5) * 64 + (cg & 1) * 32 + (lane & 31)) * 16);
+    f32x4 fa[2][4], fb[2][4];
+    typedef const __attribute__((address_space(1))) f32x4* gf4_t;     // global, not flat: the opaque scalar base has lost its address space
+    auto b_load1 = [&](const float* src, auto G, auto I) {     // src: u_src + slab * WINO_IMG
+        constexpr int g = decltype(G)::value, i = decltype(I)::value;
+        const char* us = reinterpret_cast<const char*>(src + (g * 4 + i) * WINO_POS);
+        asm volatile("" : "+s"(us));
+        asm volatile("" : "+v"(b_lane));
+        fb[g & 1][i] = *(gf4_t)(us + b_lane);
+    };
+
+    f32x16 acc[8];                                 // position 8 ph + q
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+    const int a_off = ((lane >> 5) * 32 + (lane & 31)) * 4 + ph * 8 * WN_POS;
+
+#define DS_WINO_I(n) std::integral_constant<int, (n)>{}
+#define DS_WINO_EACH4(F) F(0) F(1) F(2) F(3)
+#define DS_WINO_EACH8(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7)
+#define DS_WINO_EACH16(F, b) F((b) + 0) F((b) + 1) F((b) + 2) F((b) + 3) F((b) + 4) F((b) + 5) F((b) + 6) F((b) + 7)                \
+                             F((b) + 8) F((b) + 9) F((b) + 10) F((b) + 11) F((b) + 12) F((b) + 13) F((b) + 14) F((b) + 15)
+#define DS_WINO_LOADS(R, sl)                                                                                                           \
+    halo_load1(R, DS_WINO_I(0));                                                                                                       \
+    coef_load1(R, sl, DS_WINO_I(0)); coef_load1(R, sl, DS_WINO_I(1)); coef_load1(R, sl, DS_WINO_I(2));
+
+    // ---- prologue: halo 0 and 1 and transform 0 staged, halo 2 and the weights of (slab 0, group 0) requested (two barriers) -----------
+    halo_src(0);
+    DS_WINO_LOADS(hreg, 0)
+    {
+        HaloRegs hreg1;
+        const int s1 = min(1, nslabs - 1);
+        halo_src(s1);
+        DS_WINO_LOADS(hreg1, s1)
+#define DS_WINO_F(i) b_load1(u_src, DS_WINO_I(0), DS_WINO_I(i));
+        DS_WINO_EACH4(DS_WINO_F)
+#undef DS_WINO_F
+        DS_RACE_SKEW(wave);
+#define DS_WINO_CHAIN1(c) halo_chain(hreg, Hs, DS_WINO_I(c), DS_WINO_I(0)); halo_chain(hreg, Hs, DS_WINO_I(c), DS_WINO_I(1));          \
+                          halo_chain(hreg, Hs, DS_WINO_I(c), DS_WINO_I(2));
+        DS_WINO_EACH4(DS_WINO_CHAIN1)
+#undef DS_WINO_CHAIN1
+        DS_RACE_SKEW(wave);
+#define DS_WINO_CHAIN1(c) halo_chain(hreg1, Hs + h_buf, DS_WINO_I(c), DS_WINO_I(0)); halo_chain(hreg1, Hs + h_buf, DS_WINO_I(c), DS_WINO_I(1)); \
+                          halo_chain(hreg1, Hs + h_buf, DS_WINO_I(c), DS_WINO_I(2));
+        DS_WINO_EACH4(DS_WINO_CHAIN1)
+#undef DS_WINO_CHAIN1
+    }
+    {
+        const int s2 = min(2, nslabs - 1);
+        halo_src(s2);
+        DS_WINO_LOADS(hreg, s2)
+    }
+    __syncthreads();                                   // Hs[0], Hs[1] published
+#define DS_WINO_TR1(i) tr_read1(Hs, DS_WINO_I(i));
+    DS_WINO_EACH8(DS_WINO_TR1)
+#undef DS_WINO_TR1
+    DS_RACE_SKEW(wave);
+    tr_write(Vs);
+    DS_WINO_WAIT_VM0();                                // nothing in flight on entry: the loop's counted waits then follow from its own order of loads alone
+    __syncthreads();                                   // Vs[0] published
+
+    // ---- K loop: ONE barrier per slab and no forced `vmcnt(0)`, as in wino_n128_kernel; 32 micro-slots per wave, two waves per SIMD --------
+    int s = 0;
+    do {                                               // nslabs >= 1 (conv3x3_wino_applicable)
+        const int par = s & 1;
+        const float* vb = Vs + par * WN_IMG;
+        float* vbn = Vs + (par ^ 1) * WN_IMG;          // last read by the MFMAs of slab s-1 (barrier s-1 passed)
+        float* hb = Hs + par * h_buf;                  // last read by the transform of slab s, in front of barrier s-1
+        const float* hbn = Hs + (par ^ 1) * h_buf;     // the halo of slab s+1, published at barrier s-1
+        const int s1 = min(s + 1, nslabs - 1), s3 = min(s + 3, nslabs - 1);
+        const float* uc = u_src + (size_t)s * WINO_IMG;
+        const float* un = u_src + (size_t)s1 * WINO_IMG;
+        auto a_read = [&](auto G, auto I) {
+            constexpr int g = decltype(G)::value, i = decltype(I)::value;
+            fa[g & 1][i] = *reinterpret_cast<const f32x4*>(vb + (g * 4 + i) * WN_POS + a_off);
+        };
+#define DS_WINO_TR1(i) tr_read1(hbn, DS_WINO_I(i));       // transform of slab s+1, first half: Hs[par ^ 1] -> registers
+        DS_WINO_EACH8(DS_WINO_TR1)
+#undef DS_WINO_TR1
+        DS_RACE_SKEW(wave);                            // halo of slab s+2 (its loads were issued a slab ago)
+#define DS_WINO_CHAIN1(c) halo_chain(hreg, hb, DS_WINO_I(c), DS_WINO_I(0)); halo_chain(hreg, hb, DS_WINO_I(c), DS_WINO_I(1));          \
+                          halo_chain(hreg, hb, DS_WINO_I(c), DS_WINO_I(2));
+        DS_WINO_EACH4(DS_WINO_CHAIN1)
+#undef DS_WINO_CHAIN1
+        halo_src(s3);
+        DS_RACE_SKEW(wave);
+        tr_write(vbn);                                 // second half: its adds, registers -> Vs[par ^ 1]
+        // micro-slot k of group g = k >> 4 (positions 8 ph + 4 g .. + 3), one memory instruction at most:
+        //     16 g + 0 .. 3    the B fragments of the next group -- of group 0 of slab s+1 in group 1: a whole group (16 MFMAs) ahead of their use
+        //     4 .. 7           (group 0) the halo load and the 3 coefficient loads of slab s+3
+        //     10 .. 13         (group 0) the A fragment reads of group 1
+        auto fill = [&](auto K) {
+            constexpr int k = decltype(K)::value, g = k >> 4, q = k & 15;
+            if constexpr (q < 4) {
+                if constexpr (g == 0) b_load1(uc, DS_WINO_I(1), DS_WINO_I(q));
+                else b_load1(un, DS_WINO_I(0), DS_WINO_I(q));
+            } else if constexpr (k == 4) {
+                halo_load1(hreg, DS_WINO_I(0));
+            } else if constexpr (k < 8) {
+                coef_load1(hreg, s3, DS_WINO_I(k - 5));
+            } else if constexpr (k >= 10 && k < 14) {
+                a_read(DS_WINO_I(1), DS_WINO_I(k - 10));
+            }
+        };
+        // micro-slot k: K step r = (k >> 2) & 3 of position 8 ph + 4 (k >> 4) + (k & 3), then its filler, pinned
+#define DS_WINO_STEP(k)                                                                                                                \
+        acc[((k) >> 4) * 4 + ((k) & 3)] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[((k) >> 4) & 1][(k) & 3][((k) >> 2) & 3],            \
+                                                                               fb[((k) >> 4) & 1][(k) & 3][((k) >> 2) & 3],            \
+                                                                               acc[((k) >> 4) * 4 + ((k) & 3)], 0, 0, 0);              \
+        fill(DS_WINO_I(k));                                                                                                            \
+        __builtin_amdgcn_sched_barrier(0);
+#define DS_WINO_F(i) a_read(DS_WINO_I(0), DS_WINO_I(i));
+        DS_WINO_EACH4(DS_WINO_F)
+#undef DS_WINO_F
+        __builtin_amdgcn_sched_barrier(0);
+        DS_WINO_EACH16(DS_WINO_STEP, 0)
+        DS_WINO_EACH16(DS_WINO_STEP, 16)
+#undef DS_WINO_STEP
+        __syncthreads();                               // slab s done: Vs[par] dead; Vs and Hs [par ^ 1] published
+    } while (++s < nslabs);
+#undef DS_WINO_LOADS
+
+    // ---- output transform Y = A^T M A across the pair.  The sums over the row index i of position 4 i + j come first, as in the other
+    // kernels: patch row 0 is (M[j] + M[4 + j]) + M[8 + j], patch row 1 is (M[4 + j] - M[8 + j]) - M[12 + j].  The wave of half 0 holds rows
+    // i = 0, 1 and finishes patch row 0, for which it needs row 2 of its partner; the wave of half 1 holds rows 2, 3 and finishes patch row
+    // 1, for which it needs row 1.  Each passes those four accumulators through the LDS (every K-loop buffer died at the last barrier):
+    // wave w writes 16 KiB at smem + w * W8_XCH as [accumulator][register quad][lane][4] and reads the same cells of wave w ^ 4 -- the
+    // same lane holds the same (tile, channel) in both waves of a pair.  One barrier.  Y[b] = the wave's 32 tiles x 32 channels at patch
+    // pixel (ph, b).
+    f32x16 Y[2];
+    {
+        float* xw = smem + wave * W8_XCH + lane * 4;
+        const float* xr = smem + (wave ^ 4) * W8_XCH + lane * 4;
+        DS_RACE_SKEW(wave);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x16 m = ph == 0 ? acc[4 + q] : acc[q];
+#pragma unroll
+            for (int r4 = 0; r4 < 4; ++r4) {
+                const f32x4 v = {m[4 * r4], m[4 * r4 + 1], m[4 * r4 + 2], m[4 * r4 + 3]};
+                *reinterpret_cast<f32x4*>(xw + (q * 4 + r4) * 256) = v;
+            }
+        }
+        __syncthreads();
+        f32x16 t[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            f32x16 o;
+#pragma unroll
+            for (int r4 = 0; r4 < 4; ++r4) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(xr + (j * 4 + r4) * 256);
+                o[4 * r4] = v[0]; o[4 * r4 + 1] = v[1]; o[4 * r4 + 2] = v[2]; o[4 * r4 + 3] = v[3];
+            }
+            if (ph == 0) t[j] = acc[j] + acc[4 + j] + o;
+            else t[j] = o - acc[j] - acc[4 + j];
+        }
+        Y[0] = t[0] + t[1] + t[2];
+        Y[1] = t[1] - t[2] - t[3];
+    }
+
+    // ---- appended 1x1 slabs: wino_n128_kernel's loop on this wave's TWO patch pixels (ph, 0) and (ph, 1): 32 MFMAs per slab and wave in
+    // the order group, K step r, patch pixel.  The slab's 128 pixels x 32 raw channels go global -> registers -> a V buffer (two float4 per
+    // thread, the same swizzled layout; V[0] = Vs[0], V[1] = Vs[1]); the wave's 32 weight columns go global -> the fragment registers
+    // gb[group], each group's weights of slab es+1 requested right behind the group's last MFMA of slab es.  ONE barrier per slab:
+    //     slot 8 g         (g >= 1) the weight fragment of group g-1 of slab es+1; slot 31: of group 3
+    //     slots 8 g + 1, 2 the two pixel fragment reads of group g+1
+    //     slots 3, 4       the two ds_write_b128 of the pixels of slab es+1 -> V[(es+1) & 1]
+    //     slots 5, 6       the two global loads of slab es+2 into the registers just stored
+    // es+1 / es+2 clamped to the last slab.  The barrier in front keeps the staging from overwriting what a partner has yet to read.
+    const int nextra = (p.ec0 + p.ec1) / 32;
+    if (nextra > 0) {
+        __syncthreads();
+        const float* wsk = p.b + (size_t)(p.N / 64) * nslabs * WINO_IMG + (size_t)(2 * nt + (cg >> 1)) * nextra * 2048;
+        const int e_chunk = tid & 7;                   // channels 4 e_chunk .. + 3 of the slab: group e_chunk >> 1, kh = e_chunk & 1
+        int e_lds[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int lp = (tid >> 3) + 64 * j;        // pixel of the tile
+            const int yl = lp / p.W, x = lp - yl * p.W;
+            const int pp = (yl & 1) * 2 + (x & 1), t = (yl >> 1) * Wt + (x >> 1);
+            e_lds[j] = (((pp * 4 + (e_chunk >> 1)) * 2 + (e_chunk & 1)) * 32 + (t ^ e_chunk)) * 4;
+        }
+        int ea_off[4];                                 // fragment offset of group g, swizzled: row ^ (2 g + kh)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) ea_off[g] = ((lane >> 5) * 32 + ((lane & 31) ^ (2 * g + (lane >> 5)))) * 4;
+        const unsigned e_t0 = (unsigned)((tid >> 3) * p.elda0 + e_chunk * 4), e_t1 = (unsigned)((tid >> 3) * p.elda1 + e_chunk * 4);
+        const float* e_src = nullptr;
+        unsigned e_off = 0;
+        int e_step = 0;
+        auto e_sel = [&](int es) {
+            const int c = es * 32;
+            const bool first = c < p.ec0;
+            const int ld = first ? p.elda0 : p.elda1;
+            e_src = (first ? p.e0 + c : p.e1 + (c - p.ec0)) + (size_t)m0 * ld;
+            e_step = 64 * ld;
+            e_off = first ? e_t0 : e_t1;
+        };
+        auto e_load1 = [&](f32x4* dst, auto J) {
+            constexpr int j = decltype(J)::value;
+            dst[j] = *reinterpret_cast<const f32x4*>(e_src + (size_t)(j * e_step) + e_off);
+        };
+        f32x4 ga[2][2], gb[4];                         // fragments: the two patch pixels' pixels of group g, and the weights of every group
+        auto w_load1 = [&](int es, auto G) {
+            constexpr int g = decltype(G)::value;
+            const char* ws = reinterpret_cast<const char*>(wsk + (size_t)es * 2048 + g * WINO_POS);
+            asm volatile("" : "+s"(ws));
+            asm volatile("" : "+v"(b_lane));
+            gb[g] = *(gf4_t)(ws + b_lane);
+        };
+
+        // prologue: weights of slab 0 requested, pixels of slab 0 staged, pixels of slab 1 requested behind them
+        f32x4 ereg[2];
+        {
+            f32x4 ereg0[2];
+            w_load1(0, DS_WINO_I(0)); w_load1(0, DS_WINO_I(1)); w_load1(0, DS_WINO_I(2)); w_load1(0, DS_WINO_I(3));
+            e_sel(0);
+            e_load1(ereg0, DS_WINO_I(0)); e_load1(ereg0, DS_WINO_I(1));
+            e_sel(min(1, nextra - 1));
+            e_load1(ereg, DS_WINO_I(0)); e_load1(ereg, DS_WINO_I(1));
+            DS_RACE_SKEW(wave);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) *reinterpret_cast<f32x4*>(Vs + e_lds[j]) = ereg0[j];
+        }
+        __syncthreads();
+
+        int es = 0;
+        do {
+            const float* vb = smem + (es & 1) * WN_IMG + ph * 8 * WN_POS;      // patch pixels 2 ph, 2 ph + 1
+            float* vn = smem + ((es + 1) & 1) * WN_IMG;
+            const int es1 = min(es + 1, nextra - 1);
+            e_sel(min(es + 2, nextra - 1));
+            auto a_read = [&](auto G, auto I) {
+                constexpr int g = decltype(G)::value, i = decltype(I)::value;
+                ga[g & 1][i] = *reinterpret_cast<const f32x4*>(vb + (i * 4 + g) * WN_POS + ea_off[g]);
+            };
+            auto fill = [&](auto K) {
+                constexpr int k = decltype(K)::value, g = k >> 3, q = k & 7;
+                if constexpr (q == 0) {
+                    if constexpr (g >= 1) w_load1(es1, DS_WINO_I(g - 1));
+                } else if constexpr (q < 3) {
+                    if constexpr (g < 3) a_read(DS_WINO_I(g + 1), DS_WINO_I(q - 1));
+                } else if constexpr (k < 5) {          // pixels of slab es+1
+                    if constexpr (k == 3) DS_RACE_SKEW(wave);
+                    *reinterpret_cast<f32x4*>(vn + e_lds[k - 3]) = ereg[k - 3];
+                } else if constexpr (k < 7) {          // loads of slab es+2
+                    e_load1(ereg, DS_WINO_I(k - 5));
+                } else if constexpr (k == 31) {
+                    w_load1(es1, DS_WINO_I(3));
+                }
+            };
+            // micro-slot k: K step r = (k >> 1) & 3 of group k >> 3 into patch pixel (ph, k & 1), then its filler, pinned
+#define DS_WINO_STEP(k)                                                                                                                \
+            Y[(k) & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[((k) >> 3) & 1][(k) & 1][((k) >> 1) & 3], gb[(k) >> 3][((k) >> 1) & 3], \
+                                                              Y[(k) & 1], 0, 0, 0);                                                    \
+            fill(DS_WINO_I(k));                                                                                                        \
+            __builtin_amdgcn_sched_barrier(0);
+            a_read(DS_WINO_I(0), DS_WINO_I(0)); a_read(DS_WINO_I(0), DS_WINO_I(1));
+            __builtin_amdgcn_sched_barrier(0);
+            DS_WINO_EACH16(DS_WINO_STEP, 0)
+            DS_WINO_EACH16(DS_WINO_STEP, 16)
+#undef DS_WINO_STEP
+            __syncthreads();                           // V[es & 1] dead; V[(es+1) & 1] published
+        } while (++es < nextra);
+    }
+#undef DS_WINO_EACH16
+#undef DS_WINO_EACH8
+#undef DS_WINO_EACH4
+#undef DS_WINO_I
+
+    // ---- the fused epilogue of patch row ph, one patch pixel at a time: the first kernel's, on this wave's 32 tiles x 32 channels.  The
+    // staging rows lie in the cells this wave alone read in the exchange (its partner wrote them in front of the exchange's barrier).
+    float* stage = smem + (wave ^ 4) * W8_XCH;
+    const int c4 = (lane & 7) * 4;
+    const int col = n0 + cg * 32 + c4;
+    f32x4 cb = {0.f, 0.f, 0.f, 0.f}, cvu = {0.f, 0.f, 0.f, 0.f};
+    if (p.colbias) cb = *reinterpret_cast<const f32x4*>(p.colbias + col);
+    if (p.cbias) cvu = *reinterpret_cast<const f32x4*>(p.cbias + (size_t)(p.cbias_bcast ? 0 : img0) * p.cbias_ld + col);
+    const float acc_scale = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.acc_scale)));
+    const float scale = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.scale)));
+    int e_row[4];                                      // output row of (pass, patch pixel (ph, 0)) of this lane
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {
+        const int tl = pass * 8 + (lane >> 3);
+        const int ty = tl / Wt, tx = tl - ty * Wt;
+        e_row[pass] = m0 + (2 * ty + ph) * p.W + 2 * tx;
+    }
+    f32x4 st_s = {0.f, 0.f, 0.f, 0.f}, st_q = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const f32x16 y = Y[b];
+        f32x4 rv[4];
+        if (p.res) {
+#pragma unroll
+            for (int pass = 0; pass < 4; ++pass)
+                rv[pass] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p.res + (size_t)(e_row[pass] + b) * p.res_ld + col));
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) stage[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * WINO_EPI_LD + (lane & 31)] = y[r];
+#pragma unroll
+        for (int pass = 0; pass < 4; ++pass) {
+            f32x4 v = *reinterpret_cast<const f32x4*>(stage + (pass * 8 + (lane >> 3)) * WINO_EPI_LD + c4);
+            v *= acc_scale;
+            v += cb;
+            if (p.cbias) v += cvu;
+            if (p.res) v += rv[pass];
+            v *= scale;
+            if (p.act == DS_ACT_SILU) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = ds_silu(v[q]);
+            }
+            __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p.out + (size_t)(e_row[pass] + b) * p.ldo + col));
+            st_s += v; st_q += v * v;
+        }
+    }
+    if (p.stats) {
+        // column sums of the 64 pixels of patch row ph of the 32 tiles: block (m0 >> 6) + ph, summed in the other kernels' order
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            st_s[q] += __shfl_xor(st_s[q], 8); st_s[q] += __shfl_xor(st_s[q], 16); st_s[q] += __shfl_xor(st_s[q], 32);
+            st_q[q] += __shfl_xor(st_q[q], 8); st_q[q] += __shfl_xor(st_q[q], 16); st_q[q] += __shfl_xor(st_q[q], 32);
+        }
+        if (lane < 8) {
+            float* sp = p.stats + (size_t)((m0 >> 6) + ph) * 2 * p.N + col;
+            *reinterpret_cast<f32x4*>(sp) = st_s;
+            *reinterpret_cast<f32x4*>(sp + p.N) = st_q;
+        }
+    }
+}
+
+template <int NORM>
+int launch_wino_w8_n(KParams& p, hipStream_t stream) {
+    // the K loop's Vs and Hs (doubled; + a spare halo cell each) and, behind its last barrier, the eight waves' exchange
+    const int kloop = (2 * WN_IMG + 2 * (p.NP * WINO_K + 4)) * (int)sizeof(float), xch = 8 * W8_XCH * (int)sizeof(float);
+    DS_ENSURE_DYN_LDS((&wino_w8_kernel<NORM>), 160 * 1024);
+    hipLaunchKernelGGL((wino_w8_kernel<NORM>), dim3(grid_1d(p.mtiles, p.ntiles)), dim3(512), kloop > xch ? kloop : xch, stream, p);
+    DS_CHECK_LAUNCH();
+    return DS_OK;
+}
+
+int launch_wino_w8(KParams& p, hipStream_t stream) {
+    if (!p.norm) return launch_wino_w8_n<0>(p, stream);
+    return p.norm_act == DS_ACT_SILU ? launch_wino_w8_n<2>(p, stream) : launch_wino_w8_n<1>(p, stream);
+}
+
 
 template <int VAR, int NORM, int NSL>
 int launch_wino_ns(KParams& p, hipStream_t stream) {
@@ -1137,11 +1649,15 @@ int launch_conv3x3_wino(KParams& p, hipStream_t stream) {
 #endif
     // Tile shape: 32 tiles x 128 channels unless ds_conv_tune.variant bit 10 asks for the first kernel's 64 x 64 (A/B timing, the bit
     // comparison of tests/test_hip_wino_n128.py).  Every accepted shape fits it: 128 / W is even for W in 4 .. 64, and the route gives
-    // this file only layers whose columns all lie on 256-column tiles.
+    // this file only layers whose columns all lie on 256-column tiles.  On that tile: eight waves, two per SIMD (wino_w8_kernel), at 16 and
+    // 32 columns -- the widths at which it was measured faster (profiles/wino_w8_ab.txt: - 3.0 ... - 3.8 % per layer; at 64 columns it
+    // gains nothing, 4 and 8 columns are in no network and were not measured) -- unless bit 15 asks for the four-wave kernel (A/B
+    // timing, the bit comparison of tests/test_hip_wino_w8.py).
     if (!(p.t_variant & 1024) && p.N % 128 == 0) {
         p.TH = 128 / p.W; p.HP = p.TH + 2; p.NP = p.HP * p.WP;
         p.mtiles = p.M / 128; p.ntiles = p.N / 128;
-        return launch_wino_n128(p, stream);
+        const bool w8 = (p.W == 16 || p.W == 32) && !(p.t_variant & 32768);
+        return w8 ? launch_wino_w8(p, stream) : launch_wino_n128(p, stream);
     }
     return launch_wino<0>(p, stream);
 }

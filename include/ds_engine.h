@@ -91,7 +91,10 @@ typedef struct ds_conv_tune {
      * kernels ignore it; bit 9 (512): multi-image tiles read their GroupNorm coefficient planes from global memory instead of
      * LDS; bit 11 (2048): the four-wave 128 x 128 tile also where the default is eight half-size waves; bit 12 (4096): the 128-column
      * tiles without the scalar-addressed weight DMA / non-temporal epilogue; bit 13 (8192): no 256 x 192 tiles for the 192-multiples
-     * (ADM channel counts); bit 14 (16384): force them regardless of the tile count (tests). */
+     * (ADM channel counts); bit 14 (16384): force them regardless of the tile count (tests); bit 15 (32768): a Winograd launch on the
+     * four-wave kernel of the 32 x 128 tile (wino_n128_kernel, one wave per SIMD) also at 16 and 32 columns, where the default is the
+     * eight-wave one (wino_w8_kernel, two per SIMD) -- the same bits of output and column sums (A/B runs, tests); like bit 10, only a
+     * Winograd launch looks at it. */
     int variant;
     int splits;        /* > 0: split-K factor of a convolution that has a workspace (clamped to what the layer allows; 1 = never split).  The
                         * fp16-activation 3x3 kernel (in_f16) splits on its own where its widest tiling covers at most half of the CUs */

@@ -5,6 +5,7 @@
                                                     (ds_conv_tune.variant; ablations need a -DDS_CONV_ABLATIONS build)
     variant words: include/ds_engine.h (ds_conv_tune.variant); 256 = plain 256 x 256 kernel, 512 = coefficient planes from global memory,
     1024 = Winograd launches (--wino) on the 64-tile x 64-channel workgroups instead of 32 x 128 (--variants 0 1024: the two shapes alternating),
+    32768 = Winograd launches on the four-wave kernel of the 32 x 128 tile instead of the eight-wave one (--variants 0 32768, then 32768 0),
     2048 = four-wave 128 x 128 tiles where the default takes eight half-size waves; 65536 + {4, 16, 20, 28} = ablations of the 256 x 256 tile
 """
 import argparse
