@@ -6,132 +6,161 @@
 //     Y = A^T [ sum_c (G g_c G^T) . (B^T d_c B) ] A          (. = elementwise over the 16 positions; entries of A, B: 0, +-1; of G: 0, +-1, +-1/2)
 // i.e. 16 independent [tiles x channels] x [channels x cout] products, one per position of the 4 x 4 transformed patch.
 //
-// TILE SHAPES.  Three kernels, bit-identical in `out` and in the statistics (tests/test_hip_wino_w8.py, tests/test_hip_wino_n128.py);
-// launch_conv3x3_wino chooses:
+// THREE KERNELS, bit-identical in `out` and in the statistics (tests/test_hip_wino_w8.py, tests/test_hip_wino_n128.py); launch_conv3x3_wino chooses:
 //   wino_w8_kernel       32 tiles x 128 channels on EIGHT waves, two per SIMD: the DEFAULT at 16 and 32 columns (profiles/wino_w8_ab.txt:
 //                        - 3.0 ... - 3.8 % per layer against wino_n128_kernel; nothing gained at 64 columns, where it is not built).
-//                        Described under "Two waves per SIMD" below, in terms of wino_n128_kernel.
 //   wino_n128_kernel     32 tiles x 128 channels on four waves, one per SIMD (profiles/wino_n128_ab.txt: - 4.3 ... - 5.1 % per layer at 16 and
 //                        32 columns, - 10 % at 64, against the first kernel): the default at every other width, and ds_conv_tune.variant
-//                        bit 15 (32768) selects it at 16 and 32 columns.  Described under "The 32 x 128 shape" below, in terms of the
-//                        first kernel.
-//   conv3x3_wino_kernel  64 tiles x 64 channels, the first kernel, described next.  ds_conv_tune.variant bit 10 (1024) selects it: A/B
+//                        bit 15 (32768) selects it at 16 and 32 columns.
+//   conv3x3_wino_kernel  64 tiles x 64 channels on four waves, the first kernel.  ds_conv_tune.variant bit 10 (1024) selects it: A/B
 //                        timing in one process, the bit comparison of the tests, and the timing ablations (-DDS_CONV_ABLATIONS).
+// What makes them bit-identical is what they share: the slab order, K step r = 0 .. 3 per position and slab, the halo stage, the skip
+// loop's order (group, K step r, patch pixel), the association of the output transform's sums, and the epilogue.  The halo stage and
+// the skip-slab staging are written ONCE (WinoHalo, WinoSkip below) and described once, here -- but for conv3x3_wino_kernel, which has
+// its own copy of the halo stage, the same code text (the comment at WinoHalo says why).  The epilogue of a patch row is the same code
+// text in each kernel: written once it compiled to 37 - 81 more instructions per kernel and the layers with the fewest slabs measured
+// 0.4 - 1.3 % slower (profiles/wino_shared_isa.txt, profiles/wino_shared_ab.txt); a fix to it has to be made three times.  A kernel
+// owns its tile, who holds which positions, its input transform, its weight path, its slot tables and (wino_w8_kernel) the exchange,
+// described under its name further down.
 //
-//   workgroup = 64 tiles (256 output pixels of ONE image: TH = 256 / W rows x W columns, the 256-pixel M tile of the direct kernel) x 64
-//               output channels, four waves (2 x 2), one per SIMD; a wave holds ALL 16 positions of its 32 tiles x 32 channels
-//               (16 x f32x16 = 256 accumulator registers), so the output transform is lane-local
+// SHARED BY ALL THREE
+//   workgroup = the output pixels of TH rows x W columns of ONE image (TH x W = 256 or 128, i.e. 64 or 32 tiles) x 64 or 128 output
+//               channels; a wave's accumulators are 32 tiles x 32 channels per position (f32x16 each).
 //   slab      = 8 input channels.  Per slab: the raw halo (TH+2) x (W+2) pixels x 8 channels goes global -> registers -> LDS `Hs` with the
-//               consumer's GroupNorm affine + SiLU applied on the way (norm_coefs; the cells of out-of-image pixels hold zeros, which
-//               the activation never sees), is transformed to V = B^T d B in LDS `Vs` (16 positions x 64 tiles x 8 channels), and the
-//               transformed weights U of the workgroup's 64 columns (ops.pack_conv_weight_wino, already in the LDS image's order) stream
-//               global -> LDS by LDS-DMA into `Us`.  16 positions x 4 K steps of v_mfma_f32_32x32x2_f32 per wave and slab.  Us, Vs and Hs are double
-//               buffers: 4 x 32 KiB + 2 x (NP x 32 + 16) bytes, at most 156 448 bytes of LDS.
-//   LDS image = [position][channel quad kh = 0 / 1][row 0..63][4 floats] for U and V alike: an MFMA fragment read is one ds_read_b128 per
-//               lane at (kh = lane >> 5, row = lane & 31), 512 contiguous bytes per 32 lanes -- conflict-free, and the K index of step r is
-//               channel 4 kh + r on both operands.  Hs is split into planes [kh][column parity][row][column / 2][4] so that the tiles of a
-//               row (pixels two apart) read consecutive 16-byte cells.
+//               consumer's GroupNorm affine + SiLU applied on the way (the halo stage), is transformed to V = B^T d B in LDS `Vs` (16
+//               positions x tiles x 8 channels), and meets the transformed weights U (ops.pack_conv_weight_wino) in 16 positions x 4 K
+//               steps of v_mfma_f32_32x32x2_f32 per 32 x 32 block.  Vs and Hs are double buffers.
+//   LDS image = [position][channel quad kh = 0 / 1][row][4 floats]: an MFMA fragment read is one ds_read_b128 per lane at (kh = lane >> 5,
+//               row = lane & 31), 512 contiguous bytes per 32 lanes -- conflict-free, and the K index of step r is channel 4 kh + r on
+//               both operands.  Hs is split into planes [kh][column parity][row][column / 2][4] so that the tiles of a row (pixels two
+//               apart) read consecutive 16-byte cells.
 //   sum order = slab order, then the channel order inside the MFMA; no split-K, no dependence on batch or grid.
-//   epilogue  = the direct kernel's, in its order: acc_scale, bias, per-image cbias, res, out_scale, act, non-temporal stores, and the
-//               GroupNorm column sums of 64-pixel blocks (a wave's 32 tiles x one patch row = 64 pixels; an image's HW / 64 blocks stay
-//               contiguous, which is all ds_gn_finalize assumes).
 //
-// Who orders what: ONE barrier per slab.  Us, Vs and Hs are all doubled; between barrier s-1 and barrier s a wave
-//     reads   Vs[s & 1], Us[s & 1]      the MFMAs of slab s
+// Halo stage (WinoHalo).  A thread owns up to NSH float4 slots (halo pixel, channel quad), fixed for the whole K loop; NSL of them can
+// hold a halo pixel at the launch's width.  Per slab a slot is one global load -- a SCALAR base (the source a0 | a1 at the slab's
+// channel) plus a 32-bit byte offset chosen by a bit-select between two per-slot offsets, so that nothing between the MFMAs branches or
+// does 64-bit vector arithmetic -- and, a slab later, the halo store: the consumer's affine (a subtraction and ONE fma on the
+// coefficient planes {mu, A, B} of the tile's image, three more loads per slab) and SiLU (ds_silu's operations), once per element, then
+// one ds_write_b128.  What is uniform per launch (normalisation none / affine / affine + SiLU; the active slots) is a template parameter.
+// Out-of-image cells: which halo cells lie outside the image is fixed for the tile (its left and right columns; its top or bottom row
+// where the tile touches the image's), so their zeros are written ONCE, into both Hs buffers, where the thread's slots are set up in
+// front of the prologue -- by the thread that owns the slot, which never stores there again: a slot that holds no in-image pixel -- an
+// out-of-image pixel, loaded from the nearest pixel of the same image, or a slot beyond the halo -- stores into the spare cell behind
+// its Hs buffer.  The prologue's first barrier publishes the zeros with halo 0 and 1, and the LDS may hold whatever the workgroup before
+// left.  The halo store used to select `in-image ? v : 0` per element, 12 v_cndmask per slab and thread on top of the MFMAs
+// (profiles/wino_persist_ab.txt: - 2.0 ... - 2.8 % per layer).
+//
+// Who orders what: ONE barrier per slab.  Between barrier s-1 and barrier s a wave
+//     reads   Vs[s & 1] (and its weights)  the MFMAs of slab s
 //     reads   Hs[(s+1) & 1]             the transform of slab s+1 (published at barrier s-1)
 //     writes  Vs[(s+1) & 1]             the same; last read by the MFMAs of slab s-1 (barrier s-1 passed)
 //     writes  Hs[s & 1]                 the halo store of slab s+2, from registers; last read by the transform of slab s, which ran in
 //                                       front of barrier s-1
-//     writes  Us[(s+1) & 1]             the weight DMA of slab s+1; last read by the MFMAs of slab s-1
 //     loads                             the halo and the coefficients of slab s+3 into the registers the halo store has just consumed
-// and `s_waitcnt vmcnt(0)` stands in front of the barrier (the DMA and the loads have landed).  The prologue stages halo 0 and 1 (requested
-// together) and transform 0 and requests halo 2: two barriers.  s+1 / s+2 / s+3 are clamped to the last slab: the last slab issues a
-// redundant transform, halo store and DMA into the buffers nobody reads and redundant loads, all landed at ITS barrier (`vmcnt(0)`; a
-// wave's LDS writes complete in order in front of its later ones).  BEHIND THE LAST BARRIER EVERY K-LOOP BUFFER IS DEAD: the skip-slab loop
-// and the epilogue staging reuse the LDS from offset 0 on that ground alone.
+// The prologue stages halo 0 and 1 (requested together) and transform 0 and requests halo 2: two barriers.  s+1 / s+2 / s+3 are clamped
+// to the last slab: the last slab issues a redundant transform and halo store into the buffers nobody reads and redundant loads (a wave's
+// LDS writes complete in order in front of its later ones).  BEHIND THE LAST BARRIER EVERY K-LOOP BUFFER IS DEAD: the exchange, the
+// skip-slab loop and the epilogue staging reuse the LDS from offset 0 on that ground alone.
 //
-// Between two barriers, in program order: the 16 LDS reads of the transform, the halo store with its arithmetic, the transform's adds and
-// writes, the 8 fragment reads of position group 0, then ONE basic block of 64 micro-slots -- an MFMA, then at most one memory
-// instruction, pinned there by __builtin_amdgcn_sched_barrier(0); the wave is alone on its SIMD (512 registers):
-//     slots  0 ..  7   one LDS-DMA piece of the weights of slab s+1
-//     slots  8 .. 14   the halo loads (one per active slot) and the 3 coefficient loads of slab s+3: ~50 MFMAs ahead of the `vmcnt(0)`
-//     and the 8 fragment reads of position group g+1 in slots 8 .. 15 (20 .. 27, 32 .. 39) of group g.
-// What stands between the fp32 MFMAs is MEMORY instructions only.  Vector arithmetic beside v_mfma_f32_32x32x2_f32 is not hidden by it
-// (profiles/wino_kloop_ab.txt: the transform costs the same in front of the block as spread over its slots, one packed add per slot is
-// slower than both, and taking the 64-bit address adds of a slab's 14 or 15 global loads and DMA pieces out of the block gained 4-6 % per
-// layer).  So the halo store's arithmetic and the transform's adds stay in FRONT of the block, and the global loads and the DMA between
-// the MFMAs take a SCALAR base and a 32-bit lane offset (the `global_load ... v, s[..]` form; the offsets are kept in bytes and opaque,
-// so that the compiler does not widen them outside the loop).
-// Nothing in the block branches: what is uniform per launch (normalisation none / affine / affine + SiLU; 3 or 4 halo slots per thread) is
-// a template parameter, the source a0 | a1 is a scalar base plus a bit-select between two per-slot offsets, and a slot that holds no
-// in-image pixel -- an out-of-image pixel of the halo, loaded from the nearest pixel of the same image, or a slot beyond the halo --
-// stores into the spare cell behind its Hs buffer.
+// Between two barriers, in program order: the LDS reads of the transform, the halo store with its arithmetic, the transform's adds and
+// writes, the fragment reads of position group 0, then ONE basic block of micro-slots -- an MFMA, then at most one memory instruction,
+// pinned there by __builtin_amdgcn_sched_barrier(0).  Each kernel has its own slot table (at its K loop).  What stands between the fp32
+// MFMAs is MEMORY instructions only.  Vector arithmetic beside v_mfma_f32_32x32x2_f32 is not hidden by it (profiles/wino_kloop_ab.txt:
+// the transform costs the same in front of the block as spread over its slots, one packed add per slot is slower than both, and taking
+// the 64-bit address adds of a slab's 14 or 15 global loads and DMA pieces out of the block gained 4-6 % per layer).  So the halo store's
+// arithmetic and the transform's adds stay in FRONT of the block, and the global loads between the MFMAs take a SCALAR base and a 32-bit
+// lane offset (the `global_load ... v, s[..]` form; the offsets are kept in bytes and opaque, so that the compiler does not widen them
+// outside the loop).
 //
-// Out-of-image cells: which halo cells lie outside the image is fixed for the tile (its left and right columns; its top or bottom row
-// where the tile touches the image's), so their zeros are written ONCE, into both Hs buffers, where the thread's slots are set up in
-// front of the prologue -- by the thread that owns the slot, which never stores there again; the prologue's first barrier publishes
-// them with halo 0 and 1, and the LDS may hold whatever the workgroup before left.  The halo store used to select `in-image ? v : 0`
-// per element, 12 v_cndmask per slab and thread on top of the MFMAs (profiles/wino_persist_ab.txt: - 2.0 ... - 2.8 % per layer).
+// Skip slabs (WinoSkip): the fused skip projection, appended 1x1 slabs e0 | e1 of 32 raw channels each, as plain MFMA groups on the
+// post-transform accumulators, one per patch pixel, in the order group, K step r, patch pixel.  The slab's pixels x 32 channels go global
+// -> registers -> a V buffer as [patch pixel][8-channel group][kh][tile][4]; 8 threads hold the 8 chunks of 4 channels of one pixel, so a
+// thread has (tile pixels x 8 / threads) float4 slots.  ONE barrier per slab, in the K loop's style: the MFMAs of slab es, the stores of
+// the pixels of slab es+1 (requested a slab ago) and the loads of slab es+2 into the registers just stored; es+1 / es+2 clamped to the
+// last slab.  No VALU between the MFMAs but the address adds of the stores and loads: the source e0 | e1 (scalar base, row step,
+// per-thread offset) is selected in front.  The V buffers are swizzled: tile t of chunk c = 2 group + kh (the 8 lanes of a
+// ds_write_b128 lane group hold the 8 chunks of ONE pixel, i.e. one t) lives in row t ^ c of its block.  Unswizzled, the 8 cells of a
+// lane group are 1 KB apart -- one bank, 8 LDS cycles per group, 64 instead of 8 per store, and the four waves' stores kept the LDS busy
+// for half of the slab's MFMA time; swizzled they are 8 consecutive 16-byte cells.  The fragment read of (group, kh) reads row (its row)
+// ^ c: still one contiguous 512-byte block per 32 lanes, permuted inside aligned groups of 8 rows.  The weight path is each kernel's.
+//
+// Epilogue, per wave and patch row: the direct kernel's, in its order -- acc_scale, bias, per-image cbias, res, out_scale, act,
+// non-temporal stores -- one patch pixel at a time through 32 wave-private staging rows, and the GroupNorm column sums of the row's 64
+// pixels (a wave's 32 tiles x one patch row; an image's HW / 64 blocks stay contiguous, which is all ds_gn_finalize assumes), shuffled
+// over the 8 lane groups in one fixed order.  The same 64 pixels are one block in every kernel: (m0 >> 6) + a on the 128-pixel tiles,
+// (m0 >> 6) + 2 wr + a for wave row wr of the 256-pixel tile.
 //
 // One workgroup per tile.  A persistent form (one workgroup per compute unit, looping over the tiles b, b + G, ..., the next tile's
 // halo and weight requests in front of the epilogue and its halo stores in the epilogue's middle, epilogue staging moved to Vs[1]) was
 // built bit-identical and measured: + 1 % per layer by itself, nothing gained by the look-ahead (profiles/wino_persist_ab.txt).  It is
 // in no committed source.
 //
-// THE 32 x 128 SHAPE (wino_n128_kernel).  Every layer on this route has cout % 256 == 0, so on 64-column workgroups FOUR workgroups load the
-// same halo, apply the same GroupNorm affine + SiLU to it and run the same input transform: the input side of every slab is computed four
-// times, in vector instructions that add their cycles to the MFMAs' (profiles/wino_kloop_ab.txt).  This shape computes it twice:
-//   workgroup = 32 tiles (128 output pixels of ONE image: 128 / W rows x W columns) x 128 output channels, four waves laid out 1 x 4, one
-//               per SIMD: every wave takes the SAME 32 tiles and owns 32 of the 128 channels, all 16 positions (256 accumulators, the
-//               output transform lane-local as before).  The workgroup count of a layer is unchanged (M / 128 x N / 128).
-//   halo      = (128 / W + 2) x (W + 2) pixels: 204 at 32 columns (340 on the first shape), 180 at 16 (324), 264 at 64 (396), i.e. 2 active
-//               float4 slots per thread and slab at 16 and 32 columns and 3 at 64 (first kernel: 3 and 4).  The chain is the first kernel's.
+// conv3x3_wino_kernel (64 x 64)
+//   workgroup = 64 tiles (256 output pixels: TH = 256 / W rows, the 256-pixel M tile of the direct kernel) x 64 output channels, four
+//               waves (2 x 2), one per SIMD (512 registers); a wave holds ALL 16 positions of its 32 tiles x 32 channels (256
+//               accumulator registers), so the output transform is lane-local.
+//   halo      = 3 active float4 slots per thread and slab at 16 and 32 columns, 4 at 64.
+//   transform = one thread per (tile, channel pair): 16 ds_read_b64, 32 packed adds, 16 ds_write_b64.
+//   weights   = the U image of the workgroup's 64 columns (already in the LDS image's order) streams global -> LDS by LDS-DMA into `Us`,
+//               doubled like Vs: 4 x 32 KiB + 2 x (NP x 32 + 16) bytes, at most 156 448 bytes of LDS.  The DMA of slab s+1 goes into
+//               Us[(s+1) & 1], last read by the MFMAs of slab s-1, and `s_waitcnt vmcnt(0)` stands in front of the barrier (the DMA and
+//               the loads have landed; the last slab's redundant DMA too).
+//   slots     = 64:  0 ..  7   one LDS-DMA piece of the weights of slab s+1
+//                    8 .. 14   the halo loads (one per active slot) and the 3 coefficient loads of slab s+3: ~50 MFMAs ahead of the `vmcnt(0)`
+//               and the 8 fragment reads of position group g+1 in slots 8 .. 15 (20 .. 27, 32 .. 39) of group g.
+//   skip loop = 256 pixels per slab, eight float4 per thread; the untransformed weights (behind the U images in `wgt`, already in LDS
+//               order [group][kh][row][4]) by LDS-DMA into a doubled 8 KB buffer; slot table at the loop.
+//
+// wino_n128_kernel (32 x 128, four waves).  Every layer on this route has cout % 256 == 0, so on 64-column workgroups FOUR workgroups load
+// the same halo, apply the same GroupNorm affine + SiLU to it and run the same input transform: the input side of every slab is computed
+// four times, in vector instructions that add their cycles to the MFMAs' (profiles/wino_kloop_ab.txt).  This shape computes it twice:
+//   workgroup = 32 tiles (128 output pixels: 128 / W rows x W columns) x 128 output channels, four waves laid out 1 x 4, one per SIMD:
+//               every wave takes the SAME 32 tiles and owns 32 of the 128 channels, all 16 positions (256 accumulators, the output
+//               transform lane-local).  The workgroup count of a layer is that of the 64 x 64 shape (M / 128 x N / 128).
+//   halo      = (128 / W + 2) x (W + 2) pixels: 204 at 32 columns (340 on the 64 x 64 shape), 180 at 16 (324), 264 at 64 (396), i.e. 2
+//               active float4 slots per thread and slab at 16 and 32 columns and 3 at 64.
 //   transform = 32 tiles x 4 channel pairs = 128 items, each split over TWO threads by rows of B^T d B: a thread reads three rows of d
-//               (12 ds_read_b64), makes rows {0, 1} or {2, 3} of B^T d and their eight positions (16 packed adds, 8 ds_write_b64; the
-//               first kernel: 16 reads, 32 adds, 16 writes).  Which row pair is uniform per wave -- a scalar branch -- and every wave does
-//               the same amount: the barrier waits for the slowest.  Each value is made by the first kernel's operations on its operands.
+//               (12 ds_read_b64), makes rows {0, 1} or {2, 3} of B^T d and their eight positions (16 packed adds, 8 ds_write_b64).
+//               Which row pair is uniform per wave -- a scalar branch -- and every wave does the same amount: the barrier waits for
+//               the slowest.  Each value is made by the 64 x 64 kernel's operations on its operands.
 //   weights   = NOT through the LDS.  In the 1 x 4 layout a wave's 32 columns of U belong to that wave alone, so LDS staging would share
 //               nothing (and two doubled 64 KiB images would not fit beside V and the halo).  ops.pack_conv_weight_wino stores each
 //               (position, kh) as 64 rows x 16 bytes per 64-column image: a wave's B fragment of a position is ONE global_load_dwordx4 per
 //               lane, 512 contiguous bytes per kh, from image 2 nt + (wave >> 1), rows 32 (wave & 1) .. + 31 -- no repacking.  The four
 //               loads of position group g+1 are issued in the first four slots of group g (group 0 of slab s+1 in group 3 of slab s),
-//               16 MFMAs ~ 1 000 cycles ahead of their use, scalar base + 32-bit lane offset.  U is read from L2 at twice the first
+//               16 MFMAs ~ 1 000 cycles ahead of their use, scalar base + 32-bit lane offset.  U is read from L2 at twice the 64 x 64
 //               kernel's rate; the workgroups of an XCD walk the slabs together.
-//   LDS       = Vs doubled (2 x 16 KiB) and Hs doubled: 44 320 ... 49 696 bytes.  A fragment reads as before, one ds_read_b128 per position.
-//   order     = the first kernel's "who orders what" without Us: ONE barrier per slab and NO `vmcnt(0)` in the loop -- every global load
-//               targets registers of the wave that uses them, and the compiler's counted waits stand in front of the first use (after the
-//               prologue's single `vmcnt(0)` the loop's waits follow from its own order of loads).  Slots: 16 g + 0 .. 3 the B fragments,
-//               4 .. 9 the halo and coefficient loads of slab s+3, 16 g + 10 .. 13 the A fragments of group g+1.
-//   skip loop = the same tile: 128 pixels x 32 raw channels per slab (four float4 per thread through the swizzled V buffers, which are
-//               Vs[0] and Vs[1]), the wave's 32 weight columns from global memory into the fragment registers one group ahead.
-//   epilogue  = the first kernel's per wave.  A wave's 32 tiles x one patch row are the 64-pixel statistics block (m0 >> 6) + a -- the
-//               block the first kernel's wave row wr gives the same pixels ((m0_256 >> 6) + 2 wr + a), summed in the same order.
-// Kept from the first kernel, which makes the two bit-identical: slab order, K step r = 0 .. 3 per position and slab, the skip loop's order
-// (group, r, patch pixel), the halo chain's operations, the epilogue's order and the column-sum shuffles.
+//   LDS       = Vs doubled (2 x 16 KiB) and Hs doubled: 44 320 ... 49 696 bytes.
+//   order     = NO `vmcnt(0)` in the loop -- every global load targets registers of the wave that uses them, and the compiler's counted
+//               waits stand in front of the first use (after the prologue's single `vmcnt(0)` the loop's waits follow from its own
+//               order of loads).  Slots: 16 g + 0 .. 3 the B fragments, 4 .. 9 the halo and coefficient loads of slab s+3, 16 g + 10 ..
+//               13 the A fragments of group g+1.
+//   skip loop = 128 pixels per slab, four float4 per thread, V[0] = Vs[0], V[1] = Vs[1]; the wave's 32 weight columns from global
+//               memory into the fragment registers one group ahead.
 // What remains redundant: TWO workgroups per M tile (cout = 256: N tiles 0 and 1) still stage and transform the same halo.  A 32 x 256
 // workgroup would need 512 accumulators per wave.
 //
-// TWO WAVES PER SIMD (wino_w8_kernel).  The fp32 MFMA shares the VALU: one wave per SIMD issues v_mfma_f32_32x32x2_f32 every 68.7 cycles
-// and pays ~ 5 cycles for every vector instruction beside it; two waves per SIMD issue it every 64.8 cycles and pay 3.0 - 3.4
-// (profiles/r2_probe_mfma_valu.txt).  Same tile, same packed weights, same mtiles x ntiles as wino_n128_kernel; what changes is who holds what:
-//   workgroup = 512 threads, eight waves of at most 256 registers.  Wave w owns channel group w & 3 (32 columns, wino_n128_kernel's weight
-//               run) and half w >> 2 of the 16 positions: rows i = 2 (w >> 2), + 1 of position 4 i + j, i.e. 8 positions x one 32 x 32 block
-//               = 128 accumulators.  Per slab and wave 32 MFMAs in two groups of four positions, 8 ds_read_b128 of V and 8
-//               global_load_dwordx4 of U one group ahead; per SIMD the MFMA, LDS-read and weight traffic is wino_n128_kernel's.
+// wino_w8_kernel (32 x 128, eight waves, two per SIMD).  The fp32 MFMA shares the VALU: one wave per SIMD issues v_mfma_f32_32x32x2_f32
+// every 68.7 cycles and pays ~ 5 cycles for every vector instruction beside it; two waves per SIMD issue it every 64.8 cycles and pay
+// 3.0 - 3.4 (profiles/r2_probe_mfma_valu.txt).  Tile, packed weights, LDS image and mtiles x ntiles are wino_n128_kernel's:
+//   workgroup = 512 threads, eight waves of at most 256 registers.  Wave w owns channel group w & 3 (32 columns, one wave's weight run
+//               of the four-wave kernel) and half w >> 2 of the 16 positions: rows i = 2 (w >> 2), + 1 of position 4 i + j, i.e. 8
+//               positions x one 32 x 32 block = 128 accumulators.  Per slab and wave 32 MFMAs in two groups of four positions, 8
+//               ds_read_b128 of V and 8 global_load_dwordx4 of U one group ahead; per SIMD the MFMA, LDS-read and weight traffic is the
+//               four-wave kernel's.
 //   halo      = one float4 slot per thread (NP x 2 <= 512 at 16 and 32 columns; 64 columns would need a second slot for 16 threads).
 //   transform = the 128 items split over FOUR threads each, by rows of B^T d: a thread reads the two rows of d its row is made of (8
 //               ds_read_b64), and makes its row (4 packed adds) and that row's four positions (4 packed adds, 4 ds_write_b64).  Which
-//               row is uniform per wave.  Each value is made by the first kernel's operations on its operands.
+//               row is uniform per wave.  Each value is made by the 64 x 64 kernel's operations on its operands.
 //   slots     = 16 g + 0 .. 3 the B fragments of the next group (group 0 of slab s+1 in group 1), 4 .. 7 the halo and coefficient loads
 //               of slab s+3, 10 .. 13 the A fragments of group 1.  ONE barrier per slab, every wait a counted one.
 //   exchange  = behind the last barrier the output transform's first sums run over the row index i, which the pair splits: half 0 finishes
 //               patch row 0 = (M[j] + M[4 + j]) + M[8 + j] and needs row 2 of its partner, half 1 finishes patch row 1 = (M[4 + j] -
 //               M[8 + j]) - M[12 + j] and needs row 1.  Each wave writes those four accumulators (64 registers per lane, 16 KiB) into
-//               its own cells of the LDS -- every K-loop buffer is dead -- and reads its partner's behind ONE barrier: 128 KiB in one
-//               round, which is what the launch asks for.  The association of every sum is the other kernels'.
-//   skip loop = each wave on the two pixel accumulators of its patch row, in the order group, K step r, patch pixel: 32 MFMAs per slab.
-//   epilogue  = each wave writes its patch row; the 64-pixel statistics block (m0 >> 6) + (w >> 2) lies wholly in one wave, summed and
-//               shuffled in the other kernels' order.  Its staging rows lie in the cells the wave itself read in the exchange.
+//               its own cells of the LDS and reads its partner's behind ONE barrier: 128 KiB in one round, which is what the launch
+//               asks for.  The association of every sum is the lane-local output transform's.
+//   skip loop = each wave on the two pixel accumulators of its patch row: 32 MFMAs per slab; two float4 per thread.
+//   epilogue  = each wave writes its one patch row; its staging rows lie in the cells the wave itself read in the exchange.
 #include <type_traits>
 
 #include "igemm_common.h"
@@ -155,8 +184,195 @@ constexpr int WINO_EPI_LD = 36;                   // epilogue staging row: 32 + 
 #define DS_WINO_WAIT_VM0() do { __builtin_amdgcn_s_waitcnt(0x0F70); asm volatile("" ::: "memory"); } while (0)
 #define DS_WINO_WAIT_VM(n) do { __builtin_amdgcn_s_waitcnt(0x0F70 | (n)); asm volatile("" ::: "memory"); } while (0)      // vmcnt(n), n < 16
 
-// NORM: the consumer's normalisation on the way into Hs -- 0 none, 1 affine, 2 affine + SiLU (uniform per launch: p.norm, p.norm_act)
-// NSL:  halo float4 slots per thread that can hold a halo pixel, ceil(2 NP / 256): 3 for 16- and 32-column images, 4 for 64-column ones
+// unrolling by hand: the slot tables of the kernels take their slot number as a type (DS_WINO_I), one statement per slot
+#define DS_WINO_I(n) std::integral_constant<int, (n)>{}
+#define DS_WINO_EACH4(F) F(0) F(1) F(2) F(3)
+#define DS_WINO_EACH8(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7)
+#define DS_WINO_EACH12(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7) F(8) F(9) F(10) F(11)
+#define DS_WINO_EACH16(F, b) F((b) + 0) F((b) + 1) F((b) + 2) F((b) + 3) F((b) + 4) F((b) + 5) F((b) + 6) F((b) + 7)                \
+                             F((b) + 8) F((b) + 9) F((b) + 10) F((b) + 11) F((b) + 12) F((b) + 13) F((b) + 14) F((b) + 15)
+
+// ---- the halo stage (header comment, "Halo stage"): a thread's slots, and a slab's loads and store ------------------------------------------
+// NT:    threads per workgroup; slot j of thread tid is (halo pixel (tid + j NT) >> 1, channel quad tid & 1)
+// NSH:   slots per thread the launch route can need, NP * 2 <= NSH * NT;  NSL <= NSH: slots that can hold a halo pixel in THIS launch,
+//        ceil(2 NP / NT) -- the loads and the store touch no other
+// NORM:  the consumer's normalisation on the way into Hs -- 0 none, 1 affine, 2 affine + SiLU (uniform per launch: p.norm, p.norm_act)
+// The kernels reach load1 and coef1 from their slot tables through one-line lambdas of their own, not directly: called directly, the
+// compiler picks another slot's load for the one offset select it vectorises, and the K loop's instruction order moves.
+// conv3x3_wino_kernel keeps a copy of this stage in its body: on this struct its K loop came out with that select on another slot at
+// NORM != 0, whichever way the struct was cut (profiles/wino_shared_isa.txt); a fix to this stage has to be made there too.
+template <int NT, int NSH, int NSL, int NORM>
+struct WinoHalo {
+    // a slab's halo on its way: the raw pixels of this thread's slots and the slab's coefficient planes {mu, A, B}
+    struct Regs {
+        f32x4 h[NSH];
+        f32x4 mu = {0.f, 0.f, 0.f, 0.f}, ga = {1.f, 1.f, 1.f, 1.f}, be = {0.f, 0.f, 0.f, 0.f};
+    };
+    const int c0, Ctot;                            // channels of the first source and of both
+    const int buf;                                 // floats per buffer of Hs, its spare cell included
+    unsigned off0[NSH], off1[NSH];
+    int lds[NSH];
+    const float *a0i, *a1i;
+    const float* cpi;                              // scalar; the lane's channel quad is the byte offset c_lane
+    unsigned c_lane;
+    float t[4 * NSH], u[4 * NSH];                  // an element chain's affine value and its sigmoid on the way
+    // source of a slab: scalar base, and an all-ones / all-zeros word that selects the per-slot offset without a branch (kept opaque)
+    const float* h_src = nullptr;
+    unsigned h_sel = 0;
+
+    // The slots, fixed for the whole K loop: element offsets inside the tile's image for either source (an out-of-image pixel: the nearest
+    // pixel of the image) and the LDS cell.  An out-of-image pixel's cell holds zeros in BOTH Hs buffers for the whole tile: this thread
+    // writes them here, once, in front of every halo store (the LDS is whatever the workgroup before left), and sends the slot's stores
+    // to the spare cell, as it does for a slot beyond the halo.  No other thread writes those cells; the prologue's first barrier
+    // publishes them with halo 0 and 1.
+    __device__ __forceinline__ WinoHalo(const KParams& p, float* Hs, int tid, int img0, int r0)
+        : c0(p.c0), Ctot(p.c0 + p.c1), buf(p.NP * WINO_K + 4) {
+        const int kh_h = tid & 1, WPH = p.WP >> 1;
+#pragma unroll
+        for (int j = 0; j < NSH; ++j) {
+            const int hp = (tid + j * NT) >> 1;
+            const int hr = hp / p.WP, hc = hp - hr * p.WP;
+            const int y = r0 + hr - 1, x = hc - 1;
+            const bool in = hp < p.NP;
+            const bool ok = in && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
+            const int pix = min(max(y, 0), p.H - 1) * p.W + min(max(x, 0), p.W - 1);
+            off0[j] = (unsigned)(pix * p.lda0 + kh_h * 4) * 4u;         // BYTES: a load's address is the scalar base plus this 32-bit offset,
+            off1[j] = (unsigned)(pix * p.lda1 + kh_h * 4) * 4u;         // with no 64-bit vector arithmetic between the MFMAs
+            const int cell = (((kh_h * 2 + (hc & 1)) * p.HP + hr) * WPH + (hc >> 1)) * 4;
+            lds[j] = ok ? cell : p.NP * WINO_K;
+            if (in && !ok) {
+                const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+                *reinterpret_cast<f32x4*>(Hs + cell) = z;
+                *reinterpret_cast<f32x4*>(Hs + buf + cell) = z;
+            }
+        }
+        a0i = p.a0 + (size_t)img0 * p.HW * p.lda0;
+        a1i = p.a1 + (size_t)img0 * p.HW * p.lda1;
+        cpi = p.norm + (size_t)img0 * 3 * Ctot;
+        c_lane = (unsigned)(kh_h * 16);
+    }
+    // the source a0 | a1 of slab s, for the loads that follow
+    __device__ __forceinline__ void src(int s) {
+        const int c = s * WINO_K;
+        const bool first = c < c0;
+        h_src = first ? a0i + c : a1i + (c - c0);
+        h_sel = (unsigned)__builtin_amdgcn_readfirstlane(first ? -1 : 0);
+        asm volatile("" : "+s"(h_sel));
+    }
+    template <int J>
+    __device__ __forceinline__ void load1(Regs& R, std::integral_constant<int, J>) {
+        if constexpr (J < NSL) {
+            const unsigned off = (off0[J] & h_sel) | (off1[J] & ~h_sel);
+            R.h[J] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(h_src) + off);
+        }
+    }
+    // planes {mu, A, B} of the tile's image at slab s, one per call
+    template <int I>
+    __device__ __forceinline__ void coef1(Regs& R, int s, std::integral_constant<int, I>) {
+        if constexpr (NORM != 0) {
+            const char* cs = reinterpret_cast<const char*>(cpi + (size_t)I * Ctot + s * WINO_K);
+            asm volatile("" : "+v"(c_lane));  // kept 32 bits wide up to the load, which takes the scalar `cs` as its base
+            const f32x4 v = *reinterpret_cast<const f32x4*>(cs + c_lane);
+            if constexpr (I == 0) R.mu = v; else if constexpr (I == 1) R.ga = v; else R.be = v;
+        }
+    }
+    // every load of slab s, in the order the prologues request them
+    __device__ __forceinline__ void loads(Regs& R, int s) {
+#define DS_WINO_F(j) load1(R, DS_WINO_I(j));
+        DS_WINO_EACH4(DS_WINO_F)
+#undef DS_WINO_F
+        coef1(R, s, DS_WINO_I(0)); coef1(R, s, DS_WINO_I(1)); coef1(R, s, DS_WINO_I(2));
+    }
+    // stage ST of element chain C (slot C / 4, float C % 4) of the halo store into the buffer `hs` of Hs: the consumer's GroupNorm affine
+    // + SiLU, applied once per element (an out-of-image pixel's value goes to the spare cell; its own cell holds zeros).  The affine
+    // is a subtraction and ONE fma, the SiLU is ds_silu's operations.
+    template <int C, int ST>
+    __device__ __forceinline__ void chain(Regs& R, float* hs) {
+        constexpr int j = C >> 2, e = C & 3;
+        if constexpr (j < NSL) {
+            if constexpr (ST == 0 && NORM != 0) {
+                t[C] = __builtin_fmaf(R.h[j][e] - R.mu[e], R.ga[e], R.be[e]);
+                if constexpr (NORM == 2) u[C] = __expf(-t[C]);
+            }
+            if constexpr (ST == 1 && NORM == 2) u[C] = __builtin_amdgcn_rcpf(1.0f + u[C]);
+            if constexpr (ST == 2) {
+                float v = R.h[j][e];
+                if constexpr (NORM == 1) v = t[C];
+                if constexpr (NORM == 2) v = t[C] * u[C];
+                R.h[j][e] = v;
+                if constexpr (e == 3) *reinterpret_cast<f32x4*>(hs + lds[j]) = R.h[j];
+            }
+        }
+    }
+    // the halo store of a slab: every chain of every active slot, three stages each
+    __device__ __forceinline__ void store(Regs& R, float* hs) {
+#define DS_WINO_F(c) chain<c, 0>(R, hs); chain<c, 1>(R, hs); chain<c, 2>(R, hs);
+        DS_WINO_EACH16(DS_WINO_F, 0)
+#undef DS_WINO_F
+    }
+};
+
+// ---- skip-slab staging (header comment, "Skip slabs"): a thread's cells of a V buffer, the swizzled fragment offsets, a slab's source -------
+// NT:    threads per workgroup: 8 threads (chunks of 4 channels) per pixel, so slot j of thread tid is pixel (tid >> 3) + j NT / 8 of the tile
+// ROWS:  tiles per V block, 64 or 32: the tile is 4 ROWS pixels, NE = 32 ROWS / NT slots per thread
+template <int NT, int ROWS>
+struct WinoSkip {
+    static constexpr int STEP = NT / 8, NE = 4 * ROWS / STEP;
+    int lds[NE];                                   // V cell of slot j: [patch pixel][8-channel group][kh][tile ^ chunk][4]
+    int a_off[4];                                  // fragment offset of group g in a patch pixel's block, swizzled: row ^ (2 g + kh)
+    unsigned t0, t1;                               // element offset of slot 0 in e0 | e1; a slot steps STEP rows
+    const float* src = nullptr;
+    unsigned off = 0;
+    int step = 0;
+
+    // row0: the first of the 32 tiles whose fragments this wave reads
+    __device__ __forceinline__ WinoSkip(const KParams& p, int tid, int lane, int row0) {
+        const int e_chunk = tid & 7, Wt = p.W >> 1;    // channels 4 e_chunk .. + 3 of the slab: group e_chunk >> 1, kh = e_chunk & 1
+#pragma unroll
+        for (int j = 0; j < NE; ++j) {
+            const int lp = (tid >> 3) + STEP * j;      // pixel of the tile
+            const int yl = lp / p.W, x = lp - yl * p.W;
+            const int ph = (yl & 1) * 2 + (x & 1), t = (yl >> 1) * Wt + (x >> 1);
+            lds[j] = (((ph * 4 + (e_chunk >> 1)) * 2 + (e_chunk & 1)) * ROWS + (t ^ e_chunk)) * 4;
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) a_off[g] = ((lane >> 5) * ROWS + ((row0 + (lane & 31)) ^ (2 * g + (lane >> 5)))) * 4;
+        t0 = (unsigned)((tid >> 3) * p.elda0 + e_chunk * 4);
+        t1 = (unsigned)((tid >> 3) * p.elda1 + e_chunk * 4);
+    }
+    // the source e0 | e1 of slab es of the tile at output row m0, for the loads that follow
+    __device__ __forceinline__ void sel(const KParams& p, int es, int m0) {
+        const int c = es * 32;
+        const bool first = c < p.ec0;
+        const int ld = first ? p.elda0 : p.elda1;
+        src = (first ? p.e0 + c : p.e1 + (c - p.ec0)) + (size_t)m0 * ld;
+        step = STEP * ld;
+        off = first ? t0 : t1;
+    }
+    template <int J>
+    __device__ __forceinline__ void load1(f32x4* dst, std::integral_constant<int, J>) {
+        dst[J] = *reinterpret_cast<const f32x4*>(src + (size_t)(J * step) + off);
+    }
+};
+
+// ---- launching: one kernel instantiation on one workgroup of NT threads per tile, and the choice of NORM, which every kernel takes as a
+// template argument (nothing in the K loop branches on it)
+template <auto KERNEL, int NT, int LDS_MAX>
+int wino_launch(KParams& p, int smem, hipStream_t stream) {
+    DS_ENSURE_DYN_LDS(KERNEL, LDS_MAX);
+    hipLaunchKernelGGL(KERNEL, dim3(grid_1d(p.mtiles, p.ntiles)), dim3(NT), smem, stream, p);
+    DS_CHECK_LAUNCH();
+    return DS_OK;
+}
+
+template <typename F>
+int wino_by_norm(const KParams& p, F launch) {
+    if (!p.norm) return launch(DS_WINO_I(0));
+    return p.norm_act == DS_ACT_SILU ? launch(DS_WINO_I(2)) : launch(DS_WINO_I(1));
+}
+
+// ---- conv3x3_wino_kernel: 64 tiles x 64 channels (header comment) --------------------------------------------------------------------------
+// VAR: the timing ablations (0 in the product).  NORM, NSL: WinoHalo's; NSL = 3 for 16- and 32-column images, 4 for 64-column ones
 template <int VAR, int NORM, int NSL>
 __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -176,13 +392,9 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
     const int Ctot = p.c0 + p.c1;
     const int nslabs = Ctot / WINO_K;
     constexpr bool kDma = !(VAR & WV_NO_DMA), kHalo = !(VAR & WV_NO_HALO);
-    constexpr int kNorm = (VAR & WV_NO_NORM) ? 0 : NORM;       // the arithmetic of the halo store
 
-    // ---- halo slots of this thread: (halo pixel, channel quad), fixed for the whole K loop ------------------------------------------
-    // Element offsets inside the tile's image for either source (an out-of-image pixel: the nearest pixel of the image) and the LDS cell.
-    // An out-of-image pixel's cell holds zeros in BOTH Hs buffers for the whole tile: this thread writes them here, once, in front of
-    // every halo store (the LDS is whatever the workgroup before left), and sends the slot's stores to the spare cell, as it does for a
-    // slot beyond the halo.  No other thread writes those cells; the prologue's first barrier publishes them with halo 0 and 1.
+    // ---- halo stage: WinoHalo's, kept as this kernel's own copy (WinoHalo's comment says why), on 256 threads and WINO_NSH slots ------------
+    constexpr int kNorm = (VAR & WV_NO_NORM) ? 0 : NORM;       // the arithmetic of the halo store; the ablation keeps the coefficient loads
     const int kh_h = tid & 1;
     const int h_buf = p.NP * WINO_K + 4;           // floats per buffer of Hs, its spare cell included
     unsigned h_off0[WINO_NSH], h_off1[WINO_NSH];
@@ -307,11 +519,6 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
         for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
     const int a_off = ((lane >> 5) * 64 + wr * 32 + (lane & 31)) * 4;
     const int b_off = ((lane >> 5) * 64 + wc * 32 + (lane & 31)) * 4;
-
-#define DS_WINO_I(n) std::integral_constant<int, (n)>{}
-#define DS_WINO_EACH4(F) F(0) F(1) F(2) F(3)
-#define DS_WINO_EACH16(F, b) F((b) + 0) F((b) + 1) F((b) + 2) F((b) + 3) F((b) + 4) F((b) + 5) F((b) + 6) F((b) + 7)                \
-                             F((b) + 8) F((b) + 9) F((b) + 10) F((b) + 11) F((b) + 12) F((b) + 13) F((b) + 14) F((b) + 15)
 
 #define DS_WINO_LOADS(R, sl)                                                                                                           \
     halo_load1(R, DS_WINO_I(0)); halo_load1(R, DS_WINO_I(1)); halo_load1(R, DS_WINO_I(2)); halo_load1(R, DS_WINO_I(3));                \
@@ -444,60 +651,24 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
         Y[a * 2 + 1] = t[1] - t[2] - t[3];
     }
 
-    // ---- appended 1x1 slabs (the fused skip projection; e0 | e1, 32 raw channels per slab): four plain MFMA groups on the post-transform
-    // accumulators, one per patch pixel.  The slab's 256 pixels x 32 channels go global -> registers -> a V buffer as [patch pixel][8-channel
-    // group][kh][tile][4], the untransformed weights (behind the U images in `wgt`, already in LDS order [group][kh][row][4]) by LDS-DMA into
-    // a weight buffer.  Every LDS buffer of the K loop died at its last barrier (its clamped redundant DMA landed at the `vmcnt(0)` in
-    // front of it, its redundant transform wrote a Vs buffer in front of it, and the redundant halo store went to Hs, which this loop does
-    // not touch), so both are doubled inside the first three images:
+    // ---- appended 1x1 slabs (header comment, "Skip slabs"): 256 pixels x 32 channels per slab through a V buffer, the untransformed weights
+    // (behind the U images in `wgt`, already in LDS order [group][kh][row][4]) by LDS-DMA into a weight buffer.  Every LDS buffer of the K
+    // loop died at its last barrier (its clamped redundant DMA landed at the `vmcnt(0)` in front of it, its redundant transform wrote a Vs
+    // buffer in front of it, and the redundant halo store went to Hs, which this loop does not touch), so both are doubled inside the
+    // first three images:
     //     W[b] = smem + b * 2048 (8 KB each, the first half of Us[0]),   V[0] = Vs[0],   V[1] = Us[1]
-    // ONE barrier per slab.  Between barrier es-1 and barrier es, one basic block of 64 micro-slots in the K loop's style (an MFMA, then at
-    // most one memory instruction, pinned): the MFMAs of slab es on V[es & 1] and W[es & 1], in the order group, K step r, patch pixel, and
+    // Between barrier es-1 and barrier es, one basic block of 64 micro-slots: the MFMAs of slab es on V[es & 1] and W[es & 1], and
     //     slots  0 ..  1   the two LDS-DMA pieces of the weights of slab es+1 -> W[(es+1) & 1]   (last read by slab es-1)
     //     slots  2 ..  6   (24 .. 28, 36 .. 40 of groups 1, 2) the five fragment reads of group g+1
     //     slots  7 .. 14   the eight ds_write_b128 of the pixels of slab es+1, registers -> V[(es+1) & 1]   (last read by slab es-1; the
     //                      registers were requested a slab ago and landed at the `vmcnt(0)` in front of barrier es-1)
     //     slots 15 .. 22   the eight global loads of slab es+2 into the registers just stored: ~40 MFMAs ahead of the `vmcnt(0)`
-    // es+1 / es+2 are clamped to the last slab, as in the K loop: the last slab issues a redundant DMA and store into the buffers nobody
-    // reads and redundant loads, all landed at its barrier, behind which the epilogue reuses smem from offset 0.  No VALU between the
-    // MFMAs but the address adds of the stores and loads: the source e0 | e1 (scalar base, row step, per-thread offset) is selected in front.
-    // The V buffers are swizzled: tile t of chunk c = 2 group + kh (the 8 lanes of a ds_write_b128 lane group hold the 8 chunks of ONE
-    // pixel, i.e. one t) lives in row t ^ c of its 64-row block.  Unswizzled, the 8 cells of a lane group are 1 KB apart -- one bank, 8 LDS
-    // cycles per group, 64 instead of 8 per store, and the four waves' stores kept the LDS busy for half of the slab's MFMA time; swizzled
-    // they are 8 consecutive 16-byte cells.  The fragment read of (group, kh) reads row (its row) ^ c: still one contiguous 512-byte block
-    // per 32 lanes, permuted inside aligned groups of 8 rows.
+    // The last slab's redundant DMA, store and loads have all landed at its barrier, behind which the epilogue reuses smem from offset 0.
     const int nextra = (p.ec0 + p.ec1) / 32;
     if (nextra > 0) {
         const float* wsk = p.b + (size_t)p.ntiles * nslabs * WINO_IMG + (size_t)nt * nextra * 2048 + tid * 4;
-        const int e_chunk = tid & 7;                   // channels 4 e_chunk .. + 3 of the slab: group e_chunk >> 1, kh = e_chunk & 1
-        int e_lds[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int lp = (tid >> 3) + 32 * j;        // pixel of the tile
-            const int yl = lp / p.W, x = lp - yl * p.W;
-            const int ph = (yl & 1) * 2 + (x & 1), t = (yl >> 1) * Wt + (x >> 1);
-            e_lds[j] = (((ph * 4 + (e_chunk >> 1)) * 2 + (e_chunk & 1)) * 64 + (t ^ e_chunk)) * 4;
-        }
-        int ea_off[4];                                 // a_off of group g, swizzled: row ^ (2 g + kh)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) ea_off[g] = ((lane >> 5) * 64 + ((wr * 32 + (lane & 31)) ^ (2 * g + (lane >> 5)))) * 4;
-        // pixel (tid >> 3) + 32 j of the tile, channels 4 e_chunk .. + 3: element offset of j = 0 for either source; j steps 32 rows
-        const unsigned e_t0 = (unsigned)((tid >> 3) * p.elda0 + e_chunk * 4), e_t1 = (unsigned)((tid >> 3) * p.elda1 + e_chunk * 4);
-        const float* e_src = nullptr;
-        unsigned e_off = 0;
-        int e_step = 0;
-        auto e_sel = [&](int es) {
-            const int c = es * 32;
-            const bool first = c < p.ec0;
-            const int ld = first ? p.elda0 : p.elda1;
-            e_src = (first ? p.e0 + c : p.e1 + (c - p.ec0)) + (size_t)m0 * ld;
-            e_step = 32 * ld;
-            e_off = first ? e_t0 : e_t1;
-        };
-        auto e_load1 = [&](f32x4* dst, auto J) {
-            constexpr int j = decltype(J)::value;
-            dst[j] = *reinterpret_cast<const f32x4*>(e_src + (size_t)(j * e_step) + e_off);
-        };
+        WinoSkip<256, 64> skip(p, tid, lane, wr * 32);
+        auto e_load1 = [&](f32x4* dst, auto J) { skip.load1(dst, J); };
         auto w_dma1 = [&](int es, float* wbuf, auto I) {
             constexpr int i = decltype(I)::value;
             float* dst = wbuf + (i * 256 + wave * 64) * 4;
@@ -505,7 +676,6 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
             typedef __attribute__((address_space(3))) void* lptr_t;
             __builtin_amdgcn_global_load_lds((gptr_t)(wsk + (size_t)es * 2048 + i * 1024), (lptr_t)(dst), 16, 0, 0);
         };
-#define DS_WINO_EACH8(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7)
 
         // prologue: weights and pixels of slab 0 staged, pixels of slab 1 requested behind them
         f32x4 ereg[8];
@@ -513,18 +683,18 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
             f32x4 ereg0[8];
             DS_RACE_SKEW(wave);
             w_dma1(0, smem, DS_WINO_I(0)); w_dma1(0, smem, DS_WINO_I(1));
-            e_sel(0);
+            skip.sel(p, 0, m0);
 #define DS_WINO_F(j) e_load1(ereg0, DS_WINO_I(j));
             DS_WINO_EACH8(DS_WINO_F)
 #undef DS_WINO_F
-            e_sel(min(1, nextra - 1));
+            skip.sel(p, min(1, nextra - 1), m0);
 #define DS_WINO_F(j) e_load1(ereg, DS_WINO_I(j));
             DS_WINO_EACH8(DS_WINO_F)
 #undef DS_WINO_F
             DS_WINO_WAIT_VM(8);                        // all but the eight loads of slab 1
             DS_RACE_SKEW(wave);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4*>(Vs + e_lds[j]) = ereg0[j];
+            for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4*>(Vs + skip.lds[j]) = ereg0[j];
         }
         __syncthreads();
 
@@ -536,10 +706,10 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
             const float* wb = smem + (es & 1) * 2048;
             float* wn = smem + ((es + 1) & 1) * 2048;
             const int es1 = min(es + 1, nextra - 1);
-            e_sel(min(es + 2, nextra - 1));
+            skip.sel(p, min(es + 2, nextra - 1), m0);
             auto frag_read = [&](auto G, auto I) {
                 constexpr int g = decltype(G)::value, i = decltype(I)::value;
-                if constexpr (i < 4) ga[g & 1][i] = *reinterpret_cast<const f32x4*>(vb + (i * 4 + g) * WINO_POS + ea_off[g]);
+                if constexpr (i < 4) ga[g & 1][i] = *reinterpret_cast<const f32x4*>(vb + (i * 4 + g) * WINO_POS + skip.a_off[g]);
                 else gb[g & 1] = *reinterpret_cast<const f32x4*>(wb + g * WINO_POS + b_off);
             };
             auto fill = [&](auto K) {
@@ -549,7 +719,7 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
                     w_dma1(es1, wn, DS_WINO_I(k));
                 } else if constexpr (k >= 7 && k < 15) {   // pixels of slab es+1
                     if constexpr (k == 7) DS_RACE_SKEW(wave);
-                    *reinterpret_cast<f32x4*>(vn + e_lds[k - 7]) = ereg[k - 7];
+                    *reinterpret_cast<f32x4*>(vn + skip.lds[k - 7]) = ereg[k - 7];
                 } else if constexpr (k >= 15 && k < 23) {  // loads of slab es+2
                     e_load1(ereg, DS_WINO_I(k - 15));
                 }
@@ -573,11 +743,7 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
             DS_WINO_WAIT_VM0();                        // the weights of slab es+1 and the pixels of slab es+2 have landed
             __syncthreads();                           // V[es & 1], W[es & 1] dead; V[(es+1) & 1], W[(es+1) & 1] published
         } while (++es < nextra);
-#undef DS_WINO_EACH8
     }
-#undef DS_WINO_EACH16
-#undef DS_WINO_EACH4
-#undef DS_WINO_I
 
     // ---- the fused epilogue, one patch pixel (a, b) at a time ----------------------------------------------------------------------------
     float* stage = smem + wave * 32 * WINO_EPI_LD;     // wave-private rows; every LDS buffer died at the last barrier
@@ -641,12 +807,12 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino_kernel(const KParams p) {
     }
 }
 
-// ---- the second tile shape: 32 tiles x 128 output channels (header comment, "Tile shapes") ----------------------------------------------------
+// ---- wino_n128_kernel: 32 tiles x 128 output channels on four waves (header comment) ----------------------------------------------------------
 constexpr int WN_POS = 2 * 32 * 4;                // floats per position of a V image of 32 tiles
 constexpr int WN_IMG = 16 * WN_POS;               // floats per V image (4096)
 constexpr int WN_NSH = 3;                         // halo float4 slots per thread: NP * 2 <= 768
 
-// NORM: as above.  NSL: ceil(2 NP / 256) -- 2 for 16- and 32-column images (NP = 180, 204), 3 for 64-column ones (NP = 264)
+// NORM, NSL: WinoHalo's; NSL = 2 for 16- and 32-column images (NP = 180, 204), 3 for 64-column ones (NP = 264)
 template <int NORM, int NSL>
 __global__ void __launch_bounds__(256, 1) wino_n128_kernel(const KParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -664,87 +830,18 @@ __global__ void __launch_bounds__(256, 1) wino_n128_kernel(const KParams p) {
     const int Ctot = p.c0 + p.c1;
     const int nslabs = Ctot / WINO_K;
 
-    // ---- halo slots of this thread: as in the first kernel, on the (128 / W + 2) x (W + 2) halo ----------------------------------------
-    const int kh_h = tid & 1;
-    const int h_buf = p.NP * WINO_K + 4;           // floats per buffer of Hs, its spare cell included
-    unsigned h_off0[WN_NSH], h_off1[WN_NSH];
-    int h_lds[WN_NSH];
-#pragma unroll
-    for (int j = 0; j < WN_NSH; ++j) {
-        const int hp = (tid + j * 256) >> 1;
-        const int hr = hp / p.WP, hc = hp - hr * p.WP;
-        const int y = r0 + hr - 1, x = hc - 1;
-        const bool in = hp < p.NP;
-        const bool ok = in && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
-        const int pix = min(max(y, 0), p.H - 1) * p.W + min(max(x, 0), p.W - 1);
-        h_off0[j] = (unsigned)(pix * p.lda0 + kh_h * 4) * 4u;
-        h_off1[j] = (unsigned)(pix * p.lda1 + kh_h * 4) * 4u;
-        const int cell = (((kh_h * 2 + (hc & 1)) * p.HP + hr) * WPH + (hc >> 1)) * 4;
-        h_lds[j] = ok ? cell : p.NP * WINO_K;
-        if (in && !ok) {                           // an out-of-image cell: zeros, once, in both buffers (published by the prologue's first barrier)
-            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            *reinterpret_cast<f32x4*>(Hs + cell) = z;
-            *reinterpret_cast<f32x4*>(Hs + h_buf + cell) = z;
-        }
-    }
-    const float* a0i = p.a0 + (size_t)img0 * p.HW * p.lda0;
-    const float* a1i = p.a1 + (size_t)img0 * p.HW * p.lda1;
-    const float* cpi = p.norm + (size_t)img0 * 3 * Ctot;
-    unsigned c_lane = (unsigned)(kh_h * 16);
-    struct HaloRegs {
-        f32x4 h[WN_NSH];
-        f32x4 mu = {0.f, 0.f, 0.f, 0.f}, ga = {1.f, 1.f, 1.f, 1.f}, be = {0.f, 0.f, 0.f, 0.f};
-    };
-    HaloRegs hreg;
-    float h_t[4 * WN_NSH], h_u[4 * WN_NSH];
-    const float* h_src = nullptr;
-    unsigned h_sel = 0;
-    auto halo_src = [&](int s) {
-        const int c = s * WINO_K;
-        const bool first = c < p.c0;
-        h_src = first ? a0i + c : a1i + (c - p.c0);
-        h_sel = (unsigned)__builtin_amdgcn_readfirstlane(first ? -1 : 0);
-        asm volatile("" : "+s"(h_sel));
-    };
-    auto halo_load1 = [&](HaloRegs& R, auto J) {
-        constexpr int j = decltype(J)::value;
-        if constexpr (j < NSL) {
-            const unsigned off = (h_off0[j] & h_sel) | (h_off1[j] & ~h_sel);
-            R.h[j] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(h_src) + off);
-        }
-    };
-    auto coef_load1 = [&](HaloRegs& R, int s, auto I) {
-        constexpr int i = decltype(I)::value;
-        if constexpr (NORM != 0) {
-            const char* cs = reinterpret_cast<const char*>(cpi + (size_t)i * Ctot + s * WINO_K);
-            asm volatile("" : "+v"(c_lane));
-            const f32x4 v = *reinterpret_cast<const f32x4*>(cs + c_lane);
-            if constexpr (i == 0) R.mu = v; else if constexpr (i == 1) R.ga = v; else R.be = v;
-        }
-    };
-    // the first kernel's element chain, operation for operation
-    auto halo_chain = [&](HaloRegs& R, float* hs, auto C, auto ST) {
-        constexpr int c = decltype(C)::value, st = decltype(ST)::value, j = c >> 2, e = c & 3;
-        if constexpr (j < NSL) {
-            if constexpr (st == 0 && NORM != 0) {
-                h_t[c] = __builtin_fmaf(R.h[j][e] - R.mu[e], R.ga[e], R.be[e]);
-                if constexpr (NORM == 2) h_u[c] = __expf(-h_t[c]);
-            }
-            if constexpr (st == 1 && NORM == 2) h_u[c] = __builtin_amdgcn_rcpf(1.0f + h_u[c]);
-            if constexpr (st == 2) {
-                float v = R.h[j][e];
-                if constexpr (NORM == 1) v = h_t[c];
-                if constexpr (NORM == 2) v = h_t[c] * h_u[c];
-                R.h[j][e] = v;
-                if constexpr (e == 3) *reinterpret_cast<f32x4*>(hs + h_lds[j]) = R.h[j];
-            }
-        }
-    };
+    // ---- halo stage: NSL of three float4 slots per thread -----------------------------------------------------------------------------------
+    using Halo = WinoHalo<256, WN_NSH, NSL, NORM>;
+    Halo halo(p, Hs, tid, img0, r0);
+    const int h_buf = halo.buf;
+    typename Halo::Regs hreg;
+    auto halo_load1 = [&](typename Halo::Regs& R, auto J) { halo.load1(R, J); };
+    auto coef_load1 = [&](typename Halo::Regs& R, int sl, auto I) { halo.coef1(R, sl, I); };
 
     // ---- input transform: 32 tiles x 4 channel pairs, each split over two threads by rows of B^T d B.  A thread owns (tile t_t, channels
     // 4 kh_t + 2 cpl .. + 1, rows 2 half, 2 half + 1): it reads the rows half .. half + 2 of d and writes eight positions.  kh_t and half
     // are uniform per wave (wave = kh_t + 2 half), so the choice between the two row pairs is a scalar branch and every wave issues the
-    // same count of instructions.  Every value is made by the first kernel's operations on the same operands.
+    // same count of instructions.  Every value is made by the 64 x 64 kernel's operations on the same operands.
     const int t_t = (tid >> 1) & 31, cpl = tid & 1, kh_t = wave & 1, half = wave >> 1;
     const int t_ty = t_t / Wt, t_tx = t_t - t_ty * Wt;
     const int h_rd = ((kh_t * 2 * p.HP + 2 * t_ty + half) * WPH + t_tx) * 4 + cpl * 2;
@@ -797,41 +894,26 @@ __global__ void __launch_bounds__(256, 1) wino_n128_kernel(const KParams p) {
         for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
     const int a_off = ((lane >> 5) * 32 + (lane & 31)) * 4;
 
-#define DS_WINO_I(n) std::integral_constant<int, (n)>{}
-#define DS_WINO_EACH4(F) F(0) F(1) F(2) F(3)
-#define DS_WINO_EACH12(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7) F(8) F(9) F(10) F(11)
-#define DS_WINO_EACH16(F, b) F((b) + 0) F((b) + 1) F((b) + 2) F((b) + 3) F((b) + 4) F((b) + 5) F((b) + 6) F((b) + 7)                \
-                             F((b) + 8) F((b) + 9) F((b) + 10) F((b) + 11) F((b) + 12) F((b) + 13) F((b) + 14) F((b) + 15)
-#define DS_WINO_LOADS(R, sl)                                                                                                           \
-    halo_load1(R, DS_WINO_I(0)); halo_load1(R, DS_WINO_I(1)); halo_load1(R, DS_WINO_I(2));                                             \
-    coef_load1(R, sl, DS_WINO_I(0)); coef_load1(R, sl, DS_WINO_I(1)); coef_load1(R, sl, DS_WINO_I(2));
-
     // ---- prologue: halo 0 and 1 and transform 0 staged, halo 2 and the weights of (slab 0, group 0) requested (two barriers) -----------
-    halo_src(0);
-    DS_WINO_LOADS(hreg, 0)
+    halo.src(0);
+    halo.loads(hreg, 0);
     {
-        HaloRegs hreg1;
+        typename Halo::Regs hreg1;
         const int s1 = min(1, nslabs - 1);
-        halo_src(s1);
-        DS_WINO_LOADS(hreg1, s1)
+        halo.src(s1);
+        halo.loads(hreg1, s1);
 #define DS_WINO_F(i) b_load1(u_src, DS_WINO_I(0), DS_WINO_I(i));
         DS_WINO_EACH4(DS_WINO_F)
 #undef DS_WINO_F
         DS_RACE_SKEW(wave);
-#define DS_WINO_CHAIN1(c) halo_chain(hreg, Hs, DS_WINO_I(c), DS_WINO_I(0)); halo_chain(hreg, Hs, DS_WINO_I(c), DS_WINO_I(1));          \
-                          halo_chain(hreg, Hs, DS_WINO_I(c), DS_WINO_I(2));
-        DS_WINO_EACH12(DS_WINO_CHAIN1)
-#undef DS_WINO_CHAIN1
+        halo.store(hreg, Hs);
         DS_RACE_SKEW(wave);
-#define DS_WINO_CHAIN1(c) halo_chain(hreg1, Hs + h_buf, DS_WINO_I(c), DS_WINO_I(0)); halo_chain(hreg1, Hs + h_buf, DS_WINO_I(c), DS_WINO_I(1)); \
-                          halo_chain(hreg1, Hs + h_buf, DS_WINO_I(c), DS_WINO_I(2));
-        DS_WINO_EACH12(DS_WINO_CHAIN1)
-#undef DS_WINO_CHAIN1
+        halo.store(hreg1, Hs + h_buf);
     }
     {
         const int s2 = min(2, nslabs - 1);
-        halo_src(s2);
-        DS_WINO_LOADS(hreg, s2)
+        halo.src(s2);
+        halo.loads(hreg, s2);
     }
     __syncthreads();                                   // Hs[0], Hs[1] published
 #define DS_WINO_TR1(i) tr_read1(Hs, DS_WINO_I(i));
@@ -862,11 +944,8 @@ __global__ void __launch_bounds__(256, 1) wino_n128_kernel(const KParams p) {
         DS_WINO_EACH12(DS_WINO_TR1)
 #undef DS_WINO_TR1
         DS_RACE_SKEW(wave);                            // halo of slab s+2 (its loads were issued a slab ago)
-#define DS_WINO_CHAIN1(c) halo_chain(hreg, hb, DS_WINO_I(c), DS_WINO_I(0)); halo_chain(hreg, hb, DS_WINO_I(c), DS_WINO_I(1));          \
-                          halo_chain(hreg, hb, DS_WINO_I(c), DS_WINO_I(2));
-        DS_WINO_EACH12(DS_WINO_CHAIN1)
-#undef DS_WINO_CHAIN1
-        halo_src(s3);
+        halo.store(hreg, hb);
+        halo.src(s3);
         DS_RACE_SKEW(wave);
         tr_write(vbn);                                 // second half: its adds, registers -> Vs[par ^ 1]
         // micro-slot k of group g = k >> 4, one memory instruction at most:
@@ -904,7 +983,6 @@ __global__ void __launch_bounds__(256, 1) wino_n128_kernel(const KParams p) {
 #undef DS_WINO_STEP
         __syncthreads();                               // slab s done: Vs[par] dead; Vs and Hs [par ^ 1] published
     } while (++s < nslabs);
-#undef DS_WINO_LOADS
 
     // ---- output transform Y = A^T M A (lane-local): Y[a * 2 + b] = the wave's 32 tiles x 32 channels at patch pixel (a, b) ---------------
     f32x16 Y[4];
@@ -917,45 +995,18 @@ __global__ void __launch_bounds__(256, 1) wino_n128_kernel(const KParams p) {
         Y[a * 2 + 1] = t[1] - t[2] - t[3];
     }
 
-    // ---- appended 1x1 slabs: the first kernel's loop on 128 pixels x 32 raw channels per slab.  The pixels go global -> registers -> a V
-    // buffer [patch pixel][8-channel group][kh][tile ^ chunk][4] (V[0] = Vs[0], V[1] = Vs[1]: dead behind the K loop's last barrier), four
-    // float4 per thread; the wave's 32 weight columns go global -> fragment registers like U, one group ahead.  ONE barrier per slab:
+    // ---- appended 1x1 slabs (header comment, "Skip slabs"): 128 pixels x 32 raw channels per slab, four float4 per thread, through V[0] =
+    // Vs[0], V[1] = Vs[1] (dead behind the K loop's last barrier); the wave's 32 weight columns go global -> fragment registers like U, one
+    // group ahead.  Slots:
     //     slot 16 g        the weight fragment of group g+1 (of group 0 of slab es+1 in group 3)
     //     slots 16 g + 1 .. 4   the four pixel fragment reads of group g+1
     //     slots 5 .. 8     the four ds_write_b128 of the pixels of slab es+1 -> V[(es+1) & 1]
     //     slots 9 .. 12    the four global loads of slab es+2 into the registers just stored
-    // es+1 / es+2 clamped to the last slab.  MFMA order: group, K step r, patch pixel.
     const int nextra = (p.ec0 + p.ec1) / 32;
     if (nextra > 0) {
         const float* wsk = p.b + (size_t)(p.N / 64) * nslabs * WINO_IMG + (size_t)(2 * nt + (wave >> 1)) * nextra * 2048;
-        const int e_chunk = tid & 7;                   // channels 4 e_chunk .. + 3 of the slab: group e_chunk >> 1, kh = e_chunk & 1
-        int e_lds[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int lp = (tid >> 3) + 32 * j;        // pixel of the tile
-            const int yl = lp / p.W, x = lp - yl * p.W;
-            const int ph = (yl & 1) * 2 + (x & 1), t = (yl >> 1) * Wt + (x >> 1);
-            e_lds[j] = (((ph * 4 + (e_chunk >> 1)) * 2 + (e_chunk & 1)) * 32 + (t ^ e_chunk)) * 4;
-        }
-        int ea_off[4];                                 // a_off of group g, swizzled: row ^ (2 g + kh)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) ea_off[g] = ((lane >> 5) * 32 + ((lane & 31) ^ (2 * g + (lane >> 5)))) * 4;
-        const unsigned e_t0 = (unsigned)((tid >> 3) * p.elda0 + e_chunk * 4), e_t1 = (unsigned)((tid >> 3) * p.elda1 + e_chunk * 4);
-        const float* e_src = nullptr;
-        unsigned e_off = 0;
-        int e_step = 0;
-        auto e_sel = [&](int es) {
-            const int c = es * 32;
-            const bool first = c < p.ec0;
-            const int ld = first ? p.elda0 : p.elda1;
-            e_src = (first ? p.e0 + c : p.e1 + (c - p.ec0)) + (size_t)m0 * ld;
-            e_step = 32 * ld;
-            e_off = first ? e_t0 : e_t1;
-        };
-        auto e_load1 = [&](f32x4* dst, auto J) {
-            constexpr int j = decltype(J)::value;
-            dst[j] = *reinterpret_cast<const f32x4*>(e_src + (size_t)(j * e_step) + e_off);
-        };
+        WinoSkip<256, 32> skip(p, tid, lane, 0);
+        auto e_load1 = [&](f32x4* dst, auto J) { skip.load1(dst, J); };
         f32x4 ga[2][4], gb[2];                         // fragments of group g: the four patch pixels' pixels and the weights
         auto w_load1 = [&](int es, auto G) {
             constexpr int g = decltype(G)::value;
@@ -970,17 +1021,17 @@ __global__ void __launch_bounds__(256, 1) wino_n128_kernel(const KParams p) {
         {
             f32x4 ereg0[4];
             w_load1(0, DS_WINO_I(0));
-            e_sel(0);
+            skip.sel(p, 0, m0);
 #define DS_WINO_F(j) e_load1(ereg0, DS_WINO_I(j));
             DS_WINO_EACH4(DS_WINO_F)
 #undef DS_WINO_F
-            e_sel(min(1, nextra - 1));
+            skip.sel(p, min(1, nextra - 1), m0);
 #define DS_WINO_F(j) e_load1(ereg, DS_WINO_I(j));
             DS_WINO_EACH4(DS_WINO_F)
 #undef DS_WINO_F
             DS_RACE_SKEW(wave);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(Vs + e_lds[j]) = ereg0[j];
+            for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(Vs + skip.lds[j]) = ereg0[j];
         }
         __syncthreads();
 
@@ -989,10 +1040,10 @@ __global__ void __launch_bounds__(256, 1) wino_n128_kernel(const KParams p) {
             const float* vb = smem + (es & 1) * WN_IMG;
             float* vn = smem + ((es + 1) & 1) * WN_IMG;
             const int es1 = min(es + 1, nextra - 1);
-            e_sel(min(es + 2, nextra - 1));
+            skip.sel(p, min(es + 2, nextra - 1), m0);
             auto a_read = [&](auto G, auto I) {
                 constexpr int g = decltype(G)::value, i = decltype(I)::value;
-                ga[g & 1][i] = *reinterpret_cast<const f32x4*>(vb + (i * 4 + g) * WN_POS + ea_off[g]);
+                ga[g & 1][i] = *reinterpret_cast<const f32x4*>(vb + (i * 4 + g) * WN_POS + skip.a_off[g]);
             };
             auto fill = [&](auto K) {
                 constexpr int k = decltype(K)::value, g = k >> 4, q = k & 15;
@@ -1003,7 +1054,7 @@ __global__ void __launch_bounds__(256, 1) wino_n128_kernel(const KParams p) {
                     if constexpr (g < 3) a_read(DS_WINO_I(g + 1), DS_WINO_I(q - 1));
                 } else if constexpr (k < 9) {          // pixels of slab es+1
                     if constexpr (k == 5) DS_RACE_SKEW(wave);
-                    *reinterpret_cast<f32x4*>(vn + e_lds[k - 5]) = ereg[k - 5];
+                    *reinterpret_cast<f32x4*>(vn + skip.lds[k - 5]) = ereg[k - 5];
                 } else if constexpr (k < 13) {         // loads of slab es+2
                     e_load1(ereg, DS_WINO_I(k - 9));
                 }
@@ -1026,10 +1077,6 @@ __global__ void __launch_bounds__(256, 1) wino_n128_kernel(const KParams p) {
             __syncthreads();                           // V[es & 1] dead; V[(es+1) & 1] published
         } while (++es < nextra);
     }
-#undef DS_WINO_EACH16
-#undef DS_WINO_EACH12
-#undef DS_WINO_EACH4
-#undef DS_WINO_I
 
     // ---- the fused epilogue, one patch pixel (a, b) at a time: the first kernel's, on this wave's 32 tiles x 32 channels ------------------
     float* stage = smem + wave * 32 * WINO_EPI_LD;     // wave-private rows; every LDS buffer died at the last barrier
@@ -1093,30 +1140,20 @@ __global__ void __launch_bounds__(256, 1) wino_n128_kernel(const KParams p) {
     }
 }
 
-template <int NORM, int NSL>
-int launch_wino_n128_ns(KParams& p, hipStream_t stream) {
-    const int smem = (2 * WN_IMG + 2 * (p.NP * WINO_K + 4)) * (int)sizeof(float);    // Vs and Hs doubled; + a spare halo cell each
-    DS_ENSURE_DYN_LDS((&wino_n128_kernel<NORM, NSL>), 64 * 1024);
-    hipLaunchKernelGGL((wino_n128_kernel<NORM, NSL>), dim3(grid_1d(p.mtiles, p.ntiles)), dim3(256), smem, stream, p);
-    DS_CHECK_LAUNCH();
-    return DS_OK;
-}
-
-template <int NORM>
-int launch_wino_n128_n(KParams& p, hipStream_t stream) {
-    return p.NP * 2 <= 2 * 256 ? launch_wino_n128_ns<NORM, 2>(p, stream) : launch_wino_n128_ns<NORM, 3>(p, stream);
-}
-
 int launch_wino_n128(KParams& p, hipStream_t stream) {
-    if (!p.norm) return launch_wino_n128_n<0>(p, stream);
-    return p.norm_act == DS_ACT_SILU ? launch_wino_n128_n<2>(p, stream) : launch_wino_n128_n<1>(p, stream);
+    const int smem = (2 * WN_IMG + 2 * (p.NP * WINO_K + 4)) * (int)sizeof(float);    // Vs and Hs doubled; + a spare halo cell each
+    return wino_by_norm(p, [&](auto NORM) {
+        constexpr int norm = decltype(NORM)::value;
+        return p.NP * 2 <= 2 * 256 ? wino_launch<wino_n128_kernel<norm, 2>, 256, 64 * 1024>(p, smem, stream)
+                                   : wino_launch<wino_n128_kernel<norm, 3>, 256, 64 * 1024>(p, smem, stream);
+    });
 }
 
-// ---- the 32 x 128 tile on eight waves, two per SIMD (header comment, "Two waves per SIMD") ---------------------------------------------------
+// ---- wino_w8_kernel: the 32 x 128 tile on eight waves, two per SIMD (header comment) --------------------------------------------------------
 constexpr int W8_NSH = 1;                         // halo float4 slots per thread: NP * 2 <= 512, i.e. 16- and 32-column images (NP = 180, 204)
 constexpr int W8_XCH = 4 * 16 * 64;               // floats a wave passes to its partner: four accumulators x 16 registers x 64 lanes (16 KiB)
 
-// NORM: as above
+// NORM: WinoHalo's
 template <int NORM>
 __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1135,87 +1172,18 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
     const int Ctot = p.c0 + p.c1;
     const int nslabs = Ctot / WINO_K;
 
-    // ---- halo slots of this thread: as in the other kernels, the (128 / W + 2) x (W + 2) halo over 512 threads ----------------------------
-    const int kh_h = tid & 1;
-    const int h_buf = p.NP * WINO_K + 4;           // floats per buffer of Hs, its spare cell included
-    unsigned h_off0[W8_NSH], h_off1[W8_NSH];
-    int h_lds[W8_NSH];
-#pragma unroll
-    for (int j = 0; j < W8_NSH; ++j) {
-        const int hp = (tid + j * 512) >> 1;
-        const int hr = hp / p.WP, hc = hp - hr * p.WP;
-        const int y = r0 + hr - 1, x = hc - 1;
-        const bool in = hp < p.NP;
-        const bool ok = in && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
-        const int pix = min(max(y, 0), p.H - 1) * p.W + min(max(x, 0), p.W - 1);
-        h_off0[j] = (unsigned)(pix * p.lda0 + kh_h * 4) * 4u;
-        h_off1[j] = (unsigned)(pix * p.lda1 + kh_h * 4) * 4u;
-        const int cell = (((kh_h * 2 + (hc & 1)) * p.HP + hr) * WPH + (hc >> 1)) * 4;
-        h_lds[j] = ok ? cell : p.NP * WINO_K;
-        if (in && !ok) {                           // an out-of-image cell: zeros, once, in both buffers (published by the prologue's first barrier)
-            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            *reinterpret_cast<f32x4*>(Hs + cell) = z;
-            *reinterpret_cast<f32x4*>(Hs + h_buf + cell) = z;
-        }
-    }
-    const float* a0i = p.a0 + (size_t)img0 * p.HW * p.lda0;
-    const float* a1i = p.a1 + (size_t)img0 * p.HW * p.lda1;
-    const float* cpi = p.norm + (size_t)img0 * 3 * Ctot;
-    unsigned c_lane = (unsigned)(kh_h * 16);
-    struct HaloRegs {
-        f32x4 h[W8_NSH];
-        f32x4 mu = {0.f, 0.f, 0.f, 0.f}, ga = {1.f, 1.f, 1.f, 1.f}, be = {0.f, 0.f, 0.f, 0.f};
-    };
-    HaloRegs hreg;
-    float h_t[4 * W8_NSH], h_u[4 * W8_NSH];
-    const float* h_src = nullptr;
-    unsigned h_sel = 0;
-    auto halo_src = [&](int s) {
-        const int c = s * WINO_K;
-        const bool first = c < p.c0;
-        h_src = first ? a0i + c : a1i + (c - p.c0);
-        h_sel = (unsigned)__builtin_amdgcn_readfirstlane(first ? -1 : 0);
-        asm volatile("" : "+s"(h_sel));
-    };
-    auto halo_load1 = [&](HaloRegs& R, auto J) {
-        constexpr int j = decltype(J)::value;
-        if constexpr (j < W8_NSH) {
-            const unsigned off = (h_off0[j] & h_sel) | (h_off1[j] & ~h_sel);
-            R.h[j] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(h_src) + off);
-        }
-    };
-    auto coef_load1 = [&](HaloRegs& R, int s, auto I) {
-        constexpr int i = decltype(I)::value;
-        if constexpr (NORM != 0) {
-            const char* cs = reinterpret_cast<const char*>(cpi + (size_t)i * Ctot + s * WINO_K);
-            asm volatile("" : "+v"(c_lane));
-            const f32x4 v = *reinterpret_cast<const f32x4*>(cs + c_lane);
-            if constexpr (i == 0) R.mu = v; else if constexpr (i == 1) R.ga = v; else R.be = v;
-        }
-    };
-    // the first kernel's element chain, operation for operation
-    auto halo_chain = [&](HaloRegs& R, float* hs, auto C, auto ST) {
-        constexpr int c = decltype(C)::value, st = decltype(ST)::value, j = c >> 2, e = c & 3;
-        if constexpr (j < W8_NSH) {
-            if constexpr (st == 0 && NORM != 0) {
-                h_t[c] = __builtin_fmaf(R.h[j][e] - R.mu[e], R.ga[e], R.be[e]);
-                if constexpr (NORM == 2) h_u[c] = __expf(-h_t[c]);
-            }
-            if constexpr (st == 1 && NORM == 2) h_u[c] = __builtin_amdgcn_rcpf(1.0f + h_u[c]);
-            if constexpr (st == 2) {
-                float v = R.h[j][e];
-                if constexpr (NORM == 1) v = h_t[c];
-                if constexpr (NORM == 2) v = h_t[c] * h_u[c];
-                R.h[j][e] = v;
-                if constexpr (e == 3) *reinterpret_cast<f32x4*>(hs + h_lds[j]) = R.h[j];
-            }
-        }
-    };
+    // ---- halo stage: one float4 slot per thread over 512 threads -------------------------------------------------------------------------
+    using Halo = WinoHalo<512, W8_NSH, W8_NSH, NORM>;
+    Halo halo(p, Hs, tid, img0, r0);
+    const int h_buf = halo.buf;
+    typename Halo::Regs hreg;
+    auto halo_load1 = [&](typename Halo::Regs& R, auto J) { halo.load1(R, J); };
+    auto coef_load1 = [&](typename Halo::Regs& R, int sl, auto I) { halo.coef1(R, sl, I); };
 
     // ---- input transform: 32 tiles x 4 channel pairs, each split over FOUR threads by rows of B^T d B.  A thread owns (tile t_t, channels
     // 4 kh_t + 2 cpl .. + 1, row t_row): it reads the two rows of d its row of B^T d is made of (d0 - d2, d1 + d2, d2 - d1, d1 - d3) and
     // writes four positions.  kh_t and t_row are uniform per wave (wave = kh_t + 2 t_row): scalar branches, the same instruction count in
-    // every wave.  Every value is made by the first kernel's operations on the same operands.
+    // every wave.  Every value is made by the 64 x 64 kernel's operations on the same operands.
     const int t_t = (tid >> 1) & 31, cpl = tid & 1, kh_t = wave & 1, t_row = wave >> 1;
     const int t_ty = t_t / Wt, t_tx = t_t - t_ty * Wt;
     const int h_rd0 = ((kh_t * 2 * p.HP + 2 * t_ty + (t_row == 0 ? 0 : 1)) * WPH + t_tx) * 4 + cpl * 2;     // row 0 | 1 | 1 | 1 of d
@@ -1268,41 +1236,26 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
         for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
     const int a_off = ((lane >> 5) * 32 + (lane & 31)) * 4 + ph * 8 * WN_POS;
 
-#define DS_WINO_I(n) std::integral_constant<int, (n)>{}
-#define DS_WINO_EACH4(F) F(0) F(1) F(2) F(3)
-#define DS_WINO_EACH8(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7)
-#define DS_WINO_EACH16(F, b) F((b) + 0) F((b) + 1) F((b) + 2) F((b) + 3) F((b) + 4) F((b) + 5) F((b) + 6) F((b) + 7)                \
-                             F((b) + 8) F((b) + 9) F((b) + 10) F((b) + 11) F((b) + 12) F((b) + 13) F((b) + 14) F((b) + 15)
-#define DS_WINO_LOADS(R, sl)                                                                                                           \
-    halo_load1(R, DS_WINO_I(0));                                                                                                       \
-    coef_load1(R, sl, DS_WINO_I(0)); coef_load1(R, sl, DS_WINO_I(1)); coef_load1(R, sl, DS_WINO_I(2));
-
     // ---- prologue: halo 0 and 1 and transform 0 staged, halo 2 and the weights of (slab 0, group 0) requested (two barriers) -----------
-    halo_src(0);
-    DS_WINO_LOADS(hreg, 0)
+    halo.src(0);
+    halo.loads(hreg, 0);
     {
-        HaloRegs hreg1;
+        typename Halo::Regs hreg1;
         const int s1 = min(1, nslabs - 1);
-        halo_src(s1);
-        DS_WINO_LOADS(hreg1, s1)
+        halo.src(s1);
+        halo.loads(hreg1, s1);
 #define DS_WINO_F(i) b_load1(u_src, DS_WINO_I(0), DS_WINO_I(i));
         DS_WINO_EACH4(DS_WINO_F)
 #undef DS_WINO_F
         DS_RACE_SKEW(wave);
-#define DS_WINO_CHAIN1(c) halo_chain(hreg, Hs, DS_WINO_I(c), DS_WINO_I(0)); halo_chain(hreg, Hs, DS_WINO_I(c), DS_WINO_I(1));          \
-                          halo_chain(hreg, Hs, DS_WINO_I(c), DS_WINO_I(2));
-        DS_WINO_EACH4(DS_WINO_CHAIN1)
-#undef DS_WINO_CHAIN1
+        halo.store(hreg, Hs);
         DS_RACE_SKEW(wave);
-#define DS_WINO_CHAIN1(c) halo_chain(hreg1, Hs + h_buf, DS_WINO_I(c), DS_WINO_I(0)); halo_chain(hreg1, Hs + h_buf, DS_WINO_I(c), DS_WINO_I(1)); \
-                          halo_chain(hreg1, Hs + h_buf, DS_WINO_I(c), DS_WINO_I(2));
-        DS_WINO_EACH4(DS_WINO_CHAIN1)
-#undef DS_WINO_CHAIN1
+        halo.store(hreg1, Hs + h_buf);
     }
     {
         const int s2 = min(2, nslabs - 1);
-        halo_src(s2);
-        DS_WINO_LOADS(hreg, s2)
+        halo.src(s2);
+        halo.loads(hreg, s2);
     }
     __syncthreads();                                   // Hs[0], Hs[1] published
 #define DS_WINO_TR1(i) tr_read1(Hs, DS_WINO_I(i));
@@ -1332,11 +1285,8 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
         DS_WINO_EACH8(DS_WINO_TR1)
 #undef DS_WINO_TR1
         DS_RACE_SKEW(wave);                            // halo of slab s+2 (its loads were issued a slab ago)
-#define DS_WINO_CHAIN1(c) halo_chain(hreg, hb, DS_WINO_I(c), DS_WINO_I(0)); halo_chain(hreg, hb, DS_WINO_I(c), DS_WINO_I(1));          \
-                          halo_chain(hreg, hb, DS_WINO_I(c), DS_WINO_I(2));
-        DS_WINO_EACH4(DS_WINO_CHAIN1)
-#undef DS_WINO_CHAIN1
-        halo_src(s3);
+        halo.store(hreg, hb);
+        halo.src(s3);
         DS_RACE_SKEW(wave);
         tr_write(vbn);                                 // second half: its adds, registers -> Vs[par ^ 1]
         // micro-slot k of group g = k >> 4 (positions 8 ph + 4 g .. + 3), one memory instruction at most:
@@ -1372,10 +1322,9 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
 #undef DS_WINO_STEP
         __syncthreads();                               // slab s done: Vs[par] dead; Vs and Hs [par ^ 1] published
     } while (++s < nslabs);
-#undef DS_WINO_LOADS
 
-    // ---- output transform Y = A^T M A across the pair.  The sums over the row index i of position 4 i + j come first, as in the other
-    // kernels: patch row 0 is (M[j] + M[4 + j]) + M[8 + j], patch row 1 is (M[4 + j] - M[8 + j]) - M[12 + j].  The wave of half 0 holds rows
+    // ---- output transform Y = A^T M A across the pair.  The sums over the row index i of position 4 i + j come first, as in the lane-local
+    // output transform: patch row 0 is (M[j] + M[4 + j]) + M[8 + j], patch row 1 is (M[4 + j] - M[8 + j]) - M[12 + j].  The wave of half 0 holds rows
     // i = 0, 1 and finishes patch row 0, for which it needs row 2 of its partner; the wave of half 1 holds rows 2, 3 and finishes patch row
     // 1, for which it needs row 1.  Each passes those four accumulators through the LDS (every K-loop buffer died at the last barrier):
     // wave w writes 16 KiB at smem + w * W8_XCH as [accumulator][register quad][lane][4] and reads the same cells of wave w ^ 4 -- the
@@ -1412,47 +1361,21 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
         Y[1] = t[1] - t[2] - t[3];
     }
 
-    // ---- appended 1x1 slabs: wino_n128_kernel's loop on this wave's TWO patch pixels (ph, 0) and (ph, 1): 32 MFMAs per slab and wave in
-    // the order group, K step r, patch pixel.  The slab's 128 pixels x 32 raw channels go global -> registers -> a V buffer (two float4 per
-    // thread, the same swizzled layout; V[0] = Vs[0], V[1] = Vs[1]); the wave's 32 weight columns go global -> the fragment registers
-    // gb[group], each group's weights of slab es+1 requested right behind the group's last MFMA of slab es.  ONE barrier per slab:
+    // ---- appended 1x1 slabs (header comment, "Skip slabs") on this wave's TWO patch pixels (ph, 0) and (ph, 1): 32 MFMAs per slab and
+    // wave.  The slab's 128 pixels x 32 raw channels go through V[0] = Vs[0], V[1] = Vs[1], two float4 per thread; the wave's 32 weight
+    // columns go global -> the fragment registers gb[group], each group's weights of slab es+1 requested right behind the group's last
+    // MFMA of slab es.  Slots:
     //     slot 8 g         (g >= 1) the weight fragment of group g-1 of slab es+1; slot 31: of group 3
     //     slots 8 g + 1, 2 the two pixel fragment reads of group g+1
     //     slots 3, 4       the two ds_write_b128 of the pixels of slab es+1 -> V[(es+1) & 1]
     //     slots 5, 6       the two global loads of slab es+2 into the registers just stored
-    // es+1 / es+2 clamped to the last slab.  The barrier in front keeps the staging from overwriting what a partner has yet to read.
+    // The barrier in front keeps the staging from overwriting what a partner has yet to read.
     const int nextra = (p.ec0 + p.ec1) / 32;
     if (nextra > 0) {
         __syncthreads();
         const float* wsk = p.b + (size_t)(p.N / 64) * nslabs * WINO_IMG + (size_t)(2 * nt + (cg >> 1)) * nextra * 2048;
-        const int e_chunk = tid & 7;                   // channels 4 e_chunk .. + 3 of the slab: group e_chunk >> 1, kh = e_chunk & 1
-        int e_lds[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int lp = (tid >> 3) + 64 * j;        // pixel of the tile
-            const int yl = lp / p.W, x = lp - yl * p.W;
-            const int pp = (yl & 1) * 2 + (x & 1), t = (yl >> 1) * Wt + (x >> 1);
-            e_lds[j] = (((pp * 4 + (e_chunk >> 1)) * 2 + (e_chunk & 1)) * 32 + (t ^ e_chunk)) * 4;
-        }
-        int ea_off[4];                                 // fragment offset of group g, swizzled: row ^ (2 g + kh)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) ea_off[g] = ((lane >> 5) * 32 + ((lane & 31) ^ (2 * g + (lane >> 5)))) * 4;
-        const unsigned e_t0 = (unsigned)((tid >> 3) * p.elda0 + e_chunk * 4), e_t1 = (unsigned)((tid >> 3) * p.elda1 + e_chunk * 4);
-        const float* e_src = nullptr;
-        unsigned e_off = 0;
-        int e_step = 0;
-        auto e_sel = [&](int es) {
-            const int c = es * 32;
-            const bool first = c < p.ec0;
-            const int ld = first ? p.elda0 : p.elda1;
-            e_src = (first ? p.e0 + c : p.e1 + (c - p.ec0)) + (size_t)m0 * ld;
-            e_step = 64 * ld;
-            e_off = first ? e_t0 : e_t1;
-        };
-        auto e_load1 = [&](f32x4* dst, auto J) {
-            constexpr int j = decltype(J)::value;
-            dst[j] = *reinterpret_cast<const f32x4*>(e_src + (size_t)(j * e_step) + e_off);
-        };
+        WinoSkip<512, 32> skip(p, tid, lane, 0);
+        auto e_load1 = [&](f32x4* dst, auto J) { skip.load1(dst, J); };
         f32x4 ga[2][2], gb[4];                         // fragments: the two patch pixels' pixels of group g, and the weights of every group
         auto w_load1 = [&](int es, auto G) {
             constexpr int g = decltype(G)::value;
@@ -1467,13 +1390,13 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
         {
             f32x4 ereg0[2];
             w_load1(0, DS_WINO_I(0)); w_load1(0, DS_WINO_I(1)); w_load1(0, DS_WINO_I(2)); w_load1(0, DS_WINO_I(3));
-            e_sel(0);
+            skip.sel(p, 0, m0);
             e_load1(ereg0, DS_WINO_I(0)); e_load1(ereg0, DS_WINO_I(1));
-            e_sel(min(1, nextra - 1));
+            skip.sel(p, min(1, nextra - 1), m0);
             e_load1(ereg, DS_WINO_I(0)); e_load1(ereg, DS_WINO_I(1));
             DS_RACE_SKEW(wave);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) *reinterpret_cast<f32x4*>(Vs + e_lds[j]) = ereg0[j];
+            for (int j = 0; j < 2; ++j) *reinterpret_cast<f32x4*>(Vs + skip.lds[j]) = ereg0[j];
         }
         __syncthreads();
 
@@ -1482,10 +1405,10 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
             const float* vb = smem + (es & 1) * WN_IMG + ph * 8 * WN_POS;      // patch pixels 2 ph, 2 ph + 1
             float* vn = smem + ((es + 1) & 1) * WN_IMG;
             const int es1 = min(es + 1, nextra - 1);
-            e_sel(min(es + 2, nextra - 1));
+            skip.sel(p, min(es + 2, nextra - 1), m0);
             auto a_read = [&](auto G, auto I) {
                 constexpr int g = decltype(G)::value, i = decltype(I)::value;
-                ga[g & 1][i] = *reinterpret_cast<const f32x4*>(vb + (i * 4 + g) * WN_POS + ea_off[g]);
+                ga[g & 1][i] = *reinterpret_cast<const f32x4*>(vb + (i * 4 + g) * WN_POS + skip.a_off[g]);
             };
             auto fill = [&](auto K) {
                 constexpr int k = decltype(K)::value, g = k >> 3, q = k & 7;
@@ -1495,7 +1418,7 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
                     if constexpr (g < 3) a_read(DS_WINO_I(g + 1), DS_WINO_I(q - 1));
                 } else if constexpr (k < 5) {          // pixels of slab es+1
                     if constexpr (k == 3) DS_RACE_SKEW(wave);
-                    *reinterpret_cast<f32x4*>(vn + e_lds[k - 3]) = ereg[k - 3];
+                    *reinterpret_cast<f32x4*>(vn + skip.lds[k - 3]) = ereg[k - 3];
                 } else if constexpr (k < 7) {          // loads of slab es+2
                     e_load1(ereg, DS_WINO_I(k - 5));
                 } else if constexpr (k == 31) {
@@ -1516,10 +1439,6 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
             __syncthreads();                           // V[es & 1] dead; V[(es+1) & 1] published
         } while (++es < nextra);
     }
-#undef DS_WINO_EACH16
-#undef DS_WINO_EACH8
-#undef DS_WINO_EACH4
-#undef DS_WINO_I
 
     // ---- the fused epilogue of patch row ph, one patch pixel at a time: the first kernel's, on this wave's 32 tiles x 32 channels.  The
     // staging rows lie in the cells this wave alone read in the exchange (its partner wrote them in front of the exchange's barrier).
@@ -1581,41 +1500,29 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
     }
 }
 
-template <int NORM>
-int launch_wino_w8_n(KParams& p, hipStream_t stream) {
+int launch_wino_w8(KParams& p, hipStream_t stream) {
     // the K loop's Vs and Hs (doubled; + a spare halo cell each) and, behind its last barrier, the eight waves' exchange
     const int kloop = (2 * WN_IMG + 2 * (p.NP * WINO_K + 4)) * (int)sizeof(float), xch = 8 * W8_XCH * (int)sizeof(float);
-    DS_ENSURE_DYN_LDS((&wino_w8_kernel<NORM>), 160 * 1024);
-    hipLaunchKernelGGL((wino_w8_kernel<NORM>), dim3(grid_1d(p.mtiles, p.ntiles)), dim3(512), kloop > xch ? kloop : xch, stream, p);
-    DS_CHECK_LAUNCH();
-    return DS_OK;
-}
-
-int launch_wino_w8(KParams& p, hipStream_t stream) {
-    if (!p.norm) return launch_wino_w8_n<0>(p, stream);
-    return p.norm_act == DS_ACT_SILU ? launch_wino_w8_n<2>(p, stream) : launch_wino_w8_n<1>(p, stream);
-}
-
-
-template <int VAR, int NORM, int NSL>
-int launch_wino_ns(KParams& p, hipStream_t stream) {
-    const int smem = (4 * WINO_IMG + 2 * (p.NP * WINO_K + 4)) * (int)sizeof(float);  // Us, Vs and Hs doubled; + a spare halo cell each
-    DS_ENSURE_DYN_LDS((&conv3x3_wino_kernel<VAR, NORM, NSL>), 160 * 1024);
-    hipLaunchKernelGGL((conv3x3_wino_kernel<VAR, NORM, NSL>), dim3(grid_1d(p.mtiles, p.ntiles)), dim3(256), smem, stream, p);
-    DS_CHECK_LAUNCH();
-    return DS_OK;
-}
-
-template <int VAR, int NORM>
-int launch_wino_n(KParams& p, hipStream_t stream) {
-    return p.NP * 2 <= 3 * 256 ? launch_wino_ns<VAR, NORM, 3>(p, stream) : launch_wino_ns<VAR, NORM, 4>(p, stream);
+    return wino_by_norm(p, [&](auto NORM) {
+        return wino_launch<wino_w8_kernel<decltype(NORM)::value>, 512, 160 * 1024>(p, kloop > xch ? kloop : xch, stream);
+    });
 }
 
 template <int VAR>
 int launch_wino(KParams& p, hipStream_t stream) {
-    if (!p.norm) return launch_wino_n<VAR, 0>(p, stream);
-    return p.norm_act == DS_ACT_SILU ? launch_wino_n<VAR, 2>(p, stream) : launch_wino_n<VAR, 1>(p, stream);
+    const int smem = (4 * WINO_IMG + 2 * (p.NP * WINO_K + 4)) * (int)sizeof(float);  // Us, Vs and Hs doubled; + a spare halo cell each
+    return wino_by_norm(p, [&](auto NORM) {
+        constexpr int norm = decltype(NORM)::value;
+        return p.NP * 2 <= 3 * 256 ? wino_launch<conv3x3_wino_kernel<VAR, norm, 3>, 256, 160 * 1024>(p, smem, stream)
+                                   : wino_launch<conv3x3_wino_kernel<VAR, norm, 4>, 256, 160 * 1024>(p, smem, stream);
+    });
 }
+
+#undef DS_WINO_EACH16
+#undef DS_WINO_EACH12
+#undef DS_WINO_EACH8
+#undef DS_WINO_EACH4
+#undef DS_WINO_I
 
 }  // namespace
 
