@@ -706,44 +706,61 @@ extern "C" int ds_conv_route(const ds_conv_args* a, ds_conv_route_info* info) {
 
 // fp16 operands on fp32 activations in a 3x3 layer: no kernel (the fp16-activation kernels replaced it); the entry point stays for the ABI
 extern "C" int ds_conv_f16_supported(int, int, int, int, int, int, int) { return 0; }
+
+// ---- The geometry-only availability predicates are route queries: each describes its shape as the ds_conv_args a launch of that shape alone
+// would carry -- dense rows, no bias / residual / statistics / workspace, every pointer the aligned placeholder below (route_conv asks of
+// a pointer only whether it is set and aligned) -- and reads the answer off ds_conv_kernel_id, i.e. off route_conv like the launch itself.
+alignas(16) static float shape_placeholder[4];
+
+static ds_conv_args shape_args(int taps, long long n, int h, int w, int c0, int c1, int ec0, int ec1, int cout) {
+    ds_conv_args a{};
+    float* const m = shape_placeholder;
+    a.x0 = m; a.c0 = c0; a.ld0 = c0;
+    if (c1) { a.x1 = m; a.c1 = c1; a.ld1 = c1; }
+    if (ec0) { a.e0 = m; a.ec0 = ec0; a.eld0 = ec0; }
+    if (ec1) { a.e1 = m; a.ec1 = ec1; a.eld1 = ec1; }
+    a.n = n > 0x7fffffffLL ? -1 : (int)n;        // (row counts arrive as long long: more than an int holds is no shape of the library)
+    a.h = h; a.w = w; a.taps = taps;
+    a.wgt = m; a.cout = cout; a.out = m; a.out_ld = cout; a.out_scale = 1.0f;
+    return a;
+}
+
 extern "C" int ds_conv_f16dma_supported(int n, int h, int w, int c0, int ec0, int cout) {
-    KParams p{};
-    p.taps = 9; p.stride = 1; p.H = h; p.W = w; p.HW = h * w; p.M = n * h * w; p.N = cout; p.c0 = c0; p.ec0 = ec0;
-    p.vec_ok = 1; p.nrows_b = ((cout + BN - 1) / BN) * BN;
-    return conv3x3_f16dma_applicable(p) ? 1 : 0;
+    ds_conv_args a = shape_args(9, n, h, w, c0, 0, ec0, 0, cout);
+    a.in_f16 = a.wgt_f16 = 1;
+    const int id = ds_conv_kernel_id(&a);
+    return id == 2566 || id == 2572;
 }
 extern "C" int ds_gemm_f16dma_supported(long long rows, int k, int cout) {
-    KParams p{};
-    if (rows > 0x7fffffffLL || rows < 1) return 0;
-    p.taps = 1; p.stride = 1; p.M = (int)rows; p.N = cout; p.K = k; p.c0 = k; p.vec_ok = 1; p.nrows_b = ((cout + BN - 1) / BN) * BN;
-    return gemm_f16dma_applicable(p) ? 1 : 0;
+    ds_conv_args a = shape_args(1, rows, 1, 1, k, 0, 0, 0, cout);
+    a.in_f16 = a.wgt_f16 = 1;
+    return ds_conv_kernel_id(&a) == 2567;
 }
 extern "C" int ds_conv_f16dma_stride2_supported(int n, int h, int w, int c0, int cout) {
-    KParams p{};
-    const long long M = (long long)n * h * w;
-    if (n < 1 || h < 1 || w < 1 || M > 0x7fffffffLL / 4) return 0;
-    p.taps = 9; p.stride = 2; p.H = h; p.W = w; p.HW = h * w; p.IH = 2 * h; p.IW = 2 * w; p.M = (int)M; p.N = cout; p.c0 = c0; p.K = 9 * c0;
-    p.vec_ok = 1; p.nrows_b = ((cout + BN - 1) / BN) * BN;
-    return gemm_f16dma_gather_applicable(p) ? 1 : 0;
+    ds_conv_args a = shape_args(9, n, h, w, c0, 0, 0, 0, cout);
+    a.in_f16 = a.wgt_f16 = 1; a.stride = 2;
+    return ds_conv_kernel_id(&a) == 2571;
 }
 extern "C" int ds_gemm_f16_supported(long long rows, int c0, int c1) {
-    KParams p{};
-    if (rows > 0x7fffffffLL) return 0;
-    p.taps = 1; p.stride = 1; p.M = (int)rows; p.N = 128; p.K = c0 + c1; p.c0 = c0; p.c1 = c1; p.nrows_b = 128;
-    return gemm_f16_applicable(p) ? 1 : 0;
+    ds_conv_args a = shape_args(1, rows, 1, 1, c0, c1, 0, 0, 128);
+    a.wgt_f16 = 1;
+    return ds_conv_kernel_id(&a) == 2564;
 }
+// the number of forms the split-fp16 kernel takes: on raw input, and with the fused input normalisation (not at 8x8: four images per tile,
+// the normalisation planes are per image)
 extern "C" int ds_conv_split_supported(int n, int h, int w, int c0, int c1, int ec0, int ec1) {
-    KParams p{};
-    p.taps = 9; p.H = h; p.W = w; p.HW = h * w; p.M = n * h * w; p.N = 128; p.c0 = c0; p.c1 = c1; p.ec0 = ec0; p.ec1 = ec1;
-    p.nrows_b = 128;
-    if (!conv3x3_halo2_applicable(p, 1)) return 0;
-    return w >= 16 ? 2 : 1;                      // 8x8: four images per tile, the per-image normalisation planes are not fused
+    ds_conv_args a = shape_args(9, n, h, w, c0, c1, ec0, ec1, 128);
+    a.wgt_f16 = 2;
+    int forms = ds_conv_kernel_id(&a) == 2563;
+    a.norm_coefs = shape_placeholder; a.norm_act = DS_ACT_SILU;
+    forms += ds_conv_kernel_id(&a) == 2563;
+    return forms;
 }
 
 extern "C" int ds_conv3x3_halo_supported(int h, int w) {
-    KParams p{};
-    p.taps = 9; p.H = h; p.W = w; p.HW = h * w;
-    return conv3x3_halo_supported(p) ? 1 : 0;
+    const ds_conv_args a = shape_args(9, 1, h, w, 32, 0, 0, 0, 128);         // an fp32 3x3 layer of that geometry: the LDS-halo family?
+    const int id = ds_conv_kernel_id(&a);
+    return id == 128 || id == 256 || id == 1284 || id == 2565 || id == 2568;
 }
 
 extern "C" int ds_gemm_nt_batched(const ds_gemm_args* a, void* stream) {

@@ -246,7 +246,7 @@ class UNetEngine:
                     x1, c1 = skips.pop()
                     assert c1 == b.skip_cin and c0 + c1 == b.cin
                 # a block whose attention runs on the fp32 kernels keeps fp32 outputs; every consumer reads a tensor in the dtype it has
-                f16_out = ws.stream16 and (not b.heads or self._attn16(B, b))
+                f16_out = ws.stream16 and (not b.heads or self._attn16(bd, B, b))
                 block = self._block16 if self._dma16(bd, B, b) else self._block32
                 c1_in, c1_w, c1_kw = block(bd, ws, b, x0, c0, x1, c1)
                 out = self._block_out(bd, ws, b, f16_out)
@@ -338,11 +338,10 @@ class UNetEngine:
         """Do both 3x3 convolutions of the block run on the fp16-activation kernels (conv1 with the fused skip projection's columns)?"""
         return bool(bd.f16_conv_ok(B, b.res_out, b.cin, 0, b.cout) and bd.f16_conv_ok(B, b.res_out, b.cout, b.cin if b.skip_conv else 0, b.cout))
 
-    def _attn16(self, B, b):
+    def _attn16(self, bd, B, b):
         """Attention block on the fp16 kernels end to end (CIFAR-10's single 256-wide head is not: fp32 kernel)?"""
-        M, lib = B * b.res_out ** 2, self.lib
-        return bool(self.conv_mode == 1 and lib.ds_attention_f16_supported(b.cout // b.heads)
-                    and lib.ds_gemm_f16dma_supported(M, b.cout, 3 * b.cout) and lib.ds_gemm_f16dma_supported(M, b.cout, b.cout))
+        M = B * b.res_out ** 2
+        return bool(self.lib.ds_attention_f16_supported(b.cout // b.heads) and bd.gemm16_ok(M, b.cout, 3 * b.cout) and bd.gemm16_ok(M, b.cout, b.cout))
 
     def _emb_kw(self, ws, b):
         """(conv0's per-image embedding bias, norm1's adaptive scale / shift) of a block: one of the two is empty."""
@@ -429,9 +428,8 @@ class UNetEngine:
         cb, ss = self._emb_kw(ws, b)
         src = dict(x1=x1, c1=c1, ld1=c1)
         w16_0 = w.get(f'{nm}.conv0.w16')
-        fuse = bool(self.lib.ds_conv3x3_halo_supported(Ho, Ho))     # GroupNorm+SiLU applied by the conv's halo loader
-        if w16_0 is not None and bd.f16_level(n, Ho, Ho, cin, 0, 0, 0) == 1:
-            fuse = False        # fp16 operands without the fused normalisation (8x8: four images per tile): normalise in a pass
+        # GroupNorm+SiLU applied by the conv's halo loader -- not where split-fp16 operands come without the fused normalisation: a pass there
+        fuse = bd.halo_ok(n, Ho) and not (w16_0 is not None and bd.split_needs_pass(n, Ho, cin))
         conv0 = dict(bias=w[f'{nm}.conv0.b'], stats=True, w16=w16_0, **cb)      # (+ per-image embedding for the non-adaptive variant)
         wup = w.get(f'{nm}.conv0.wup') if b.up and w16_0 is None else None
         if self.fir and rs != DS_RESAMPLE_NONE:
@@ -539,7 +537,7 @@ class UNetEngine:
         G = arch.num_groups(cout)
         # fp16 mode: the GroupNorm output and the attention output are only operands of the qkv / proj 1x1s, and q | k | v are the rows the
         # reference's qkv projection emits (networks_edm.py:171-173) -> fp16 rows, streamed by the fp16-activation GEMM (csrc/gemm_f16dma.hip)
-        if self._attn16(n, b):
+        if self._attn16(bd, n, b):
             n2, ao, qk = ws.n2_16[:M * cout].view(M, cout), ws.ao_16[:M * cout].view(M, cout), ws.qk_16
         else:
             n2, ao, qk = ws.n2, ws.ao, ws.qk
@@ -558,7 +556,7 @@ class UNetEngine:
         """Output head: GroupNorm + SiLU + 3x3 conv to the channel-planar network output, with the solver update fused where it can be."""
         spec, w, lib, P = self.spec, self.w, self.lib, bd.P
         B, R, G = ws.B, spec.img_resolution, arch.num_groups(co)
-        if lib.ds_conv3x3_halo_supported(R, R) and xo.dtype == torch.float32:
+        if bd.halo_ok(B, R) and xo.dtype == torch.float32:
             bd.norm('stats', xo, co, co, B, R, R, 'out.norm.stats', groups=G, eps=spec.out_eps, gamma=w['out.g'], beta=w['out.b'], coefs=bd.coefs)
             bd.conv(xo, co, co, B, R, R, w['outc.w'], spec.out_channels, P.bufs['out'], 4, 9, 'out.conv', bias=w['outc.b'],
                     norm_coefs=bd.coefs, norm_act=DS_ACT_SILU, out_nchw=1, w16=w.get('outc.w16'))

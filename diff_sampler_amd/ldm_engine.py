@@ -229,9 +229,7 @@ class LDMUNetEngine:
             # fp16 mode: tensors that are only the operand of the next projection -- the GroupNorm output, the three LayerNorm outputs,
             # both attention outputs, the GEGLU product -- are stored as fp16 rows and streamed by the fp16-activation GEMM
             # (csrc/gemm_f16dma.hip); with the fp16 stream (`ts`) so is the transformer's residual stream t0 .. t3; q / k / v stay fp32
-            h16 = bool(bd.conv_mode == 1 and lib.ds_attention_f16_supported(d) and lib.ds_gemm_f16dma_supported(M, c, c)
-                       and lib.ds_gemm_f16dma_supported(M, c, 3 * c) and lib.ds_gemm_f16dma_supported(M, c, 8 * c)
-                       and lib.ds_gemm_f16dma_supported(M, 4 * c, c))
+            h16 = bool(lib.ds_attention_f16_supported(d) and all(bd.gemm16_ok(M, k, o) for k, o in ((c, c), (c, 3 * c), (c, 8 * c), (4 * c, c))))
             mk = bd.new16 if h16 else new
             ts = new_act if h16 else new                     # the transformer's residual stream t0 .. t3 and its output
             if not h16:
@@ -297,7 +295,7 @@ class LDMUNetEngine:
                     # (csrc/gemm_f16dma.hip, GATHER) and its output joins the fp16 stream (under autocast the reference's Downsample
                     # conv emits fp16, openaimodel.py:146-148); otherwise an fp32 copy of the input and the generic fp32 kernel
                     f16dn = bool(self.f16_downsample and w.get(f'{p}.w16') is not None and stream16 and cur[0].dtype == torch.float16
-                                 and lib.ds_conv_f16dma_stride2_supported(N, l.res_out, l.res_out, l.cin, l.cout))
+                                 and bd.stride2_ok(N, l.res_out, l.cin, l.cout))
                     if f16dn:
                         out = new_act(N * l.res_out ** 2, l.cout)
                         bd.conv(cur[0], l.cin, l.cin, N, l.res_out, l.res_out, w[f'{p}.w'], l.cout, out, l.cout, 9, p + '.op',

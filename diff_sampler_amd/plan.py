@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from types import SimpleNamespace
 from typing import Dict, List
 
 import torch
@@ -157,6 +158,12 @@ def tune_report():
 
 def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+# Stand-ins for a tensor where a layer is known by its shape alone (Builder.shape_args): a dtype and a 16-byte-aligned address -- ds_conv_route
+# asks of a pointer only whether it is set and aligned, and launches nothing
+F32, F16 = (SimpleNamespace(dtype=d, data_ptr=lambda: 16) for d in (torch.float32, torch.float16))
+HALO_IDS = (128, 256, 1284, 2565, 2568)          # ds_conv_kernel_id of the LDS-halo family (csrc/conv3x3_halo.hip)
 
 
 class Op:
@@ -328,16 +335,30 @@ class Builder:
         return wide
 
     def f16_conv_ok(self, n, side, cin, extra, cout, wide=False):
-        """Does this stride-1 3x3 layer (`extra` = channels of a fused 1x1 skip projection) run on an fp16-activation kernel?  fp16 mode and
-        whole 64-channel slabs only (the layers that have an fp16 weight packing); conv3x3_f16dma's own rule, which ends at 64 pixels.
-        wide: above 64 pixels the layer may take the patch kernel (csrc/conv3x3_f16wide.hip: power-of-two sides).  That kernel has one
-        source, no fused skip columns, no fused normalisation and no per-image bias row, so only a caller whose layers above 64 pixels are
-        all of that kind asks (the AutoencoderKL decoder); the denoisers' layers above 64 pixels keep the fp32 routes."""
-        if self.conv_mode != 1 or cin % 64 or cout % 64:
-            return False
-        if side > 64:
-            return bool(wide and not extra and side & (side - 1) == 0)
-        return bool(self.lib.ds_conv_f16dma_supported(n, side, side, cin, extra, cout))
+        """Does this stride-1 3x3 layer (`extra` = channels of a fused 1x1 skip projection) run on an fp16-activation kernel?  fp16 mode only;
+        the library's answer for the shape on fp16 rows: conv3x3_f16dma (kernel ids 2566 / 2572), which ends at 64 pixels.
+        wide: above 64 pixels the layer may take the patch kernel (2575, csrc/conv3x3_f16wide.hip).  That kernel has one source, no fused skip
+        columns, no fused normalisation and no per-image bias row, so only a caller whose layers above 64 pixels are all of that kind asks
+        (the AutoencoderKL decoder); the denoisers' layers above 64 pixels keep the fp32 routes."""
+        return self.conv_mode == 1 and self.routes_to(self.shape_args(n, side, cin, cout, in_f16=True, ec0=extra), 2566, 2572, *((2575,) if wide else ()))
+
+    def gemm16_ok(self, rows, k, cout):
+        """Does a 1x1 / Linear layer [rows][k] -> [rows][cout] on fp16 rows run on the fp16-activation GEMM (csrc/gemm_f16dma.hip)?"""
+        return self.conv_mode == 1 and self.routes_to(self.shape_args(rows, 1, k, cout, taps=1, in_f16=True), 2567)
+
+    def stride2_ok(self, n, side, cin, cout):
+        """Does the stride-2 3x3 layer with `side` x `side` OUTPUT images run on fp16 rows (the gather form of the fp16-activation GEMM)?"""
+        return self.conv_mode == 1 and self.routes_to(self.shape_args(n, side, cin, cout, in_f16=True, stride=2), 2571)
+
+    def halo_ok(self, n, side):
+        """Do fp32 3x3 layers on `side` x `side` images run on the LDS-halo kernels (the family that takes norm_coefs on fp32 rows)?"""
+        return self.routes_to(self.shape_args(n, side, 32, 128), *HALO_IDS)
+
+    def split_needs_pass(self, n, side, cin, ec0=0, ec1=0):
+        """Split mode: the split-fp16 kernel (2563) takes this 3x3 layer on raw input but not with the fused input normalisation (8x8 images:
+        four per tile, the normalisation planes are per image) -- both forms asked; the caller then normalises in a pass."""
+        takes = lambda **kw: self.routes_to(self.shape_args(n, side, cin, 128, w16=True, ec0=ec0, ec1=ec1, **kw), 2563)
+        return self.conv_mode == 2 and takes() and not takes(norm_coefs=F32, norm_act=DS_ACT_SILU)
 
     @staticmethod
     def fuses_norm16(mode, side, cout, x0, c0, x1=None, c1=0):
@@ -354,7 +375,7 @@ class Builder:
         fp16-activation matrix kernel, or (fuses_norm16 under the mode `fuse_norm16`) the convolution normalises its own LDS halo on the raw sources.  `e16` = (tensor,
         channels) or (tensor, channels, tensor, channels): raw fp16 source(s) of a fused 1x1 skip projection; an fp16 `out` is stored as such.
         Otherwise fp32 activations: the normalisation rides in the LDS-halo kernel's loader where that kernel takes the shape, else a
-        separate pass (also when the fp16-operand kernel is available for the normalised tensor but not with the fused normalisation)."""
+        separate pass (also where the split-fp16 kernel takes the normalised tensor but not the fused normalisation: split_needs_pass)."""
         assert self.coefs is not None and self.coefs.numel() >= 3 * n * (c0 + c1), (name, 'the engine sizes Builder.coefs for its widest layer')
         cin = c0 + c1
         src = dict(x1=x1, c1=c1, ld1=c1)
@@ -377,8 +398,8 @@ class Builder:
             self.free(a16)
             return
         kw = dict(kw, bias=bias, stats=True, w16=w16)
-        unfused_f16 = w16 is not None and self.f16_level(n, side, side, cin, 0, kw.get('ec0', 0), kw.get('ec1', 0)) == 1
-        if self.lib.ds_conv3x3_halo_supported(side, side) and not unfused_f16 and x0.dtype == torch.float32 and (x1 is None or x1.dtype == torch.float32):
+        unfused_f16 = w16 is not None and self.split_needs_pass(n, side, cin, kw.get('ec0', 0), kw.get('ec1', 0))
+        if self.halo_ok(n, side) and not unfused_f16 and x0.dtype == torch.float32 and (x1 is None or x1.dtype == torch.float32):
             gn_stats(gamma=gamma, beta=beta, coefs=self.coefs)
             self.conv(x0, c0, c0, n, side, side, wgt, cout, out, out_ld, 9, name, **src, norm_coefs=self.coefs, norm_act=DS_ACT_SILU, **kw)
         else:
@@ -419,14 +440,25 @@ class Builder:
         release_tuning_scratch()
         return P
 
-    def conv(self, x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, taps, name, x1=None, c1=0, ld1=0, bias=None, cbias=None,
-             cbias_ld=0, cbias_rows=1, res=None, res_ld=0, scale=1.0, act=DS_ACT_NONE, norm_coefs=None, norm_act=DS_ACT_NONE,
-             e0=None, ec0=0, e1=None, ec1=0, stride=1, stats=False, w16=None, out_nchw=0, in_f16=False, out_f16=False, emb=False,
-             in_up2=False, wino=False):
-        """stats=True: the epilogue also leaves the output's per-(64-row block, channel) sums for the consumer's GroupNorm
+    def conv(self, x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, taps, name, **kw):
+        """One ds_conv2d_nhwc launch: the struct of conv_args (`kw`: its keywords)."""
+        a = self.conv_args(x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, taps, name, **kw)
+        assert a.stride != 2 or not a.in_f16 or self.routes_to(a, 2571), name      # (stride 2 on fp16 rows: the caller asked stride2_ok())
+        self._autotune(a, (x0,) + tuple(kw.get(k) if a.in_f16 else None for k in ('e0', 'x1', 'e1', 'norm_coefs')))
+        self.add(self.lib.ds_conv2d_nhwc, (C.byref(a),), name, keep=(a,))
+
+    def conv_args(self, x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, taps, name, x1=None, c1=0, ld1=0, bias=None, cbias=None,
+                  cbias_ld=0, cbias_rows=1, res=None, res_ld=0, scale=1.0, act=DS_ACT_NONE, norm_coefs=None, norm_act=DS_ACT_NONE,
+                  e0=None, ec0=0, e1=None, ec1=0, stride=1, stats=False, w16=None, out_nchw=0, in_f16=False, out_f16=False, emb=False,
+                  in_up2=False, wino=False, probe=False):
+        """The ds_conv_args of a convolution: HOW a plan describes a layer to the library is known here alone; whether and how the library
+        takes it is asked of route() with this struct.  probe: the struct is only shown to route() (up2_ok, wino_ok, shape_args) -- nothing
+        plan-owned is allocated, no weight packed, no builder state touched; the split-K workspace is offered at a launch's capacity.
+        stats=True: the epilogue also leaves the output's per-(64-row block, channel) sums for the consumer's GroupNorm
         (honoured when cout % 64 == 0; otherwise the consumer falls back to a ds_gn_stats pass).
-        w16: fp16 weights of the same layer (ops.pack_conv_weight_f16); used -- with the fp16-operand kernel -- when the
-        geometry supports it (f16_level), else the fp32 weights `wgt` are.
+        w16: (fp16 weights of the same layer, shift) -- ops.pack_conv_weight_f16 for the fp16-activation kernels (in_f16); in split mode
+        ops.pack_conv_weight_split, used where the library takes this very launch with them, else the fp32 weights `wgt` are.  A 1x1 /
+        Linear layer finds its own (linear_w16).
         in_f16: x0 (and e0) are fp16 NHWC tensors (leading dimensions in halfs) written by ``norm(..., out_f16=True)``: the
         fp16-activation kernel (csrc/conv3x3_f16dma.hip); needs w16.
         emb: a projection of the embedding path (one row per image or one shared row): in the invariant mode the row kernel at every row
@@ -435,41 +467,36 @@ class Builder:
         ops.pack_conv_weight_up2 (ds_conv_args.in_up2; fp32 only -- the caller asked up2_ok()).
         wino: the Winograd form of the layer, `wgt` = ops.pack_conv_weight_wino (ds_conv_args.wino; exact fp32 only -- the caller asked
         wino_ok())."""
-        if wino:
-            assert w16 is None and not in_f16 and not in_up2 and stride == 1 and taps == 9 and not self.invariant, name
-        if in_up2:
-            assert w16 is None and not in_f16 and norm_coefs is None and not ec0 and res is None and stride == 1 and taps == 9, name
-        if taps == 1 and x0.dtype == torch.float16:
+        assert not wino or (w16 is None and not in_f16 and not in_up2 and stride == 1 and taps == 9 and not self.invariant), name
+        assert not in_up2 or (w16 is None and not in_f16 and norm_coefs is None and not ec0 and res is None and stride == 1 and taps == 9), name
+        lin16 = taps == 1 and x0.dtype == torch.float16
+        if lin16:
             # 1x1 / Linear on an fp16 tensor (LayerNorm / GroupNorm pass / attention / GEGLU output in fp16 mode): csrc/gemm_f16dma.hip
             assert x1 is None and not ec0 and norm_coefs is None and not out_nchw and stride == 1
-            wgt, ok = self.linear_w16(wgt, n * h * w, c0, 0, dma=True, cout=cout)
-            assert ok, (name, 'no fp16-activation GEMM for this shape')
-            w16, in_f16 = (wgt, 0), True
+            in_f16 = True
         elif in_f16:
             # stride 2 (the LDM Downsample on the fp16 stream): the gather form of the fp16-activation GEMM; no extras, no residual
             # (round 5) stride 1 with norm_coefs: RAW fp16 sources, the kernel normalises its LDS halo; second sources x1 / e1 allowed then
             assert w16 is not None and taps == 9 and stride in (1, 2) and not out_nchw
             assert norm_coefs is not None or (x1 is None and e1 is None), name
             assert norm_coefs is None or (stride == 1 and all(t is None or t.dtype == torch.float16 for t in (x0, x1, e0, e1))), name
-            assert stride == 1 or (not ec0 and res is None and self.lib.ds_conv_f16dma_stride2_supported(n, h, w, c0, cout)), name
-        f16 = in_f16 or w16 is not None and taps == 9 and stride == 1 and self.f16_level(n, h, w, c0, c1, ec0, ec1) >= (2 if norm_coefs is not None else 1)
-        shift = 0
-        if f16:
-            wgt, shift = w16
-        elif (self.conv_mode == 1 and taps == 1 and stride == 1 and norm_coefs is None and not ec0 and not ec1 and not out_nchw
-              and (not self.invariant or self._rows_per_image_ok(n * h * w))):
-            wgt, f16 = self.linear_w16(wgt, n * h * w, c0, c1)
-        a = ConvArgs(ptr(x0), ptr(x1), c0, c1, ld0, ld1, n, h, w, taps, ptr(wgt), cout, ptr(bias), ptr(cbias), cbias_ld,
+        if taps == 1 and w16 is None and (lin16 or (self.conv_mode == 1 and stride == 1 and norm_coefs is None and not ec0 and not ec1
+                                                    and not out_nchw and (not self.invariant or self._rows_per_image_ok(n * h * w)))):
+            w16 = self.linear_w16(wgt, n * h * w, c0, c1, dma=lin16, cout=cout)
+            assert w16 is not None or not lin16, (name, 'no fp16-activation GEMM for this shape')
+        f16 = w16 is not None and (in_f16 or taps == 1)
+        # split mode: the split-fp16 weights where the library takes the finished struct with them (asked at the end); invariant: never at 8x8,
+        # whose 256-pixel tiles hold four images, i.e. take only batches that are multiples of four
+        split = w16 is not None and not f16 and self.conv_mode == 2 and taps == 9 and stride == 1 and not (self.invariant and (h * w) % 256)
+        a = ConvArgs(ptr(x0), ptr(x1), c0, c1, ld0, ld1, n, h, w, taps, ptr(w16[0] if f16 or split else wgt), cout, ptr(bias), ptr(cbias), cbias_ld,
                      cbias_rows, ptr(res), res_ld, scale, act, ptr(out), out_ld, ptr(norm_coefs), norm_act, ptr(e0), ptr(e1),
                      ec0, ec1, ec0, ec1, stride)
-        if self.ws is None:
+        if self.ws is None and not probe:
             self.ws = self.new(SPLITK_WORKSPACE_FLOATS)
-        a.workspace, a.workspace_floats = ptr(self.ws), self.ws.numel()
+        a.workspace, a.workspace_floats = ptr(F32 if self.ws is None else self.ws), SPLITK_WORKSPACE_FLOATS
         a.out_nchw = out_nchw               # network output written channel-planar (NCHW) by the epilogue
-        a.wgt_f16, a.wgt_shift = (self.conv_mode, shift) if f16 else (0, 0)
-        a.in_f16 = 1 if in_f16 else 0
-        a.in_up2 = 1 if in_up2 else 0
-        a.wino = 1 if wino else 0
+        a.wgt_f16, a.wgt_shift = (self.conv_mode, w16[1]) if f16 or split else (0, 0)
+        a.in_f16, a.in_up2, a.wino = int(bool(in_f16)), int(bool(in_up2)), int(bool(wino))
         if self.invariant:
             a.tune.invariant = 3 if emb else 1
         if out_f16 or out.dtype == torch.float16:          # fp16 output rows: conv0 outputs, projection operands, the fp16 residual stream
@@ -478,44 +505,50 @@ class Builder:
         if res is not None and res.dtype == torch.float16:  # the residual operand is a tensor of the fp16 stream
             assert in_f16, name
             a.res_f16 = 1
-        self.stats_of.pop(out.data_ptr(), None)
+        if not probe:
+            self.stats_of.pop(out.data_ptr(), None)
         if stats and cout % 64 == 0 and out_ld == cout:
-            sb = self.new(-(-(n * h * w) // 64) * 2 * cout)
-            a.stats_out = ptr(sb)
-            self.stats_of[out.data_ptr()] = (sb, cout)
-        self._autotune(a, (x0, e0 if in_f16 else None, x1 if in_f16 else None, e1 if in_f16 else None, norm_coefs if in_f16 else None))
-        self.add(self.lib.ds_conv2d_nhwc, (C.byref(a),), name, keep=(a,))
+            sums = out if probe else self.new(-(-(n * h * w) // 64) * 2 * cout)       # (a probe: any 16-byte-aligned address)
+            a.stats_out = ptr(sums)
+            if not probe:
+                self.stats_of[out.data_ptr()] = (sums, cout)
+        if split and not self.routes_to(a, 2563):
+            a.wgt, a.wgt_f16, a.wgt_shift = ptr(wgt), 0, 0
+        return a
 
-    def up2_ok(self, x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, bias=None, cbias=None, cbias_ld=0, cbias_rows=1, stats=False, **_):
-        """Does the library take this layer as an upsampled-input convolution (ds_conv_args.in_up2)?  Asked of ds_conv_route (host logic
-        only) with the arguments conv(..., in_up2=True) would pass.  On the batch-invariant route the answer depends on the layer alone (the
-        256 x 192 tiles, the one shape whose use follows the tile count, are off there)."""
-        a = ConvArgs(ptr(x0), None, c0, 0, ld0, 0, n, h, w, 9, ptr(wgt), cout, ptr(bias), ptr(cbias), cbias_ld, cbias_rows, None, 0,
-                     1.0, DS_ACT_NONE, ptr(out), out_ld)
-        a.in_up2 = 1
-        if stats and cout % 64 == 0 and out_ld == cout:
-            a.stats_out = ptr(out)              # (any 16-byte-aligned address: the probe launches nothing)
-        if self.invariant:
-            a.tune.invariant = 1
+    def route(self, a):
+        """The library's answer to a ds_conv_args: (return code, ConvRouteInfo) of ds_conv_route -- host logic only, nothing is launched.
+        Every question this builder or an engine has about a convolution is put here."""
         info = ConvRouteInfo()
-        return self.lib.ds_conv_route(C.byref(a), C.byref(info)) == 0
+        return self.lib.ds_conv_route(C.byref(a), C.byref(info)), info
 
-    def wino_ok(self, x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, x1=None, c1=0, ld1=0, bias=None, cbias=None, cbias_ld=0, cbias_rows=1,
-                res=None, res_ld=0, scale=1.0, act=DS_ACT_NONE, norm_coefs=None, norm_act=DS_ACT_NONE, e0=None, ec0=0, e1=None, ec1=0, stats=False, **_):
-        """Does the library take this layer in the Winograd form (ds_conv_args.wino)?  Asked of ds_conv_route (host logic only) with the
-        arguments conv(..., wino=True) would pass: yes exactly where the direct form would run on the 256 x 256 tiles without split-K."""
+    def routes_to(self, a, *kernel_ids):
+        rc, info = self.route(a)
+        return rc == 0 and info.kernel_id in kernel_ids
+
+    def shape_args(self, n, side, c0, cout, taps=9, in_f16=False, w16=False, c1=0, ec0=0, ec1=0, **kw):
+        """conv_args, in probe form, of a layer known by its shape alone -- the block-level decisions, taken before buffers exist: `n` images
+        of side x side pixels (a Linear layer: n rows, side 1), dense rows, an fp16 packing if in_f16 or w16, and no bias, residual,
+        statistics or norm_coefs unless `kw` names one."""
+        t = F16 if in_f16 else F32
+        return self.conv_args(t, c0, c0, n, side, side, F32, cout, F32, cout, taps, 'shape', x1=t if c1 else None, c1=c1, ld1=c1,
+                              e0=t if ec0 else None, ec0=ec0, e1=t if ec1 else None, ec1=ec1, w16=(F32, 0) if in_f16 or w16 else None,
+                              in_f16=in_f16, probe=True, **kw)
+
+    def up2_ok(self, x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, **kw):
+        """Does the library take this layer as an upsampled-input convolution (ds_conv_args.in_up2)?  The route of the struct
+        conv(..., in_up2=True, **kw) would launch.  On the batch-invariant route the answer depends on the layer alone (the 256 x 192
+        tiles, the one shape whose use follows the tile count, are off there)."""
+        return self.route(self.conv_args(x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, 9, 'up2_ok', in_up2=True, probe=True, **kw))[0] == 0
+
+    def wino_ok(self, x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, **kw):
+        """Does the library take this layer in the Winograd form (ds_conv_args.wino)?  The route of the struct conv(..., wino=True, **kw)
+        would launch, split-K workspace included (the split-K decision is part of the answer): yes exactly where the direct form would
+        run on the 256 x 256 tiles without split-K."""
         if self.invariant or self.conv_mode:
             return False
-        a = ConvArgs(ptr(x0), ptr(x1), c0, c1, ld0, ld1, n, h, w, 9, ptr(wgt), cout, ptr(bias), ptr(cbias), cbias_ld, cbias_rows, ptr(res), res_ld,
-                     scale, act, ptr(out), out_ld, ptr(norm_coefs), norm_act, ptr(e0), ptr(e1), ec0, ec1, ec0, ec1)
-        a.wino = 1
-        if self.ws is None:
-            self.ws = self.new(SPLITK_WORKSPACE_FLOATS)
-        a.workspace, a.workspace_floats = ptr(self.ws), self.ws.numel()      # as conv() offers it: the split-K decision is part of the answer
-        if stats and cout % 64 == 0 and out_ld == cout:
-            a.stats_out = ptr(out)              # (any 16-byte-aligned address: the probe launches nothing)
-        info = ConvRouteInfo()
-        return self.lib.ds_conv_route(C.byref(a), C.byref(info)) == 0 and info.wino == 1
+        rc, info = self.route(self.conv_args(x0, c0, ld0, n, h, w, wgt, cout, out, out_ld, 9, 'wino_ok', wino=True, probe=True, **kw))
+        return rc == 0 and info.wino == 1
 
     @staticmethod
     def _tune_key(a, stride):
@@ -596,30 +629,21 @@ class Builder:
         return best[0], best[1], times
 
     def linear_w16(self, wgt, rows, c0, c1, dma=False, cout=0):
-        """(weights, use the fp16-operand GEMM?) of a 1x1 / Linear layer in fp16 mode: the fp16 packing of `wgt` (cached per weight
-        tensor) where gemm_f16_kernel covers the shape, else the fp32 weights unchanged."""
-        ok = self.lib.ds_gemm_f16dma_supported(rows, c0, cout) if dma else self.lib.ds_gemm_f16_supported(rows, c0, c1)
+        """w16 of a 1x1 / Linear layer in fp16 mode: (the fp16 packing of `wgt`, cached per weight tensor; shift 0) where the library takes the
+        shape with it -- dma: on fp16 rows (gemm16_ok), else on fp32 rows, rounded while staged (gemm_f16_kernel, kernel id 2564) -- else None."""
+        ok = self.gemm16_ok(rows, c0, cout) if dma else self.routes_to(self.shape_args(rows, 1, c0, 128, taps=1, w16=True, c1=c1), 2564)
         if wgt.dtype != torch.float32 or wgt.dim() != 2 or wgt.shape[0] % 128 or wgt.shape[1] != c0 + c1 or not ok:
-            return wgt, False
+            return None
         key = wgt.data_ptr()
         if key not in self.w16_cache:
             from .ops import pack_linear_weight_f16
             self.w16_cache[key] = (pack_linear_weight_f16(wgt), wgt)       # keep the source alive: its address is the key
-        return self.w16_cache[key][0], True
+        return self.w16_cache[key][0], 0
 
     def _rows_per_image_ok(self, rows):
         """Invariant mode: may a 1x1 / Linear layer over `rows` rows take the fp16-operand GEMM (whole 256-row tiles)?  Only where every
         batch gives it whole tiles -- a multiple of 256 rows per image -- so the choice never depends on the batch."""
         return bool(self.batch) and rows % self.batch == 0 and (rows // self.batch) % 256 == 0
-
-    def f16_level(self, n, h, w, c0, c1, ec0, ec1):
-        """0 = no fp16-operand kernel for this 3x3 layer, 1 = on raw input only, 2 = also with the fused input normalisation."""
-        if self.conv_mode == 0 or any(c % (64 if self.conv_mode == 1 else 32) for c in (c0, c1, ec0, ec1)):
-            return 0
-        if self.invariant and (h * w) % 256:
-            return 0            # 8x8: the reduced-operand kernels take whole 256-pixel tiles, i.e. only batches that are multiples of four
-        fn = self.lib.ds_conv_f16_supported if self.conv_mode == 1 else self.lib.ds_conv_split_supported
-        return int(fn(n, h, w, c0, c1, ec0, ec1))
 
     def linear(self, x, k, rows, wgt, cout, out, name, ldx=None, out_ld=None, **kw):
         """out[rows, cout] = x[rows, k] W^T (+bias +res ...): a 1x1 'convolution' over rows."""

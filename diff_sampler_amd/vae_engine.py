@@ -149,7 +149,7 @@ class VAEDecoder:
                           eps=EPS, w16=w.get(f'{p}.c1.w16') if f16 else None, f16=f16)
             short = x
             if cin != cout:         # nin_shortcut (model.py:135-139): a 1x1 convolution of the raw input, added by conv2's epilogue
-                s16 = f16 and x.dtype == torch.float16 and bool(lib.ds_gemm_f16dma_supported(M, cin, cout))
+                s16 = f16 and x.dtype == torch.float16 and bd.gemm16_ok(M, cin, cout)
                 if f16 and x.dtype == torch.float16 and not s16:
                     raise NotImplementedError(f'{p}.nin_shortcut: no fp16-activation GEMM for {M} x {cin} -> {cout}')
                 short = bd.alloc(M, cout, f16=s16)
@@ -168,7 +168,7 @@ class VAEDecoder:
             if not lib.ds_attention_supported(c):
                 raise NotImplementedError(f'attention head size {c} has no kernel instantiation')
             x = fp32_rows(x, c, side, p + '.x')
-            h16 = bool(self.use_fp16 and lib.ds_gemm_f16dma_supported(M, c, 3 * c))
+            h16 = bd.gemm16_ok(M, c, 3 * c)
             n = bd.alloc(M, c, f16=h16)
             bd.norm('stats', x, c, c, N, side, side, p + '.norm.stats', groups=32, eps=EPS)
             bd.norm('apply', x, c, c, N, side, side, p + '.norm', groups=32, eps=EPS, gamma=w[f'{p}.n.g'], beta=w[f'{p}.n.b'], out=n, out_ld=c,

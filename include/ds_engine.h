@@ -262,7 +262,10 @@ typedef struct ds_conv_route_info {
 } ds_conv_route_info;
 DS_API int ds_conv_route(const ds_conv_args* a, ds_conv_route_info* info);
 
-/* 1 if a 3x3 convolution on h x w images runs on the LDS-halo kernel (needed for norm_coefs), else 0. */
+/* The six geometry-only predicates below are ROUTE QUERIES: each describes its shape as the ds_conv_args of a launch of that shape alone
+ * (dense rows, no bias / residual / statistics / workspace) and answers from ds_conv_route's own routing function, by return code and kernel
+ * id -- there is no second copy of a kernel family's rule.  A caller that knows more than the shape asks ds_conv_route with its own struct.
+ * 1 if a 3x3 convolution on h x w images runs on the LDS-halo kernel (needed for norm_coefs), else 0. */
 DS_API int ds_conv3x3_halo_supported(int h, int w);
 
 /* fp16-operand 3x3 convolution (ds_conv_args.wgt_f16): returns 0 = not available for this geometry, 1 = available, 2 = available
@@ -283,7 +286,8 @@ DS_API int ds_conv_f16dma_stride2_supported(int n, int h, int w, int c0, int cou
  * input rows are rounded to fp16 while they are staged): 1 if rows % 256 == 0 and every source is a multiple of 64 channels. */
 DS_API int ds_gemm_f16_supported(long long rows, int c0, int c1);
 
-/* The same for the split-fp16 (fp32-emulated) operands of wgt_f16 == 2; every source a multiple of 32 channels. */
+/* 3x3 convolution on the split-fp16 (fp32-emulated) operands of wgt_f16 == 2, every source a multiple of 32 channels: the number of forms
+ * taken -- 0 = none, 1 = on raw input, 2 = also with the fused input normalisation (norm_coefs).  ec1 without ec0 is no launch: 0. */
 DS_API int ds_conv_split_supported(int n, int h, int w, int c0, int c1, int ec0, int ec1);
 
 /* Batched per-seed latent generator: out[b][i], i < n, = the tensor `torch.randn([n], generator=g_b, device=<this GPU>)` of a generator

@@ -300,3 +300,39 @@ def test_fuse_norm16_auto_fuses_exactly_the_measured_layer_class():
     lspec = la.ldm_unet_spec(**dict(la.NAMED_LDM_CONFIGS['sd15']))
     leng = LDMUNetEngine(lspec, la.init_ldm_params(lspec, seed=0), device='cpu', use_fp16=True)
     assert leng.fuse_norm16 == 'auto' and fused(leng.plan(32, 1, 77)) == []          # SD-1.5 has no layer of that class (its 64x64 layers have 320 channels)
+
+
+def test_geometry_predicates_equal_the_builders_shape_probes():
+    """The six geometry-only exports and the Builder's shape probes describe a shape to ds_conv_route on their own side (csrc/gemm_conv.hip
+    shape_args / plan.Builder.shape_args): over a grid of shapes -- odd batches, sides with and without a kernel, channel counts that are
+    and are not whole slabs, a second source, appended 1x1 columns, ragged row counts -- every export equals the probe of the same shape,
+    and ds_conv_split_supported counts the forms (raw input, fused normalisation) the two split probes accept.  Appended columns in the
+    second source without any in the first are no launch (DS_E_SHAPE from ds_conv_route), so the count there is 0."""
+    import itertools
+    from diff_sampler_amd.plan import Builder, F32, DS_ACT_SILU
+    lib = _lib.load()
+    DS_E_SHAPE = -3                                           # include/ds_engine.h
+    b16, b2 = Builder('cpu', conv_mode=1), Builder('cpu', conv_mode=2)
+    NS, SIDES, CH, C1, COUT, ROWS = (1, 3, 4, 64), (4, 8, 16, 24, 64, 128), (32, 64, 96), (0, 32, 64), (64, 96, 320), (1, 77, 256, 4096)
+    for n, s, c0, ec0, cout in itertools.product(NS, SIDES, CH, C1, COUT):
+        assert lib.ds_conv_f16dma_supported(n, s, s, c0, ec0, cout) == b16.f16_conv_ok(n, s, c0, ec0, cout), (n, s, c0, ec0, cout)
+    for n, s, c0, cout in itertools.product(NS, SIDES, CH, COUT):
+        assert lib.ds_conv_f16dma_stride2_supported(n, s, s, c0, cout) == b16.stride2_ok(n, s, c0, cout), (n, s, c0, cout)
+    for rows, k, cout in itertools.product(ROWS, CH, COUT):
+        assert lib.ds_gemm_f16dma_supported(rows, k, cout) == b16.gemm16_ok(rows, k, cout), (rows, k, cout)
+    for rows, c0, c1 in itertools.product(ROWS, CH, C1):
+        assert lib.ds_gemm_f16_supported(rows, c0, c1) == b16.routes_to(b16.shape_args(rows, 1, c0, 128, taps=1, w16=True, c1=c1), 2564), (rows, c0, c1)
+    for n, s in itertools.product(NS, SIDES + (2, 12, 48)):
+        assert lib.ds_conv3x3_halo_supported(s, s) == b16.halo_ok(n, s) == b2.halo_ok(n, s), (n, s)
+    some_yes = set()
+    for n, s, c0, c1, ec0, ec1 in itertools.product(NS, SIDES, (32, 96), (0, 32), C1, (0, 32)):
+        takes = lambda **kw: b2.routes_to(b2.shape_args(n, s, c0, 128, w16=True, c1=c1, ec0=ec0, ec1=ec1, **kw), 2563)
+        forms = takes() + takes(norm_coefs=F32, norm_act=DS_ACT_SILU)
+        assert lib.ds_conv_split_supported(n, s, s, c0, c1, ec0, ec1) == forms, (n, s, c0, c1, ec0, ec1)
+        assert b2.split_needs_pass(n, s, c0 + c1, ec0, ec1) == (lib.ds_conv_split_supported(n, s, s, c0 + c1, 0, ec0, ec1) == 1)
+        if ec1 and not ec0:
+            a = b2.shape_args(n, s, c0, 128, w16=True, c1=c1, ec1=ec1)
+            a.wgt_f16 = 2
+            assert forms == 0 and b2.route(a)[0] == DS_E_SHAPE, (n, s, c0, c1, ec1)
+        some_yes.add(forms)
+    assert some_yes == {0, 1, 2}                               # 8x8 images: raw input only

@@ -130,7 +130,10 @@ def dump(engine, P):
         if fn == 'ds_conv2d_nhwc':
             r = _lib.ConvRouteInfo()
             rc = lib.ds_conv_route(C.byref(st), C.byref(r))
-            row.append(['route', [rc, r.kernel_id, r.splits, list(r.f16_widths[:r.f16_groups])]])
+            # ds_conv_args.wino is a property on the struct's tail padding, not in _fields_: recorded here, with the route's own wino word,
+            # where either is set -- a launch that changes form changes its row, rows of the direct form keep the hashes tests have recorded
+            wino = [['wino', repr(st.wino)]] if st.wino else []
+            row += wino + [['route', [rc, r.kernel_id, r.splits, list(r.f16_widths[:r.f16_groups])] + ([r.wino] if r.wino else [])]]
         dead = {}                           # words no kernel reads: kept out of the row's hash, compared on their own
         if fn == 'ds_attention':            # the library's answer decides (it is 2 for d >= 512 whatever the raw word says)
             row.append(['library_variant', lib.ds_attention_variant(C.byref(st))])
