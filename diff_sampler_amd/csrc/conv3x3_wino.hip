@@ -43,8 +43,8 @@
 // coefficient planes {mu, A, B} of the tile's image, three more loads per slab) and SiLU (ds_silu's operations), once per element, then
 // one ds_write_b128.  What is uniform per launch (normalisation none / affine / affine + SiLU; the active slots) is a template parameter.
 // Out-of-image cells: which halo cells lie outside the image is fixed for the tile (its left and right columns; its top or bottom row
-// where the tile touches the image's), so their zeros are written ONCE, into both Hs buffers, where the thread's slots are set up in
-// front of the prologue -- by the thread that owns the slot, which never stores there again: a slot that holds no in-image pixel -- an
+// where the tile touches the image's), so their zeros are written ONCE, into both Hs buffers, where the thread's LDS cells are set up
+// (WinoHalo::cells, in front of the thread's first halo store) -- by the thread that owns the slot, which never stores there again: a slot that holds no in-image pixel -- an
 // out-of-image pixel, loaded from the nearest pixel of the same image, or a slot beyond the halo -- stores into the spare cell behind
 // its Hs buffer.  The prologue's first barrier publishes the zeros with halo 0 and 1, and the LDS may hold whatever the workgroup before
 // left.  The halo store used to select `in-image ? v : 0` per element, 12 v_cndmask per slab and thread on top of the MFMAs
@@ -161,6 +161,18 @@
 //               asks for.  The association of every sum is the lane-local output transform's.
 //   skip loop = each wave on the two pixel accumulators of its patch row: 32 MFMAs per slab; two float4 per thread.
 //   epilogue  = each wave writes its one patch row; its staging rows lie in the cells the wave itself read in the exchange.
+//   OUTSIDE THE LOOPS a workgroup holds the whole compute unit and nothing overlaps it (profiles/wino_outside_ab.txt, wino_outside_isa.txt):
+//     prologue  = first what the first loads need (tile decode, the slot's offsets, the bases: WinoHalo's constructor; the weight run), then the
+//                 requests of halo 0 and 1 and of the B fragments of (slab 0, group 0), and under their latency the rest: the slot's LDS cell and
+//                 zero cells (WinoHalo::cells), the transform's and the fragments' indices.  Divisions by W and W / 2 are shifts, hp / WP is a
+//                 multiplication by wino_wp_rcp(W).
+//     slab 0    = peeled: K step 0 of each position takes the constant 0 as C, no accumulator is zeroed.  The loop is back(s) (MFMA block,
+//                 barrier), exit test, front(s + 1) (transform, halo store).
+//     the tail's requests = behind the K loop's last barrier, in front of the exchange's writes: the skip loop's weights of slab 0 and pixels of
+//                 slabs 0 and 1, colbias, the cbias row, the eight residual quads.  The exchange reads its partner one accumulator ahead, so
+//                 that they fit beside the 128 accumulators.
+//     branches  = on the wave's half, p.cbias, p.res, p.act as SCALARS (w8_uni), no selects; half 1's differences packed (w8_sub).
+//     addresses = epilogue and residual: a 64-bit scalar base per (pass, patch pixel) plus one 32-bit lane offset per tensor.
 #include <type_traits>
 
 #include "igemm_common.h"
@@ -201,6 +213,15 @@ constexpr int WINO_EPI_LD = 36;                   // epilogue staging row: 32 + 
 // compiler picks another slot's load for the one offset select it vectorises, and the K loop's instruction order moves.
 // conv3x3_wino_kernel keeps a copy of this stage in its body: on this struct its K loop came out with that select on another slot at
 // NORM != 0, whichever way the struct was cut (profiles/wino_shared_isa.txt); a fix to this stage has to be made there too.
+// r = 65536 / WP + 1 for WP = W + 2 at the widths of this route (powers of two, 4 .. 64: conv3x3_wino_applicable): (hp * r) >> 16 == hp / WP
+// for every halo pixel hp < 1024.  10923 at W = 4; 6554, 3641, 1928, 993 at W = 8 .. 64 are the 16-bit fields of one constant, taken
+// with a scalar shift (a chain of selects compiled to 40 scalar instructions in front of the first load).  As a field of KParams,
+// set by the launcher, it would change igemm_common.h, whose text is hashed into the measured fp16 tile table.
+__device__ __forceinline__ int wino_wp_rcp(int W) {
+    const int lw = __builtin_ctz(W);
+    return lw == 2 ? 10923 : (int)((0x03E107880E39199Aull >> ((16 * (lw - 3)) & 63)) & 0xFFFF);
+}
+
 template <int NT, int NSH, int NSL, int NORM>
 struct WinoHalo {
     // a slab's halo on its way: the raw pixels of this thread's slots and the slab's coefficient planes {mu, A, B}
@@ -220,24 +241,40 @@ struct WinoHalo {
     const float* h_src = nullptr;
     unsigned h_sel = 0;
 
-    // The slots, fixed for the whole K loop: element offsets inside the tile's image for either source (an out-of-image pixel: the nearest
-    // pixel of the image) and the LDS cell.  An out-of-image pixel's cell holds zeros in BOTH Hs buffers for the whole tile: this thread
-    // writes them here, once, in front of every halo store (the LDS is whatever the workgroup before left), and sends the slot's stores
-    // to the spare cell, as it does for a slot beyond the halo.  No other thread writes those cells; the prologue's first barrier
-    // publishes them with halo 0 and 1.
-    __device__ __forceinline__ WinoHalo(const KParams& p, float* Hs, int tid, int img0, int r0)
+    // The slots, fixed for the whole K loop, in two steps so that a kernel can request its first halos between them.  The constructor
+    // makes what the LOADS need: element offsets inside the tile's image for either source (an out-of-image pixel: the nearest pixel of
+    // the image) and the image's bases.  The halo row of a pixel is hp / WP as a multiplication by wino_wp_rcp(W) (exact for every
+    // halo pixel hp < 1024), the image row of the tile comes as r0.
+    __device__ __forceinline__ WinoHalo(const KParams& p, int tid, int img0, int r0)
         : c0(p.c0), Ctot(p.c0 + p.c1), buf(p.NP * WINO_K + 4) {
-        const int kh_h = tid & 1, WPH = p.WP >> 1;
+        const int kh_h = tid & 1, wp_rcp = wino_wp_rcp(p.W);
 #pragma unroll
         for (int j = 0; j < NSH; ++j) {
             const int hp = (tid + j * NT) >> 1;
-            const int hr = hp / p.WP, hc = hp - hr * p.WP;
+            const int hr = (hp * wp_rcp) >> 16, hc = hp - hr * p.WP;
             const int y = r0 + hr - 1, x = hc - 1;
-            const bool in = hp < p.NP;
-            const bool ok = in && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
             const int pix = min(max(y, 0), p.H - 1) * p.W + min(max(x, 0), p.W - 1);
             off0[j] = (unsigned)(pix * p.lda0 + kh_h * 4) * 4u;         // BYTES: a load's address is the scalar base plus this 32-bit offset,
             off1[j] = (unsigned)(pix * p.lda1 + kh_h * 4) * 4u;         // with no 64-bit vector arithmetic between the MFMAs
+        }
+        a0i = p.a0 + (size_t)img0 * p.HW * p.lda0;
+        a1i = p.a1 + (size_t)img0 * p.HW * p.lda1;
+        cpi = p.norm + (size_t)img0 * 3 * Ctot;
+        c_lane = (unsigned)(kh_h * 16);
+    }
+    // ... and cells() what the STORES need, in front of the first of them: the LDS cell of every slot.  An out-of-image pixel's cell
+    // holds zeros in BOTH Hs buffers for the whole tile: this thread writes them here, once, in front of every halo store (the LDS is
+    // whatever the workgroup before left), and sends the slot's stores to the spare cell, as it does for a slot beyond the halo.  No
+    // other thread writes those cells; the prologue's first barrier publishes them with halo 0 and 1.
+    __device__ __forceinline__ void cells(const KParams& p, float* Hs, int tid, int r0) {
+        const int kh_h = tid & 1, WPH = p.WP >> 1, wp_rcp = wino_wp_rcp(p.W);
+#pragma unroll
+        for (int j = 0; j < NSH; ++j) {
+            const int hp = (tid + j * NT) >> 1;
+            const int hr = (hp * wp_rcp) >> 16, hc = hp - hr * p.WP;
+            const int y = r0 + hr - 1, x = hc - 1;
+            const bool in = hp < p.NP;
+            const bool ok = in && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
             const int cell = (((kh_h * 2 + (hc & 1)) * p.HP + hr) * WPH + (hc >> 1)) * 4;
             lds[j] = ok ? cell : p.NP * WINO_K;
             if (in && !ok) {
@@ -246,10 +283,6 @@ struct WinoHalo {
                 *reinterpret_cast<f32x4*>(Hs + buf + cell) = z;
             }
         }
-        a0i = p.a0 + (size_t)img0 * p.HW * p.lda0;
-        a1i = p.a1 + (size_t)img0 * p.HW * p.lda1;
-        cpi = p.norm + (size_t)img0 * 3 * Ctot;
-        c_lane = (unsigned)(kh_h * 16);
     }
     // the source a0 | a1 of slab s, for the loads that follow
     __device__ __forceinline__ void src(int s) {
@@ -320,25 +353,38 @@ struct WinoSkip {
     static constexpr int STEP = NT / 8, NE = 4 * ROWS / STEP;
     int lds[NE];                                   // V cell of slot j: [patch pixel][8-channel group][kh][tile ^ chunk][4]
     int a_off[4];                                  // fragment offset of group g in a patch pixel's block, swizzled: row ^ (2 g + kh)
-    unsigned t0, t1;                               // element offset of slot 0 in e0 | e1; a slot steps STEP rows
+    unsigned t_pix, t_e4;                          // pixel of slot 0 and the thread's channel chunk: slot 0 is element t_pix * ld + t_e4 of e0 | e1; a slot steps STEP rows
     const float* src = nullptr;
     unsigned off = 0;
     int step = 0;
 
     // row0: the first of the 32 tiles whose fragments this wave reads
-    __device__ __forceinline__ WinoSkip(const KParams& p, int tid, int lane, int row0) {
-        const int e_chunk = tid & 7, Wt = p.W >> 1;    // channels 4 e_chunk .. + 3 of the slab: group e_chunk >> 1, kh = e_chunk & 1
+    __device__ __forceinline__ WinoSkip(const KParams& p, int tid, int lane, int row0) { setup(p, tid, lane, row0); }
+    // for a kernel that sets its slots up only where the launch has skip slabs
+    __device__ __forceinline__ WinoSkip() {}
+    __device__ __forceinline__ void setup(const KParams& p, int tid, int lane, int row0) {
+        setup_loads(p, tid);
+        setup_cells(p, tid, lane, row0);
+    }
+    // what the loads need ...
+    __device__ __forceinline__ void setup_loads(const KParams& p, int tid) {
+        const int e_chunk = tid & 7;                   // channels 4 e_chunk .. + 3 of the slab: group e_chunk >> 1, kh = e_chunk & 1
+        t_pix = (unsigned)(tid >> 3);
+        t_e4 = (unsigned)(e_chunk * 4);
+    }
+    // ... and what the stores and the fragment reads need
+    __device__ __forceinline__ void setup_cells(const KParams& p, int tid, int lane, int row0) {
+        const int e_chunk = tid & 7, Wt = p.W >> 1;
+        const int lw = __builtin_ctz(p.W);             // every width on this route is a power of two (conv3x3_wino_applicable)
 #pragma unroll
         for (int j = 0; j < NE; ++j) {
             const int lp = (tid >> 3) + STEP * j;      // pixel of the tile
-            const int yl = lp / p.W, x = lp - yl * p.W;
+            const int yl = lp >> lw, x = lp & (p.W - 1);
             const int ph = (yl & 1) * 2 + (x & 1), t = (yl >> 1) * Wt + (x >> 1);
             lds[j] = (((ph * 4 + (e_chunk >> 1)) * 2 + (e_chunk & 1)) * ROWS + (t ^ e_chunk)) * 4;
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) a_off[g] = ((lane >> 5) * ROWS + ((row0 + (lane & 31)) ^ (2 * g + (lane >> 5)))) * 4;
-        t0 = (unsigned)((tid >> 3) * p.elda0 + e_chunk * 4);
-        t1 = (unsigned)((tid >> 3) * p.elda1 + e_chunk * 4);
     }
     // the source e0 | e1 of slab es of the tile at output row m0, for the loads that follow
     __device__ __forceinline__ void sel(const KParams& p, int es, int m0) {
@@ -347,7 +393,7 @@ struct WinoSkip {
         const int ld = first ? p.elda0 : p.elda1;
         src = (first ? p.e0 + c : p.e1 + (c - p.ec0)) + (size_t)m0 * ld;
         step = STEP * ld;
-        off = first ? t0 : t1;
+        off = __umul24(t_pix, (unsigned)ld) + t_e4;    // one v_mad_u32_u24 on the scalar row step (a row step is far below 2^24 floats)
     }
     template <int J>
     __device__ __forceinline__ void load1(f32x4* dst, std::integral_constant<int, J>) {
@@ -832,7 +878,8 @@ __global__ void __launch_bounds__(256, 1) wino_n128_kernel(const KParams p) {
 
     // ---- halo stage: NSL of three float4 slots per thread -----------------------------------------------------------------------------------
     using Halo = WinoHalo<256, WN_NSH, NSL, NORM>;
-    Halo halo(p, Hs, tid, img0, r0);
+    Halo halo(p, tid, img0, r0);
+    halo.cells(p, Hs, tid, r0);
     const int h_buf = halo.buf;
     typename Halo::Regs hreg;
     auto halo_load1 = [&](typename Halo::Regs& R, auto J) { halo.load1(R, J); };
@@ -1153,6 +1200,30 @@ int launch_wino_n128(KParams& p, hipStream_t stream) {
 constexpr int W8_NSH = 1;                         // halo float4 slots per thread: NP * 2 <= 512, i.e. 16- and 32-column images (NP = 180, 204)
 constexpr int W8_XCH = 4 * 16 * 64;               // floats a wave passes to its partner: four accumulators x 16 registers x 64 lanes (16 KiB)
 
+// a - b on register pairs, as v_pk_add_f32 with the negate bits -- what the compiler makes of a two-float subtraction in the input
+// transform.  A sixteen-float one it leaves as sixteen v_sub_f32, and pairs cut out of it in the source are widened again or cost a
+// register copy per operand; the same IEEE subtraction on the same operands either way.
+__device__ __forceinline__ f32x16 w8_sub(const f32x16& a, const f32x16& b) {
+    f32x16 d;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const f32x2 x = {a[2 * i], a[2 * i + 1]}, y = {b[2 * i], b[2 * i + 1]};
+        f32x2 z;
+        asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(z) : "v"(x), "v"(y));
+        d[2 * i] = z[0]; d[2 * i + 1] = z[1];
+    }
+    return d;
+}
+
+// A wave-uniform value (a kernel argument, the wave's half) as a fresh scalar at each use: the branch on it is then s_cmp + s_cbranch_scc.
+// One flag shared by several branches is kept as a lane mask, inverted with v_cndmask + v_cmp where a branch wants its complement, or
+// turned into selects.
+template <typename T>
+__device__ __forceinline__ T w8_uni(T x) {
+    asm volatile("" : "+s"(x));
+    return x;
+}
+
 // NORM: WinoHalo's
 template <int NORM>
 __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
@@ -1166,26 +1237,60 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
     int mt, nt;
     if (!decode_tile(blockIdx.x, p.mtiles, p.ntiles, mt, nt)) return;
     const int m0 = mt * 128, n0 = nt * 128;
+    const int lw = __builtin_ctz(p.W);             // W = 16 | 32 on this kernel: divisions by W and by W / 2 are shifts
     const int img0 = m0 / p.HW;
-    const int r0 = (m0 - img0 * p.HW) / p.W;
-    const int WPH = p.WP >> 1, Wt = p.W >> 1;
+    const int r0 = (m0 - img0 * p.HW) >> lw;
     const int Ctot = p.c0 + p.c1;
     const int nslabs = Ctot / WINO_K;
 
-    // ---- halo stage: one float4 slot per thread over 512 threads -------------------------------------------------------------------------
+    // ---- FIRST what the first loads need, and the loads: the slot's offsets and the image's bases (WinoHalo's constructor), the weight
+    // run.  Halo 0 and 1 and the B fragments of (slab 0, group 0) are on their way while the rest of the set-up runs.
+    // halo stage: one float4 slot per thread over 512 threads
     using Halo = WinoHalo<512, W8_NSH, W8_NSH, NORM>;
-    Halo halo(p, Hs, tid, img0, r0);
+    Halo halo(p, tid, img0, r0);
     const int h_buf = halo.buf;
-    typename Halo::Regs hreg;
+    typename Halo::Regs hreg, hreg1;
     auto halo_load1 = [&](typename Halo::Regs& R, auto J) { halo.load1(R, J); };
     auto coef_load1 = [&](typename Halo::Regs& R, int sl, auto I) { halo.coef1(R, sl, I); };
+
+    // transformed weights: global -> the B fragment registers, as in wino_n128_kernel: the 32 columns of channel group cg are rows
+    // 32 (cg & 1) .. + 31 of the 64-column image 2 nt + (cg >> 1); this wave reads the positions 8 ph .. 8 ph + 7 of them.  The two waves
+    // of a pair read disjoint halves of the run: per SIMD the weight traffic is wino_n128_kernel's.
+    const float* u_src = p.b + (size_t)(2 * nt + (cg >> 1)) * nslabs * WINO_IMG + ph * 8 * WINO_POS;
+    unsigned b_lane = (unsigned)(((lane >> 5) * 64 + (cg & 1) * 32 + (lane & 31)) * 16);
+    f32x4 fa[2][4], fb[2][4];
+    typedef const __attribute__((address_space(1))) f32x4* gf4_t;     // global, not flat: the opaque scalar base has lost its address space
+    auto b_load1 = [&](const float* src, auto G, auto I) {     // src: u_src + slab * WINO_IMG
+        constexpr int g = decltype(G)::value, i = decltype(I)::value;
+        const char* us = reinterpret_cast<const char*>(src + (g * 4 + i) * WINO_POS);
+        asm volatile("" : "+s"(us));
+        asm volatile("" : "+v"(b_lane));
+        fb[g & 1][i] = *(gf4_t)(us + b_lane);
+    };
+
+    halo.src(0);
+    halo.loads(hreg, 0);
+    {
+        const int s1 = min(1, nslabs - 1);             // slab 1, requested behind slab 0 so that the two latencies overlap
+        halo.src(s1);
+        halo.loads(hreg1, s1);
+    }
+#define DS_WINO_F(i) b_load1(u_src, DS_WINO_I(0), DS_WINO_I(i));
+    DS_WINO_EACH4(DS_WINO_F)
+#undef DS_WINO_F
+    __builtin_amdgcn_sched_barrier(0);                 // the requests stay in front of the set-up below
+
+    // ---- THEN, under their latency, the rest: the slot's LDS cell and its zero cells (written here, by the thread that owns the slot, in
+    // front of its first halo store; the first barrier publishes them), the transform's and the fragments' indices.
+    halo.cells(p, Hs, tid, r0);
+    const int WPH = p.WP >> 1, Wt = p.W >> 1;
 
     // ---- input transform: 32 tiles x 4 channel pairs, each split over FOUR threads by rows of B^T d B.  A thread owns (tile t_t, channels
     // 4 kh_t + 2 cpl .. + 1, row t_row): it reads the two rows of d its row of B^T d is made of (d0 - d2, d1 + d2, d2 - d1, d1 - d3) and
     // writes four positions.  kh_t and t_row are uniform per wave (wave = kh_t + 2 t_row): scalar branches, the same instruction count in
     // every wave.  Every value is made by the 64 x 64 kernel's operations on the same operands.
     const int t_t = (tid >> 1) & 31, cpl = tid & 1, kh_t = wave & 1, t_row = wave >> 1;
-    const int t_ty = t_t / Wt, t_tx = t_t - t_ty * Wt;
+    const int t_ty = t_t >> (lw - 1), t_tx = t_t & (Wt - 1);
     const int h_rd0 = ((kh_t * 2 * p.HP + 2 * t_ty + (t_row == 0 ? 0 : 1)) * WPH + t_tx) * 4 + cpl * 2;     // row 0 | 1 | 1 | 1 of d
     const int h_rd1 = ((kh_t * 2 * p.HP + 2 * t_ty + (t_row == 3 ? 3 : 2)) * WPH + t_tx) * 4 + cpl * 2;     // row 2 | 2 | 2 | 3
     const int h_par = p.HP * WPH * 4;              // odd-column plane
@@ -1214,50 +1319,20 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
         }
     };
 
-    // ---- transformed weights: global -> the B fragment registers, as in wino_n128_kernel: the 32 columns of channel group cg are rows
-    // 32 (cg & 1) .. + 31 of the 64-column image 2 nt + (cg >> 1); this wave reads the positions 8 ph .. 8 ph + 7 of them.  The two waves
-    // of a pair read disjoint halves of the run: per SIMD the weight traffic is wino_n128_kernel's.
-    const float* u_src = p.b + (size_t)(2 * nt + (cg >> 1)) * nslabs * WINO_IMG + ph * 8 * WINO_POS;
-    unsigned b_lane = (unsigned)(((lane >> 5) * 64 + (cg & 1) * 32 + (lane & 31)) * 16);
-    f32x4 fa[2][4], fb[2][4];
-    typedef const __attribute__((address_space(1))) f32x4* gf4_t;     // global, not flat: the opaque scalar base has lost its address space
-    auto b_load1 = [&](const float* src, auto G, auto I) {     // src: u_src + slab * WINO_IMG
-        constexpr int g = decltype(G)::value, i = decltype(I)::value;
-        const char* us = reinterpret_cast<const char*>(src + (g * 4 + i) * WINO_POS);
-        asm volatile("" : "+s"(us));
-        asm volatile("" : "+v"(b_lane));
-        fb[g & 1][i] = *(gf4_t)(us + b_lane);
-    };
-
-    f32x16 acc[8];                                 // position 8 ph + q
-#pragma unroll
-    for (int q = 0; q < 8; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+    f32x16 acc[8];                                 // position 8 ph + q; never zeroed: the first slab's first K step takes the constant 0 as C
     const int a_off = ((lane >> 5) * 32 + (lane & 31)) * 4 + ph * 8 * WN_POS;
 
-    // ---- prologue: halo 0 and 1 and transform 0 staged, halo 2 and the weights of (slab 0, group 0) requested (two barriers) -----------
-    halo.src(0);
-    halo.loads(hreg, 0);
-    {
-        typename Halo::Regs hreg1;
-        const int s1 = min(1, nslabs - 1);
-        halo.src(s1);
-        halo.loads(hreg1, s1);
-#define DS_WINO_F(i) b_load1(u_src, DS_WINO_I(0), DS_WINO_I(i));
-        DS_WINO_EACH4(DS_WINO_F)
-#undef DS_WINO_F
-        DS_RACE_SKEW(wave);
-        halo.store(hreg, Hs);
-        DS_RACE_SKEW(wave);
-        halo.store(hreg1, Hs + h_buf);
-    }
+    // ---- prologue, second part: halo 0 and 1 and transform 0 staged, halo 2 requested (two barriers) ------------------------------------
+    DS_RACE_SKEW(wave);
+    halo.store(hreg, Hs);
+    DS_RACE_SKEW(wave);
+    halo.store(hreg1, Hs + h_buf);
     {
         const int s2 = min(2, nslabs - 1);
         halo.src(s2);
         halo.loads(hreg, s2);
     }
-    __syncthreads();                                   // Hs[0], Hs[1] published
+    __syncthreads();                                   // Hs[0], Hs[1] and the zero cells published
 #define DS_WINO_TR1(i) tr_read1(Hs, DS_WINO_I(i));
     DS_WINO_EACH8(DS_WINO_TR1)
 #undef DS_WINO_TR1
@@ -1267,20 +1342,19 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
     __syncthreads();                                   // Vs[0] published
 
     // ---- K loop: ONE barrier per slab and no forced `vmcnt(0)`, as in wino_n128_kernel; 32 micro-slots per wave, two waves per SIMD --------
-    int s = 0;
-    do {                                               // nslabs >= 1 (conv3x3_wino_applicable)
+    // A slab in two parts.  front(s): the transform of slab s+1 and the halo store of slab s+2, i.e. everything in front of the MFMA
+    // block; back(s): the fragment reads of group 0, the block of micro-slots, the barrier.  Slab 0 is PEELED in front of the loop, and K
+    // step 0 of each of its positions takes the constant 0 as its C operand -- 0 + a b has the bits the zeroed accumulator gave -- so no
+    // move zeroes an accumulator.  The loop runs back(s), the exit test, front(s + 1): the MFMA block is the loop's header and the
+    // scalar branches on the wave's transform row, which end front(), jump straight to it; with the whole slab as the body the compiler
+    // put one more taken branch behind every barrier, and the layers of 64 slabs measured 0.3 - 0.7 % slower for it
+    // (profiles/wino_outside_ab.txt).
+    auto front = [&](const int s) {
         const int par = s & 1;
-        const float* vb = Vs + par * WN_IMG;
         float* vbn = Vs + (par ^ 1) * WN_IMG;          // last read by the MFMAs of slab s-1 (barrier s-1 passed)
         float* hb = Hs + par * h_buf;                  // last read by the transform of slab s, in front of barrier s-1
         const float* hbn = Hs + (par ^ 1) * h_buf;     // the halo of slab s+1, published at barrier s-1
-        const int s1 = min(s + 1, nslabs - 1), s3 = min(s + 3, nslabs - 1);
-        const float* uc = u_src + (size_t)s * WINO_IMG;
-        const float* un = u_src + (size_t)s1 * WINO_IMG;
-        auto a_read = [&](auto G, auto I) {
-            constexpr int g = decltype(G)::value, i = decltype(I)::value;
-            fa[g & 1][i] = *reinterpret_cast<const f32x4*>(vb + (g * 4 + i) * WN_POS + a_off);
-        };
+        const int s3 = min(s + 3, nslabs - 1);
 #define DS_WINO_TR1(i) tr_read1(hbn, DS_WINO_I(i));       // transform of slab s+1, first half: Hs[par ^ 1] -> registers
         DS_WINO_EACH8(DS_WINO_TR1)
 #undef DS_WINO_TR1
@@ -1289,6 +1363,18 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
         halo.src(s3);
         DS_RACE_SKEW(wave);
         tr_write(vbn);                                 // second half: its adds, registers -> Vs[par ^ 1]
+    };
+    auto back = [&](const int s, auto FIRST) {
+        constexpr bool first = decltype(FIRST)::value != 0;
+        const int par = s & 1;
+        const float* vb = Vs + par * WN_IMG;
+        const int s1 = min(s + 1, nslabs - 1), s3 = min(s + 3, nslabs - 1);
+        const float* uc = u_src + (size_t)s * WINO_IMG;
+        const float* un = u_src + (size_t)s1 * WINO_IMG;
+        auto a_read = [&](auto G, auto I) {
+            constexpr int g = decltype(G)::value, i = decltype(I)::value;
+            fa[g & 1][i] = *reinterpret_cast<const f32x4*>(vb + (g * 4 + i) * WN_POS + a_off);
+        };
         // micro-slot k of group g = k >> 4 (positions 8 ph + 4 g .. + 3), one memory instruction at most:
         //     16 g + 0 .. 3    the B fragments of the next group -- of group 0 of slab s+1 in group 1: a whole group (16 MFMAs) ahead of their use
         //     4 .. 7           (group 0) the halo load and the 3 coefficient loads of slab s+3
@@ -1306,11 +1392,16 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
                 a_read(DS_WINO_I(1), DS_WINO_I(k - 10));
             }
         };
+        auto c_in = [&](auto K) -> f32x16 {
+            constexpr int k = decltype(K)::value;
+            if constexpr (first && ((k >> 2) & 3) == 0) return f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            else return acc[(k >> 4) * 4 + (k & 3)];
+        };
         // micro-slot k: K step r = (k >> 2) & 3 of position 8 ph + 4 (k >> 4) + (k & 3), then its filler, pinned
 #define DS_WINO_STEP(k)                                                                                                                \
         acc[((k) >> 4) * 4 + ((k) & 3)] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[((k) >> 4) & 1][(k) & 3][((k) >> 2) & 3],            \
                                                                                fb[((k) >> 4) & 1][(k) & 3][((k) >> 2) & 3],            \
-                                                                               acc[((k) >> 4) * 4 + ((k) & 3)], 0, 0, 0);              \
+                                                                               c_in(DS_WINO_I(k)), 0, 0, 0);                           \
         fill(DS_WINO_I(k));                                                                                                            \
         __builtin_amdgcn_sched_barrier(0);
 #define DS_WINO_F(i) a_read(DS_WINO_I(0), DS_WINO_I(i));
@@ -1321,7 +1412,18 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
         DS_WINO_EACH16(DS_WINO_STEP, 16)
 #undef DS_WINO_STEP
         __syncthreads();                               // slab s done: Vs[par] dead; Vs and Hs [par ^ 1] published
-    } while (++s < nslabs);
+    };
+    front(0);
+    back(0, DS_WINO_I(1));                             // nslabs >= 1 (conv3x3_wino_applicable)
+    if (nslabs > 1) {
+        int s = 1;
+        front(1);
+        for (;;) {
+            back(s, DS_WINO_I(0));
+            if (++s >= nslabs) break;
+            front(s);
+        }
+    }
 
     // ---- output transform Y = A^T M A across the pair.  The sums over the row index i of position 4 i + j come first, as in the lane-local
     // output transform: patch row 0 is (M[j] + M[4 + j]) + M[8 + j], patch row 1 is (M[4 + j] - M[8 + j]) - M[12 + j].  The wave of half 0 holds rows
@@ -1330,35 +1432,116 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
     // wave w writes 16 KiB at smem + w * W8_XCH as [accumulator][register quad][lane][4] and reads the same cells of wave w ^ 4 -- the
     // same lane holds the same (tile, channel) in both waves of a pair.  One barrier.  Y[b] = the wave's 32 tiles x 32 channels at patch
     // pixel (ph, b).
+    //
+    // THE TAIL'S REQUESTS stand here, in front of the exchange's writes and its barrier: behind the K loop's last barrier its registers
+    // (fragments, halo, transform) are dead, and what the skip-slab loop and the epilogue read from global memory depends on nothing the
+    // exchange makes.  In the order of their use: the skip loop's weights of slab 0 and its pixels of slabs 0 and 1, the column bias, the
+    // image's cbias row, and all eight residual quads of the wave's patch row (two patch pixels x four passes).  Only the requests
+    // moved; every value is used where it was.
+    //
+    // Rows of the epilogue.  Lane l handles tile tl = 8 pass + (l >> 3) of the wave's 32 in pass 0 .. 3, i.e. output row
+    // m0 + (2 ty + ph) W + 2 tx + b with ty = tl / Wt, tx = tl % Wt.  Wt >= 8, so the lane's part of tl never carries into ty: the row is a
+    // scalar row of (pass, b) plus 2 (l >> 3), and an address is a 64-bit SCALAR base per (pass, b) plus ONE 32-bit lane offset per
+    // tensor -- the form of the K loop's loads.  A tile spans 128 rows, so the lane offset fits whatever the tensor's size.
+    const int nextra = (p.ec0 + p.ec1) / 32;
+    const int c4 = (lane & 7) * 4;
+    const int colw = n0 + cg * 32, col = colw + c4;    // the wave's first column (scalar), the lane's
+    typedef __attribute__((address_space(1))) f32x4* gf4w_t;
+    unsigned res_lane = (unsigned)(2 * (lane >> 3) * p.res_ld + c4) * 4u, out_lane = (unsigned)(2 * (lane >> 3) * p.ldo + c4) * 4u;   // BYTES
+    auto e_srow = [&](int pass, int b) {               // scalar
+        const int tp = pass * 8;
+        return m0 + (((2 * (tp >> (lw - 1)) + ph)) << lw) + 2 * (tp & (Wt - 1)) + b;
+    };
+
+    WinoSkip<512, 32> skip;
+    const float* wsk = p.b + (size_t)(p.N / 64) * nslabs * WINO_IMG + (size_t)(2 * nt + (cg >> 1)) * nextra * 2048;
+    f32x4 ga[2][2], gb[4];                             // skip-loop fragments: the two patch pixels' pixels of group g, and the weights of every group
+    auto e_load1 = [&](f32x4* dst, auto J) { skip.load1(dst, J); };
+    auto w_load1 = [&](int es, auto G) {
+        constexpr int g = decltype(G)::value;
+        const char* ws = reinterpret_cast<const char*>(wsk + (size_t)es * 2048 + g * WINO_POS);
+        asm volatile("" : "+s"(ws));
+        asm volatile("" : "+v"(b_lane));
+        gb[g] = *(gf4_t)(ws + b_lane);
+    };
+    f32x4 ereg[2], ereg0[2];
+    if (nextra > 0) {                                  // weights of slab 0, pixels of slab 0 and, behind them, of slab 1
+        skip.setup_loads(p, tid);
+        w_load1(0, DS_WINO_I(0)); w_load1(0, DS_WINO_I(1)); w_load1(0, DS_WINO_I(2)); w_load1(0, DS_WINO_I(3));
+        skip.sel(p, 0, m0);
+        e_load1(ereg0, DS_WINO_I(0)); e_load1(ereg0, DS_WINO_I(1));
+        skip.sel(p, min(1, nextra - 1), m0);
+        e_load1(ereg, DS_WINO_I(0)); e_load1(ereg, DS_WINO_I(1));
+    }
+    f32x4 cb = {0.f, 0.f, 0.f, 0.f}, cvu = {0.f, 0.f, 0.f, 0.f};
+    if (p.colbias) cb = *reinterpret_cast<const f32x4*>(p.colbias + col);
+    if (p.cbias) cvu = *reinterpret_cast<const f32x4*>(p.cbias + (size_t)(p.cbias_bcast ? 0 : img0) * p.cbias_ld + col);
+    f32x4 rv[2][4];
+    auto res_load = [&](auto B) {                      // the four residual quads of patch pixel (ph, b)
+        constexpr int b = decltype(B)::value;
+        if (p.res) {
+#pragma unroll
+            for (int pass = 0; pass < 4; ++pass) {
+                const char* rs = reinterpret_cast<const char*>(p.res + (size_t)e_srow(pass, b) * p.res_ld + colw);
+                asm volatile("" : "+s"(rs));
+                asm volatile("" : "+v"(res_lane));
+                rv[b][pass] = __builtin_nontemporal_load((gf4_t)(rs + res_lane));
+            }
+        }
+    };
+    res_load(DS_WINO_I(0));
+    res_load(DS_WINO_I(1));
+    __builtin_amdgcn_sched_barrier(0);                 // the requests stay in front of the exchange
+
     f32x16 Y[2];
     {
         float* xw = smem + wave * W8_XCH + lane * 4;
         const float* xr = smem + (wave ^ 4) * W8_XCH + lane * 4;
-        DS_RACE_SKEW(wave);
+        // `ph` is uniform per wave: ONE scalar branch per step, and each half names its accumulators directly (selected per register,
+        // `ph == 0 ? acc[4 + q] : acc[q]` cost 64 v_cndmask and left half 1's differences unpacked)
+        auto put = [&](const f32x16 (&m)[4]) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x16 m = ph == 0 ? acc[4 + q] : acc[q];
+            for (int q = 0; q < 4; ++q)
 #pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const f32x4 v = {m[4 * r4], m[4 * r4 + 1], m[4 * r4 + 2], m[4 * r4 + 3]};
-                *reinterpret_cast<f32x4*>(xw + (q * 4 + r4) * 256) = v;
-            }
-        }
-        __syncthreads();
-        f32x16 t[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
+                for (int r4 = 0; r4 < 4; ++r4) {
+                    const f32x4 v = {m[q][4 * r4], m[q][4 * r4 + 1], m[q][4 * r4 + 2], m[q][4 * r4 + 3]};
+                    *reinterpret_cast<f32x4*>(xw + (q * 4 + r4) * 256) = v;
+                }
+        };
+        auto get = [&](int j) {
             f32x16 o;
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) {
                 const f32x4 v = *reinterpret_cast<const f32x4*>(xr + (j * 4 + r4) * 256);
                 o[4 * r4] = v[0]; o[4 * r4 + 1] = v[1]; o[4 * r4 + 2] = v[2]; o[4 * r4 + 3] = v[3];
             }
-            if (ph == 0) t[j] = acc[j] + acc[4 + j] + o;
-            else t[j] = o - acc[j] - acc[4 + j];
-        }
+            return o;
+        };
+        DS_RACE_SKEW(wave);
+        // (the empty asm statements differ, so the two halves' stores are not merged back into one run of selected stores)
+        if (w8_uni(ph) == 0) { put(reinterpret_cast<const f32x16 (&)[4]>(acc[4])); asm volatile("; exchange: half 0 has written row 1" ::: "memory"); }
+        else { put(reinterpret_cast<const f32x16 (&)[4]>(acc[0])); asm volatile("; exchange: half 1 has written row 2" ::: "memory"); }
+        __syncthreads();
+        // The partner's accumulator j + 1 is read while sum j is made, no further ahead, and accumulator 1 only behind sum 0, which frees 16
+        // registers: all sixteen reads at once would hold 64 registers beside the 128 accumulators and what the tail has requested.
+        f32x16 t[4], o[2];
+        auto sum = [&](auto J) {
+            constexpr int j = decltype(J)::value;
+            __builtin_amdgcn_sched_barrier(0);
+            if (w8_uni(ph) == 0) t[j] = acc[j] + acc[4 + j] + o[j & 1];
+            else t[j] = w8_sub(w8_sub(o[j & 1], acc[j]), acc[4 + j]);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        o[0] = get(0);
+        sum(DS_WINO_I(0));
+        o[1] = get(1);
+        o[0] = get(2);
+        sum(DS_WINO_I(1));
+        o[1] = get(3);
+        sum(DS_WINO_I(2));
+        sum(DS_WINO_I(3));
         Y[0] = t[0] + t[1] + t[2];
-        Y[1] = t[1] - t[2] - t[3];
+        Y[1] = w8_sub(w8_sub(t[1], t[2]), t[3]);
     }
 
     // ---- appended 1x1 slabs (header comment, "Skip slabs") on this wave's TWO patch pixels (ph, 0) and (ph, 1): 32 MFMAs per slab and
@@ -1370,34 +1553,13 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
     //     slots 3, 4       the two ds_write_b128 of the pixels of slab es+1 -> V[(es+1) & 1]
     //     slots 5, 6       the two global loads of slab es+2 into the registers just stored
     // The barrier in front keeps the staging from overwriting what a partner has yet to read.
-    const int nextra = (p.ec0 + p.ec1) / 32;
     if (nextra > 0) {
+        skip.setup_cells(p, tid, lane, 0);
         __syncthreads();
-        const float* wsk = p.b + (size_t)(p.N / 64) * nslabs * WINO_IMG + (size_t)(2 * nt + (cg >> 1)) * nextra * 2048;
-        WinoSkip<512, 32> skip(p, tid, lane, 0);
-        auto e_load1 = [&](f32x4* dst, auto J) { skip.load1(dst, J); };
-        f32x4 ga[2][2], gb[4];                         // fragments: the two patch pixels' pixels of group g, and the weights of every group
-        auto w_load1 = [&](int es, auto G) {
-            constexpr int g = decltype(G)::value;
-            const char* ws = reinterpret_cast<const char*>(wsk + (size_t)es * 2048 + g * WINO_POS);
-            asm volatile("" : "+s"(ws));
-            asm volatile("" : "+v"(b_lane));
-            gb[g] = *(gf4_t)(ws + b_lane);
-        };
-
-        // prologue: weights of slab 0 requested, pixels of slab 0 staged, pixels of slab 1 requested behind them
-        f32x4 ereg[2];
-        {
-            f32x4 ereg0[2];
-            w_load1(0, DS_WINO_I(0)); w_load1(0, DS_WINO_I(1)); w_load1(0, DS_WINO_I(2)); w_load1(0, DS_WINO_I(3));
-            skip.sel(p, 0, m0);
-            e_load1(ereg0, DS_WINO_I(0)); e_load1(ereg0, DS_WINO_I(1));
-            skip.sel(p, min(1, nextra - 1), m0);
-            e_load1(ereg, DS_WINO_I(0)); e_load1(ereg, DS_WINO_I(1));
-            DS_RACE_SKEW(wave);
+        // prologue: the pixels of slab 0 staged (requested in front of the exchange, with the weights of slab 0 and the pixels of slab 1)
+        DS_RACE_SKEW(wave);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) *reinterpret_cast<f32x4*>(Vs + skip.lds[j]) = ereg0[j];
-        }
+        for (int j = 0; j < 2; ++j) *reinterpret_cast<f32x4*>(Vs + skip.lds[j]) = ereg0[j];
         __syncthreads();
 
         int es = 0;
@@ -1443,30 +1605,14 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
     // ---- the fused epilogue of patch row ph, one patch pixel at a time: the first kernel's, on this wave's 32 tiles x 32 channels.  The
     // staging rows lie in the cells this wave alone read in the exchange (its partner wrote them in front of the exchange's barrier).
     float* stage = smem + (wave ^ 4) * W8_XCH;
-    const int c4 = (lane & 7) * 4;
-    const int col = n0 + cg * 32 + c4;
-    f32x4 cb = {0.f, 0.f, 0.f, 0.f}, cvu = {0.f, 0.f, 0.f, 0.f};
-    if (p.colbias) cb = *reinterpret_cast<const f32x4*>(p.colbias + col);
-    if (p.cbias) cvu = *reinterpret_cast<const f32x4*>(p.cbias + (size_t)(p.cbias_bcast ? 0 : img0) * p.cbias_ld + col);
     const float acc_scale = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.acc_scale)));
     const float scale = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.scale)));
-    int e_row[4];                                      // output row of (pass, patch pixel (ph, 0)) of this lane
-#pragma unroll
-    for (int pass = 0; pass < 4; ++pass) {
-        const int tl = pass * 8 + (lane >> 3);
-        const int ty = tl / Wt, tx = tl - ty * Wt;
-        e_row[pass] = m0 + (2 * ty + ph) * p.W + 2 * tx;
-    }
     f32x4 st_s = {0.f, 0.f, 0.f, 0.f}, st_q = {0.f, 0.f, 0.f, 0.f};
+    // p.cbias, p.res and p.act are uniform per launch: scalar branches (the empty asm statements keep the compiler from turning them
+    // into four selects per quad again)
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
         const f32x16 y = Y[b];
-        f32x4 rv[4];
-        if (p.res) {
-#pragma unroll
-            for (int pass = 0; pass < 4; ++pass)
-                rv[pass] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p.res + (size_t)(e_row[pass] + b) * p.res_ld + col));
-        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) stage[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * WINO_EPI_LD + (lane & 31)] = y[r];
 #pragma unroll
@@ -1474,14 +1620,18 @@ __global__ void __launch_bounds__(512, 1) wino_w8_kernel(const KParams p) {
             f32x4 v = *reinterpret_cast<const f32x4*>(stage + (pass * 8 + (lane >> 3)) * WINO_EPI_LD + c4);
             v *= acc_scale;
             v += cb;
-            if (p.cbias) v += cvu;
-            if (p.res) v += rv[pass];
+            if (w8_uni(p.cbias) != nullptr) { v += cvu; asm volatile("" ::: "memory"); }
+            if (w8_uni(p.res) != nullptr) { v += rv[b][pass]; asm volatile("" ::: "memory"); }
             v *= scale;
-            if (p.act == DS_ACT_SILU) {
+            if (w8_uni(p.act) == DS_ACT_SILU) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = ds_silu(v[q]);
+                asm volatile("" ::: "memory");
             }
-            __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p.out + (size_t)(e_row[pass] + b) * p.ldo + col));
+            char* os = reinterpret_cast<char*>(p.out + (size_t)e_srow(pass, b) * p.ldo + colw);
+            asm volatile("" : "+s"(os));
+            asm volatile("" : "+v"(out_lane));
+            __builtin_nontemporal_store(v, (gf4w_t)(os + out_lane));
             st_s += v; st_q += v * v;
         }
     }
