@@ -64,6 +64,7 @@ _SIGNATURES = {
     'dsm_fir_resample': (C.c_int, [C.POINTER(DsmFirArgs), vp]),
     'dsm_fir_resample_supported': (C.c_int, [C.c_int] * 5),
     'dsm_zero_border': (C.c_int, [vp, vp, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    'dsm_dynamic_threshold_large': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_float, vp]),
     'dsm_traj_gram': (C.c_int, [vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp, C.c_longlong, vp]),
     'dsm_traj_gram_workspace_bytes': (C.c_longlong, [C.c_int, C.c_longlong, C.c_int]),
     'dsm_traj_gram_splits': (C.c_int, [C.c_int, C.c_longlong]),

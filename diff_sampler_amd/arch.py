@@ -73,6 +73,9 @@ class UNetSpec:
     # SFD's distilled, step-conditioned nets (sfd-main/models/networks_edm.py:290-292, :438-440, :153): a second embedding path `map_step*` and an
     # `affine_step` Linear in every block.  False: the key list and the parameters of the spec are those of a plain EDM net.
     step_condition: bool = False
+    # The consistency-model nets behind CMPrecond (cm_arch.py; networks_edm.py:540-541): the embedding takes 1000 * c_noise, and its frequencies
+    # are rounded as models/cm/nn.py timestep_embedding rounds them.
+    cm_noise: bool = False
 
     @property
     def ncsnpp(self) -> bool:

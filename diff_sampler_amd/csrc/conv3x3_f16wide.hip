@@ -20,8 +20,16 @@
 //     sum at any batch size (the batch-invariant mode needs nothing special here).
 // LDS: 2 halo buffers x 56 KB + D x NB x 8 KB weights = 160 KB at NB = 3 (D = 2), 160 KB at NB = 2 (D = 3), 144 KB at NB = 1 (D = 4): one
 // workgroup of eight waves per CU, like the kernel it derives from.
-// Scope: taps == 9, stride 1, ONE activated fp16 source [M][c0] (c0 % 64 == 0), no fused input normalisation, no appended 1x1 slabs,
-// W a power of two >= 128, H a power of two >= 4, cout % 64 == 0.  Reached from route_conv only where conv3x3_f16dma_applicable refuses.
+// Scope: taps == 9, stride 1, ONE activated fp16 source [M][c0] (c0 % 64 == 0), no fused input normalisation, W a power of two >= 128,
+// H a power of two >= 4, cout % 64 == 0.  Reached from route_conv only where conv3x3_f16dma_applicable refuses.
+// U-Net blocks above 64 pixels (the consistency-model LSUN nets: 256 channels x (1, 1, 2, 2, 4, 4) over 256 .. 8 pixels) need two more things:
+//   * the per-image embedding row of conv0 (ds_conv_args.cbias): both epilogues already take it -- a patch never spans images and
+//     HW % 32 == 0, so it is one row pointer per wave;
+//   * appended 1x1 slabs, the fused skip projection of conv1 (ds_conv_args.e0 / ec0, ec0 % 64 == 0, ONE raw fp16 source of the layer's own
+//     geometry; K order and packing of conv3x3_f16dma: ops.pack_conv_weight_f16(w, skip_w)): the X1 instantiations, kernel id 2576.  An
+//     appended slab is a one-tap slab (the centre tap) behind the 3x3 slabs.  Its operand goes through the same patch image, of which the
+//     centre tap reads the interior only (halo pixels 67 .. 328): DMA rounds 1 .. 5 of 7 are fetched.  The ec0 == 0 instantiations are the
+//     code they were (2575).
 #include "pipe_common.h"
 #include "epi_direct.h"
 
@@ -44,7 +52,8 @@ template <int NB>
 constexpr unsigned f16wide_smem() { return (unsigned)f16wide_ring<NB>() * NB * 8192u + 2u * HALO_BW; }
 
 // DIRECT: the epilogue that stores straight from the accumulators (fp16 rows out) or the staged one (fp32 rows out), as in conv3x3_f16dma
-template <int NB, bool DIRECT>
+// X1: the layer has appended 1x1 slabs (p.ec0 > 0)
+template <int NB, bool DIRECT, bool X1>
 __global__ void __launch_bounds__(512, 2) conv3x3_f16wide_kernel(const KParams p) {
     constexpr unsigned WB = NB * 8192u, HB = HALO_BW;
     constexpr int D = f16wide_ring<NB>();                      // weight ring: taps kt .. kt + D - 1 are in LDS or in flight
@@ -80,11 +89,22 @@ __global__ void __launch_bounds__(512, 2) conv3x3_f16wide_kernel(const KParams p
         const bool ok = hp < NPW && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
         hpix[j] = ok ? (img * p.H + y) * p.W + x : -1;
     }
-    const int NCH = p.c0 / 64;                                 // 64-channel slabs, nine taps each
-    const int KT = NCH * 9;
+    const int N33 = p.c0 / 64;                                 // 64-channel slabs, nine taps each
+    const int NCH = X1 ? N33 + p.ec0 / 64 : N33;               // ... followed by the appended 1x1 slabs, one (centre) tap each
+    const int KT = X1 ? N33 * 9 + (NCH - N33) : N33 * 9;
+    const _Float16* e0 = reinterpret_cast<const _Float16*>(p.e0);
+    constexpr int JX0 = (WPW + 1) / 64, JX1 = ((PH - 1) * WPW + PW - 1 + WPW + 1) / 64;      // DMA rounds that hold the patch interior: 1 .. 5
     auto halo_dma = [&](int chunk, int hbuf, auto jc) {        // DMA round j of slab `chunk` into halo buffer hbuf
         constexpr int j = decltype(jc)::value;
-        const _Float16* g = hpix[j] >= 0 ? a0 + (size_t)hpix[j] * p.lda0 + (size_t)chunk * 64 + hch : g_zero_halfs_wide;
+        const _Float16* base = a0 + (size_t)chunk * 64;
+        int ld = p.lda0;
+        if constexpr (X1) {
+            if (chunk >= N33) {                                // appended slab: the raw second tensor, interior rounds only
+                if (j < JX0 || j > JX1) return;
+                base = e0 + (size_t)(chunk - N33) * 64; ld = p.elda0;
+            }
+        }
+        const _Float16* g = hpix[j] >= 0 ? base + (size_t)hpix[j] * ld + hch : g_zero_halfs_wide;
         DS_RACE_SKEW(wave);
         __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(lds + D * WB + hbuf * HB + (j * 512 + wave * 64) * 16), 16, 0, 0);
     };
@@ -155,7 +175,10 @@ __global__ void __launch_bounds__(512, 2) conv3x3_f16wide_kernel(const KParams p
 
     // ---- prologue: halo of slab 0, round 0 of slab 1's halo, weights of the first D taps ------------------------------------------------
     static_for<NDMAW>([&](auto jc) { halo_dma(0, 0, jc); });
-    if (1 < NCH) halo_dma(1, 1, IC<0>{});
+    if (1 < NCH) {
+        if (X1 && 1 >= N33) static_for<NDMAW>([&](auto jc) { halo_dma(1, 1, jc); });      // slab 1 is a one-tap slab: all of it now
+        else halo_dma(1, 1, IC<0>{});
+    }
 #pragma unroll
     for (int d = 0; d < D; ++d)
         if (d < KT) w_dma(d, d);
@@ -165,7 +188,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_f16wide_kernel(const KParams p
     frag_read(P_, halo0 + a_addr(0, 0), halo0 + a_addr(1, 0), bbase);
 
     int kt = 0, slot = 0;                                      // slot = kt % D: the ring buffer of tap kt
-    // One tap (T9 = 0 .. 8 of a slab).  P holds the fragments of its K step 0 (read after the previous tap's barrier).
+    // One tap (T9 = 0 .. 8 of a 3x3 slab, 9 = the centre tap of an appended 1x1 slab).  P holds the fragments of its K step 0 (read after the previous tap's barrier).
     //   K steps 0..2 : reads of step k+1 in flight under the MFMAs of step k
     //   then         : all reads of this tap done, own DMAs landed (counted, see below), barrier: ring buffer kt % D -- and, at a slab end, the
     //                  halo buffer -- are free and the operands of tap kt+1 are in LDS
@@ -173,15 +196,18 @@ __global__ void __launch_bounds__(512, 2) conv3x3_f16wide_kernel(const KParams p
     //                  kt+D's weights and of the next halo round
     // Halo schedule: slab s+1 lives in buffer (s+1) & 1, free once slab s-1 is done; its 7 DMA rounds are issued one per barrier: round 0 at
     // the last tap of slab s-1 (or in the prologue), rounds 1 .. 6 behind the barriers of taps 0 .. 5 of slab s.  Every round is covered by
-    // the vmcnt(0) of the slab's last tap at the latest, and that tap's barrier publishes it.
+    // the vmcnt(0) of the slab's last tap at the latest, and that tap's barrier publishes it.  A slab that FOLLOWS a one-tap slab has no such
+    // taps to ride on: all its rounds are issued at once, at the last tap of the slab before that one (or in the prologue).
     auto tap = [&](auto t9c, int chunk) {
         Frag &P = P_, &Q = Q_;
         constexpr int T9 = decltype(t9c)::value;
-        constexpr bool SLAB_END = T9 == 8;
+        constexpr bool X = (T9 == 9);
+        constexpr int TT = X ? 4 : T9;
+        constexpr bool SLAB_END = X || T9 == 8;
         const unsigned hoff = halo0 + (unsigned)(chunk & 1) * HB;
         const unsigned woff = (unsigned)slot * WB;
         const int nslot = slot + 1 == D ? 0 : slot + 1;
-        const unsigned a_0 = a_addr(0, T9) + hoff, a_1 = a_addr(1, T9) + hoff;
+        const unsigned a_0 = a_addr(0, TT) + hoff, a_1 = a_addr(1, TT) + hoff;
         const unsigned vb = bbase + woff;
         frag_read(Q, a_0 ^ 32u, a_1 ^ 32u, vb ^ 32u);
         frag_wait(P, IC<NR>{});
@@ -204,14 +230,18 @@ __global__ void __launch_bounds__(512, 2) conv3x3_f16wide_kernel(const KParams p
             const unsigned nwoff = (unsigned)nslot * WB;
             if constexpr (SLAB_END) {
                 const unsigned nh = halo0 + (unsigned)((chunk + 1) & 1) * HB;
-                frag_read(P, nh + a_addr(0, 0), nh + a_addr(1, 0), bbase + nwoff);
+                const int nt9 = (X1 && chunk + 1 >= N33) ? 4 : 0;
+                frag_read(P, nh + a_addr(0, nt9), nh + a_addr(1, nt9), bbase + nwoff);
             } else {
                 frag_read(P, a_addr(0, T9 + 1) + hoff, a_addr(1, T9 + 1) + hoff, bbase + nwoff);
             }
         }
         auto halo_issue = [&]() {
             if constexpr (SLAB_END) {
-                if (chunk + 2 < NCH) halo_dma(chunk + 2, chunk & 1, IC<0>{});
+                if (chunk + 2 < NCH) {
+                    if (X1 && chunk + 1 >= N33) static_for<NDMAW>([&](auto jc) { halo_dma(chunk + 2, chunk & 1, jc); });   // next slab has one tap
+                    else halo_dma(chunk + 2, chunk & 1, IC<0>{});
+                }
             } else if constexpr (T9 + 1 < NDMAW) {
                 if (chunk + 1 < NCH) halo_dma(chunk + 1, (chunk + 1) & 1, IC<T9 + 1>{});
             }
@@ -233,11 +263,13 @@ __global__ void __launch_bounds__(512, 2) conv3x3_f16wide_kernel(const KParams p
         DS2_FENCE();
         ++kt; slot = nslot;
     };
-    for (int chunk = 0; chunk < NCH; ++chunk) {
+    for (int chunk = 0; chunk < N33; ++chunk) {
         tap(IC<0>{}, chunk); tap(IC<1>{}, chunk); tap(IC<2>{}, chunk);
         tap(IC<3>{}, chunk); tap(IC<4>{}, chunk); tap(IC<5>{}, chunk);
         tap(IC<6>{}, chunk); tap(IC<7>{}, chunk); tap(IC<8>{}, chunk);
     }
+    if constexpr (X1)
+        for (int chunk = N33; chunk < NCH; ++chunk) tap(IC<9>{}, chunk);
 #undef DSW_MM
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // (no fragment read is pending after the last tap; cheap insurance)
 
@@ -261,13 +293,14 @@ int launch_wide_nb(KParams p, int n_begin, int ntiles, hipStream_t stream) {
     int smem = (int)f16wide_smem<NB>();
     const bool staged = !epi_direct_ok(p, true, NB);
     const dim3 grid(grid_1d(p.mtiles, p.ntiles));
-    if (staged) {
-        DS_ENSURE_DYN_LDS((&conv3x3_f16wide_kernel<NB, false>), 160 * 1024);
-        hipLaunchKernelGGL((conv3x3_f16wide_kernel<NB, false>), grid, dim3(512), smem, stream, p);
-    } else {
-        DS_ENSURE_DYN_LDS((&conv3x3_f16wide_kernel<NB, true>), 160 * 1024);
-        hipLaunchKernelGGL((conv3x3_f16wide_kernel<NB, true>), grid, dim3(512), smem, stream, p);
-    }
+#define DSW_LAUNCH(DIRECT_, X1_)                                                                                   \
+    do {                                                                                                          \
+        DS_ENSURE_DYN_LDS((&conv3x3_f16wide_kernel<NB, DIRECT_, X1_>), 160 * 1024);                                \
+        hipLaunchKernelGGL((conv3x3_f16wide_kernel<NB, DIRECT_, X1_>), grid, dim3(512), smem, stream, p);          \
+    } while (0)
+    if (p.ec0) { if (staged) DSW_LAUNCH(false, true); else DSW_LAUNCH(true, true); }
+    else { if (staged) DSW_LAUNCH(false, false); else DSW_LAUNCH(true, false); }
+#undef DSW_LAUNCH
     DS_CHECK_LAUNCH();
     return DS_OK;
 }
@@ -280,7 +313,8 @@ bool conv3x3_f16wide_applicable(const KParams& p) {
     if (p.taps != 9 || p.stride > 1) return false;
     if (!pow2(p.W) || !pow2(p.H) || p.W < 2 * PW || p.H < PH) return false;           // whole 4 x 64 patches; narrower images: conv3x3_f16dma
     if (p.HW != p.H * p.W || p.M <= 0 || p.M % p.HW) return false;
-    if (p.c0 <= 0 || p.c0 % 64 || p.c1 || p.ec0 || p.ec1 || p.norm) return false;    // one activated fp16 source, no appended 1x1 slabs
+    if (p.c0 <= 0 || p.c0 % 64 || p.c1 || p.ec1 || p.norm) return false;             // one activated fp16 source
+    if (p.ec0 < 0 || p.ec0 % 64 || (p.ec0 && !p.e0)) return false;                   // appended 1x1 slabs: whole 64-channel slabs of one raw fp16 source
     if (p.rowbias || p.out_planar || p.act == DS_ACT_GEGLU) return false;
     if (p.N % 64 || !p.vec_ok || p.nrows_b < p.N) return false;
     return true;
@@ -307,7 +341,7 @@ void conv3x3_f16wide_route(const KParams& p, ConvRoute& r) {
             const int n = tiling(nb, tmp, &cost);
             if (cost < best_cost || (cost == best_cost && n < best_n)) { best_cost = cost; best_n = n; best_nb = nb; }
         }
-    r.kernel_id = 2575;
+    r.kernel_id = p.ec0 ? 2576 : 2575;                         // 2576: the instantiations with appended 1x1 slabs
     r.splits = 1;
     r.ngroups = tiling(best_nb, r.groups, &cost);
 }

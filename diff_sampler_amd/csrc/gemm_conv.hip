@@ -369,7 +369,7 @@ int launch_splitk_reduce(const KParams& p, hipStream_t stream) {
 
 }  // namespace igemm
 
-// conv3x3_f16wide.hip: the fp16-activation 3x3 convolution on 4 x 64 patches, for images wider than 64 pixels (kernel id 2575).  Declared here,
+// conv3x3_f16wide.hip: the fp16-activation 3x3 convolution on 4 x 64 patches, for images wider than 64 pixels (kernel ids 2575, and 2576 with appended 1x1 slabs).  Declared here,
 // next to their only caller, and not in igemm_common.h: the persisted tile table (diff_sampler_amd/data/tile_table.json) is tied to the hash
 // of every header of csrc/.
 namespace igemm {
@@ -592,6 +592,9 @@ static int route_conv(const ds_conv_args* a, KParams& p, ConvRoute& r) {
             if (!conv3x3_f16dma_applicable(p)) {
                 // images wider than 64 pixels (the AutoencoderKL decoder): the 4 x 64 patch form of the kernel, csrc/conv3x3_f16wide.hip
                 if (a->wgt_shift || !conv3x3_f16wide_applicable(p)) return DS_E_SHAPE;
+                // appended 1x1 slabs above 64 pixels (kernel id 2576) are a form a caller asks for (tune.variant bit 17): a call without the bit
+                // keeps the answer it always had, DS_E_SHAPE
+                if (p.ec0 && !(p.t_variant & 131072)) return DS_E_SHAPE;
                 p.part = nullptr; p.part_cap = 0;
                 conv3x3_f16wide_route(p, r);
                 return DS_OK;
@@ -677,7 +680,7 @@ extern "C" int ds_conv2d_nhwc(const ds_conv_args* a, void* stream) {
         case 2570: return launch_conv3x3_thin(p, s);
         case 2571: return launch_gemm_f16dma(p, s, true);
         case 2573: return launch_gemv_rows(p, s);
-        case 2575: return launch_conv3x3_f16wide(p, r, s);
+        case 2575: case 2576: return launch_conv3x3_f16wide(p, r, s);
         default: return launch_conv3x3_halo(p, r, s);      // 128 / 256 / 1284 / 2565 / 2568
     }
 }

@@ -193,6 +193,13 @@ DSM_API int dsm_fir_resample_supported(int up, int pad, int h, int w, int c);
  * pointer, x == out, a non-positive size, p < 0;  DS_E_SHAPE: a side or p above 32768, more than 2^31 - 1 output pixels. */
 DSM_API int dsm_zero_border(const float* x, float* out, long long outer, int h, int w, int inner, int p, void* stream);
 
+/* Dynamic thresholding of DPM-Solver++ (solver_utils.py:77-86) for samples beyond the LDS form of libdsamd's ds_dynamic_threshold (more than
+ * 38 144 values: images of 128 pixels and above; csrc/metrics/threshold_large.hip; added without a version step: nothing existing changed).
+ * x0, out: [n][per] fp32, out may be x0.  out = clamp(x0, -s, s) / s per sample with s = max(quantile_p(|x0|), 1), torch.quantile's linear
+ * interpolation -- the same radix select, on keys read from global memory.  DS_E_ARG: NULL pointer, n <= 0, per <= 1, p outside [0, 1];
+ * DS_E_SHAPE: more than 2^24 values per sample. */
+DSM_API int dsm_dynamic_threshold_large(const float* x0, float* out, int n, int per, float p, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------------------------
  * Trajectory analysis (diff-analyzer-main; csrc/metrics/traj.hip; added without a version step: nothing existing changed).
  *

@@ -499,7 +499,10 @@ __global__ void noise_embed_kernel(const float* __restrict__ sigma, int bs, cons
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= bs * half) return;
     const int b = idx / half, i = idx - b * half;
-    const float cn = (swap & 2) ? sigma[b] : logf(sigma[b]) / 4.0f;       // c_noise (networks_edm.py:491) or given
+    float cn = (swap & 2) ? sigma[b] : logf(sigma[b]) / 4.0f;             // c_noise (networks_edm.py:491) or given
+    // CMPrecond's rescaled_t = 1000 * (ln(sigma) / 4) (networks_edm.py:540-541), rounded in its order.  The angle reaches ~1 500 rad, where one
+    // ulp of the logarithm is 1e-4 of a radian: the logarithm is the correctly rounded one (through fp64), not logf's (off by an ulp now and then)
+    if (swap & 4) cn = 1000.0f * ((swap & 2) ? sigma[b] : (float)log((double)sigma[b]) / 4.0f);
     const float ang = cn * freqs[i];
     const float cs = cosf(ang), sn = sinf(ang);
     float* o = out + (size_t)b * out_ld;

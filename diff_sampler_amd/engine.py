@@ -36,8 +36,11 @@ from .plan import FUSE_NORM16_DEFAULT, Builder, Plan as _Plan, fuse_norm16_here,
 
 class UNetEngine:
     def __init__(self, spec: arch.UNetSpec, params: Dict[str, torch.Tensor], device='cuda', use_fp16=False, split_fp16=False,
-                 batch_invariant=False, up_phase=True, winograd=True):
-        """winograd (exact fp32 mode only, never with batch_invariant): the stride-1 3x3 layers the library would run on its 256 x 256 tiles
+                 batch_invariant=False, up_phase=True, winograd=True, wide16=True):
+        """wide16 (fp16 mode only): blocks whose output is wider than 64 pixels run their 3x3 convolutions on fp16 rows too, on the patch kernel
+        (csrc/conv3x3_f16wide.hip, kernel ids 2575 / 2576) -- with them the whole plan of a 256-pixel net keeps the fp16 stream.  False: such
+        blocks keep the fp32 routes (A/B runs).  No named EDM config has a layer above 64 pixels: their plans are the same either way.
+        winograd (exact fp32 mode only, never with batch_invariant): the stride-1 3x3 layers the library would run on its 256 x 256 tiles
         run in the Winograd form F(2x2, 3x3) instead (ds_conv_args.wino, csrc/conv3x3_wino.hip: 2.25 x fewer fp32 multiply-adds, weights
         transformed once per build; the same launches, the same kernel ids) wherever the library takes the layer; layers it refuses -- and
         every layer with False -- are emitted as the direct form, bit for bit.  Results differ from the direct form in rounding only (~1e-6
@@ -70,6 +73,10 @@ class UNetEngine:
         self.batch_invariant = bool(batch_invariant)
         self.up_phase = bool(up_phase) and not self.use_fp16 and not self.split_fp16
         self.winograd = bool(winograd) and not self.use_fp16 and not self.split_fp16 and not self.batch_invariant
+        self.wide16 = bool(wide16) and self.use_fp16
+        # CM nets: the output of middle_block (the spec's dec.RxR_in1) is the AMED tap: it gets a buffer of its own instead of a turn in the
+        # decoder's ping-pong pair, so that it outlives the evaluation like the encoder outputs the EDM nets tap
+        self.tap_block = next((b.name for b in spec.blocks if b.name.startswith('dec.') and b.name.endswith('_in1')), None) if spec.cm_noise else None
         # fp16 mode: GroupNorm apply + SiLU inside the fp16-activation convolution's LDS halo instead of a ds_norm_act pass (plan(): fz0 / fz1;
         # bit-identical results).  An attribute, not an argument, so that A/B runs flip it per engine: DS_FUSE_NORM16 sets the default.
         self.fuse_norm16 = fuse_norm16_value(os.environ.get('DS_FUSE_NORM16', FUSE_NORM16_DEFAULT))
@@ -91,6 +98,8 @@ class UNetEngine:
         freqs = torch.arange(0, half, dtype=torch.float32)
         freqs = freqs / (half - (1 if spec.pos_endpoint else 0))
         freqs = (1 / spec.pos_max_positions) ** freqs            # exactly networks_edm.py:193-195, on the host
+        if spec.cm_noise:                                        # timestep_embedding of the CM nets (models/cm/nn.py): the same numbers in its own rounding
+            freqs = torch.exp(-math.log(spec.pos_max_positions) * torch.arange(0, half, dtype=torch.float32) / half)
         if spec.embedding_type == 'fourier':                     # FourierEmbedding: the reference's own expression on its fp32 buffer (networks_edm.py:210)
             freqs = (2 * np.pi * params[f'{m}.map_noise.freqs'].detach().to(device='cpu', dtype=torch.float32)).to(torch.float32)
             assert freqs.shape == (half,), (tuple(freqs.shape), half)
@@ -201,7 +210,7 @@ class UNetEngine:
         step = bool(step)
         if step and not self.spec.step_condition:
             raise ValueError('this network was built without step-condition weights (UNetSpec.step_condition)')
-        key = (B, emb_rows, self.fuse_norm16) + ((True,) if step else ())
+        key = (B, emb_rows, self.fuse_norm16) + ((True,) if step else ()) + (('narrow16',) if self.use_fp16 and not self.wide16 else ())
         if key in self._plans:
             return self._plans[key]
         spec, w, lib = self.spec, self.w, self.lib
@@ -313,7 +322,9 @@ class UNetEngine:
         pos, e0, emb, aff = new(Bs, NC), new(Bs, E), new(Bs, E), new(Bs, self.aff_total)
         lab = bufs.get('labels')
         lpad = lab.shape[1] if lab is not None else 0
-        bd.add(self.lib.ds_noise_embed, (_ptr(bufs['sigma']), Bs, _ptr(w['freqs']), NC, int(spec.swap_sincos), _ptr(pos), NC), 'noise_embed')
+        # cm_noise (bit 2): the embedding of 1000 * c_noise (CMPrecond, networks_edm.py:540-541)
+        bd.add(self.lib.ds_noise_embed, (_ptr(bufs['sigma']), Bs, _ptr(w['freqs']), NC, int(spec.swap_sincos) | (4 if spec.cm_noise else 0), _ptr(pos), NC),
+               'noise_embed')
         if spec.model_type == 'SongUNet':
             src = pos
             if lab is not None:
@@ -336,7 +347,9 @@ class UNetEngine:
 
     def _dma16(self, bd, B, b):
         """Do both 3x3 convolutions of the block run on the fp16-activation kernels (conv1 with the fused skip projection's columns)?"""
-        return bool(bd.f16_conv_ok(B, b.res_out, b.cin, 0, b.cout) and bd.f16_conv_ok(B, b.res_out, b.cout, b.cin if b.skip_conv else 0, b.cout))
+        wide = self.wide16 and b.res_out > 64       # the patch kernel: no fused normalisation (Builder.fuses_norm16 ends at 64 pixels)
+        return bool(bd.f16_conv_ok(B, b.res_out, b.cin, 0, b.cout, wide=wide) and
+                    bd.f16_conv_ok(B, b.res_out, b.cout, b.cin if b.skip_conv else 0, b.cout, wide=wide))
 
     def _attn16(self, bd, B, b):
         """Attention block on the fp16 kernels end to end (CIFAR-10's single 256-wide head is not: fp32 kernel)?"""
@@ -371,8 +384,8 @@ class UNetEngine:
         # is applied by the convolution itself to its LDS halo (conv3x3_f16dma NORM: same arithmetic, same bits) and the ds_norm_act pass
         # -- with it the materialised concatenation and the raw copy for the skip projection -- disappears; the statistics launch
         # (ds_gn_finalize over the producers' column sums) stays.  Resampling blocks keep the pass for conv0.
-        fz0 = bool(ws.stream16 and rs == DS_RESAMPLE_NONE and bd.fuses_norm16(self.fuse_norm16, Ho, cout, x0, c0, x1, c1))
-        fz1 = bool(ws.stream16 and bd.fuses_norm16(self.fuse_norm16, Ho, cout, h16, cout))
+        fz0 = bool(ws.stream16 and Ho <= 64 and rs == DS_RESAMPLE_NONE and bd.fuses_norm16(self.fuse_norm16, Ho, cout, x0, c0, x1, c1))
+        fz1 = bool(ws.stream16 and Ho <= 64 and bd.fuses_norm16(self.fuse_norm16, Ho, cout, h16, cout))
         conv0 = dict(bias=w[f'{nm}.conv0.b'], stats=True, w16=w[f'{nm}.conv0.w16'], in_f16=True, out_f16=True, **cb)
         bd.norm('stats', x0, c0, c0, n, Hin, Hin, nm + '.norm0.stats', x1=x1, c1=c1, ld1=c1, groups=G_in, eps=b.eps,
                 gamma=w[f'{nm}.norm0.g'], beta=w[f'{nm}.norm0.b'], coefs=ncoef)
@@ -517,7 +530,7 @@ class UNetEngine:
         """Output buffer of a block (and of its attention): encoder outputs are kept for the skip stack, decoder outputs ping-pong between two
         fp32-sized buffers that blocks use in either dtype."""
         M = ws.B * b.res_out ** 2
-        if b.pushes_skip:
+        if b.pushes_skip or b.name == self.tap_block:
             return bd.new16(M, b.cout) if f16 else bd.new(M, b.cout)
         t = ws.dec_pp[ws.dec_i]
         if t is None:
@@ -587,11 +600,11 @@ class EDMDenoiser:
     edm_raw_output = True      # solvers._Run: ds_solver_update applies the EDM preconditioning to the raw output itself
 
     def __init__(self, spec: arch.UNetSpec, params: Dict[str, torch.Tensor], device='cuda', use_fp16=False, split_fp16=False,
-                 batch_invariant=False, up_phase=True, winograd=True):
-        """batch_invariant: same seed, same bits at any batch (UNetEngine).  up_phase, winograd: UNetEngine."""
+                 batch_invariant=False, up_phase=True, winograd=True, wide16=True):
+        """batch_invariant: same seed, same bits at any batch (UNetEngine).  up_phase, winograd, wide16: UNetEngine."""
         self.spec = spec
         self.engine = UNetEngine(spec, params, device, use_fp16=use_fp16, split_fp16=split_fp16, batch_invariant=batch_invariant,
-                                 up_phase=up_phase, winograd=winograd)
+                                 up_phase=up_phase, winograd=winograd, wide16=wide16)
         self.batch_invariant = bool(batch_invariant)
         self.device = self.engine.device
         self.img_resolution = spec.img_resolution
@@ -606,14 +619,14 @@ class EDMDenoiser:
 
     @classmethod
     def from_config(cls, name_or_kwargs, seed=0, mode='signal', device='cuda', use_fp16=False, split_fp16=False, batch_invariant=False,
-                    up_phase=True, winograd=True, step_condition=False):
+                    up_phase=True, winograd=True, step_condition=False, wide16=True):
         """step_condition: the net with SFD's step-condition weights (arch.UNetSpec.step_condition)."""
         kw = arch.NAMED_CONFIGS[name_or_kwargs] if isinstance(name_or_kwargs, str) else name_or_kwargs
         if step_condition:
             kw = dict(kw, step_condition=True)
         spec = arch.edm_precond_spec(**kw)
         return cls(spec, arch.init_params(spec, seed=seed, mode=mode), device, use_fp16=use_fp16, split_fp16=split_fp16,
-                   batch_invariant=batch_invariant, up_phase=up_phase, winograd=winograd)
+                   batch_invariant=batch_invariant, up_phase=up_phase, winograd=winograd, wide16=wide16)
 
     @classmethod
     def from_reference_module(cls, net, device='cuda', use_fp16=None, batch_invariant=False):

@@ -56,6 +56,7 @@ _FLUSH: Dict[int, torch.Tensor] = {}     # device index -> the 512 MiB scratch w
 # ignored -- stale or foreign measurements never steer a kernel -- and the miss is reported ONCE (RuntimeWarning): routing then falls back to
 # on-box measurement (+5 ... 9 s per network on first use, tiles no longer reproducible run to run).  DS_TILE_TABLE=<path> | off overrides.
 TILE_TABLE_FILE = os.environ.get('DS_TILE_TABLE', os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', 'tile_table.json'))
+WIDE_EXTRA = 131072             # ds_conv_tune.variant bit 17
 TILE_TABLE_KERNELS = ('conv3x3_f16dma.hip', 'gemm_f16dma.hip')
 _TABLE = {'loaded': False, 'entries': {}, 'why': None}
 
@@ -337,10 +338,10 @@ class Builder:
     def f16_conv_ok(self, n, side, cin, extra, cout, wide=False):
         """Does this stride-1 3x3 layer (`extra` = channels of a fused 1x1 skip projection) run on an fp16-activation kernel?  fp16 mode only;
         the library's answer for the shape on fp16 rows: conv3x3_f16dma (kernel ids 2566 / 2572), which ends at 64 pixels.
-        wide: above 64 pixels the layer may take the patch kernel (2575, csrc/conv3x3_f16wide.hip).  That kernel has one source, no fused skip
-        columns, no fused normalisation and no per-image bias row, so only a caller whose layers above 64 pixels are all of that kind asks
-        (the AutoencoderKL decoder); the denoisers' layers above 64 pixels keep the fp32 routes."""
-        return self.conv_mode == 1 and self.routes_to(self.shape_args(n, side, cin, cout, in_f16=True, ec0=extra), 2566, 2572, *((2575,) if wide else ()))
+        wide: above 64 pixels the layer may take the patch kernel (csrc/conv3x3_f16wide.hip: 2575, and 2576 with the fused skip columns).  That
+        kernel has one source and no fused normalisation, so only a caller that normalises such layers in a pass asks (the AutoencoderKL decoder;
+        UNetEngine under `wide16`)."""
+        return self.conv_mode == 1 and self.routes_to(self.shape_args(n, side, cin, cout, in_f16=True, ec0=extra), 2566, 2572, *((2575, 2576) if wide else ()))
 
     def gemm16_ok(self, rows, k, cout):
         """Does a 1x1 / Linear layer [rows][k] -> [rows][cout] on fp16 rows run on the fp16-activation GEMM (csrc/gemm_f16dma.hip)?"""
@@ -499,6 +500,8 @@ class Builder:
         a.in_f16, a.in_up2, a.wino = int(bool(in_f16)), int(bool(in_up2)), int(bool(wino))
         if self.invariant:
             a.tune.invariant = 3 if emb else 1
+        if in_f16 and ec0 and taps == 9 and stride == 1 and w > 64:
+            a.tune.variant = WIDE_EXTRA          # the patch kernel's appended 1x1 slabs (kernel id 2576) are asked for (ds_conv_tune.variant bit 17)
         if out_f16 or out.dtype == torch.float16:          # fp16 output rows: conv0 outputs, projection operands, the fp16 residual stream
             assert in_f16 and out.dtype == torch.float16 and cout % 64 == 0, name
             a.out_f16 = 1

@@ -304,7 +304,8 @@ def create_model(dataset_name=None, model_path=None, random_init=False, device=N
     batch_invariant: the engines' batch-invariant mode -- a seed's output bits do not depend on --batch, the seeds sharing its batch or
     the number of ranks.
 
-    EDM networks (cifar10 / ffhq / afhqv2 / imagenet64; sample.py:80-85) -> (net, 'edm'); Stable Diffusion v1.x latent
+    EDM networks (cifar10 / ffhq / afhqv2 / imagenet64; sample.py:80-85) -> (net, 'edm'); the consistency-model LSUN nets (lsun_bedroom /
+    lsun_cat; sample.py:86-91) -> (net, 'cm'); Stable Diffusion v1.x latent
     U-Net under classifier-free guidance (ms_coco; sample.py:111-116) -> (net, 'ldm').
 
     use_fp16: the fp16-operand kernels (fp32 accumulation and storage).  The reference leaves `--use_fp16` unwired
@@ -332,9 +333,19 @@ def create_model(dataset_name=None, model_path=None, random_init=False, device=N
         random = bool(random_init or model_path is None)
         return _cfg_denoiser(spec, params, vae_params, clip_sd, random, model_path, seed, device, guidance_rate, use_fp16, batch_invariant,
                              decode_latents, text_encoder), 'ldm'
+    if dataset_name in ('lsun_bedroom', 'lsun_cat'):
+        # the consistency-model pixel-space nets behind CMPrecond (sample.py:86-91): cm_engine.CMDenoiser.  A checkpoint is the UNetModel's
+        # state dict (models/cm/cm_model_loader.load_cm_model) and runs its body in fp16 as lsun_setting() says; random-init is fp32 unless asked
+        from .cm_engine import CMDenoiser
+        if random_init or model_path is None:
+            net = CMDenoiser.from_config(dataset_name, seed=seed, device=device, use_fp16=bool(use_fp16), batch_invariant=bool(batch_invariant))
+        else:
+            net = CMDenoiser.from_state_dict(model_path, dataset_name, device=device, use_fp16=(True if use_fp16 else None),
+                                             batch_invariant=bool(batch_invariant))
+        return net, 'cm'
     if dataset_name not in arch.NAMED_CONFIGS:
         raise ValueError(f'dataset {dataset_name!r}: only the EDM networks are in scope of the HIP engine '
-                         f'({sorted(k for k in arch.NAMED_CONFIGS if not k.startswith("tiny"))} and ms_coco); CM / ADM-classifier-guided / LSUN-LDM models run on the reference')
+                         f'({sorted(k for k in arch.NAMED_CONFIGS if not k.startswith("tiny"))} lsun_bedroom / lsun_cat and ms_coco); ADM-classifier-guided / LSUN-LDM models run on the reference')
     if random_init or model_path is None:
         net = EDMDenoiser.from_config(dataset_name, seed=seed, device=device, use_fp16=bool(use_fp16), batch_invariant=bool(batch_invariant))
     else:

@@ -78,11 +78,23 @@ def host_times(t_steps) -> List[float]:
 # ------------------------------------------------------------------------------------------------------------------
 # Dynamic thresholding and generic linear combinations on the device.
 
+THRESHOLD_LDS_CAP = 38144       # (per + 256) * 4 bytes <= 150 KiB: what ds_dynamic_threshold stages in LDS
+
+
 def dynamic_thresholding_fn(x0: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """clamp(x0, -s, s) / s with s = max(quantile_0.995(|x0|) per sample, 1) -- HIP radix-select kernel."""
+    """clamp(x0, -s, s) / s with s = max(quantile_0.995(|x0|) per sample, 1) -- HIP radix-select kernel.  A sample beyond what
+    ds_dynamic_threshold holds in LDS (THRESHOLD_LDS_CAP values: images of 128 pixels and above) takes the same selection on global memory
+    (dsm_dynamic_threshold_large, csrc/metrics/threshold_large.hip)."""
     x0 = x0.contiguous()
     out = torch.empty_like(x0) if out is None else out
-    ops.dynamic_threshold(x0, out, x0.shape[0], x0[0].numel(), 0.995)
+    per = x0[0].numel()
+    if per > THRESHOLD_LDS_CAP:
+        from . import _lib, _metrics_lib as ML
+        assert x0.is_cuda and out.is_cuda and x0.dtype == out.dtype == torch.float32 and out.is_contiguous()
+        ML.check(ML.load().dsm_dynamic_threshold_large(x0.data_ptr(), out.data_ptr(), x0.shape[0], per, 0.995, _lib.stream_ptr()),
+                 'dsm_dynamic_threshold_large')
+        return out
+    ops.dynamic_threshold(x0, out, x0.shape[0], per, 0.995)
     return out
 
 

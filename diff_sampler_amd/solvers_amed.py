@@ -114,8 +114,13 @@ def init_hook(net, class_labels=None):
     class-conditional EDM nets, ``enc['8x8_block3']`` otherwise, and the middle block (``middle_block.2``, the output of
     ``net.model.model.diffusion_model.middle_block``) for the latent-diffusion ``ldm_engine.CFGDenoiser``: there ``unet_enc_out[-1]`` is
     ``[2B, C, h, w]`` under classifier-free guidance, unconditional half first, as the reference's hook sees it.  ``guidance_type='uncond'``
-    LDMs and 256-pixel ADM / CM nets are outside the engine's AMED scope and raise."""
+    LDMs and the 256-pixel classifier-guided ADM net are outside the engine's AMED scope and raise.  A CM net
+    (cm_engine.CMDenoiser) taps the output of ``middle_block`` (solvers_amed.py:12-13), 8 x 8 at 256 pixels."""
     if _is_cfg_net(net) and net.guidance_type == 'classifier-free':
+        tap = _BottleneckTap(net, net.bottleneck_name)
+        return tap, _TapHandle(tap)
+    cm = bool(getattr(getattr(net, 'spec', None), 'cm_noise', False)) and hasattr(net, 'block_output')
+    if cm:
         tap = _BottleneckTap(net, net.bottleneck_name)
         return tap, _TapHandle(tap)
     if hasattr(net, 'guidance_type') or getattr(net, 'img_resolution', 0) == 256 or not hasattr(net, 'block_output'):
@@ -190,6 +195,11 @@ def _amed_loop(mode, net, latents, class_labels, condition, unconditional_condit
         raise RuntimeError('AMED samplers need the bottleneck tap of engine.EDMDenoiser or ldm_engine.CFGDenoiser (the reference hooks '
                            'net.model.enc[...] / ...diffusion_model.middle_block)')
     predictor = _as_predictor(predictor, latents.device)
+    if not cfg_net and hasattr(net, 'tap_shape'):           # a CM net taps middle_block's output: 8 x 8 at 256 pixels, the same check
+        _, tap_res = net.tap_shape()
+        if tap_res * tap_res != predictor.w['enc_layer0.weight'].shape[1]:
+            raise ValueError(f"the AMED tap of this net is {tap_res}x{tap_res} = {tap_res * tap_res} values per image, the predictor's "
+                             f"enc_layer0 takes {predictor.w['enc_layer0.weight'].shape[1]}")
     lib = _lib.load()
     dev, B = latents.device, run.B
     ts, x = run.ts, run.x

@@ -94,7 +94,9 @@ typedef struct ds_conv_tune {
      * (ADM channel counts); bit 14 (16384): force them regardless of the tile count (tests); bit 15 (32768): a Winograd launch on the
      * four-wave kernel of the 32 x 128 tile (wino_n128_kernel, one wave per SIMD) also at 16 and 32 columns, where the default is the
      * eight-wave one (wino_w8_kernel, two per SIMD) -- the same bits of output and column sums (A/B runs, tests); like bit 10, only a
-     * Winograd launch looks at it. */
+     * Winograd launch looks at it.  Bit 17 (131072): an fp16-activation 3x3 layer (in_f16) WIDER than 64 pixels may carry appended 1x1 slabs
+     * (ec0 % 64 == 0 on one raw fp16 source: kernel id 2576, csrc/conv3x3_f16wide.hip); without the bit such a call is DS_E_SHAPE, as it
+     * always was.  Only that route looks at it. */
     int variant;
     int splits;        /* > 0: split-K factor of a convolution that has a workspace (clamped to what the layer allows; 1 = never split).  The
                         * fp16-activation 3x3 kernel (in_f16) splits on its own where its widest tiling covers at most half of the CUs */
@@ -243,8 +245,9 @@ DS_API int ds_conv2d_nhwc(const ds_conv_args* a, void* stream);
  * embedding path's one-row projections; one fp32 source, bias / scale / SiLU only, cout >= 64; tune.mode != 0 keeps the matrix kernels), 2566 / 2572 =
  * the fp16-activation 3x3 kernel without / with the fused input normalisation (conv3x3_f16dma_kernel), 2567 = the fp16-activation 1x1 / Linear
  * (gemm_f16dma_kernel), 2568 = LDS-halo kernel <4> with 256-pixel x 192-channel tiles, 2575 = the fp16-activation 3x3 kernel on 4 x 64 patches for images wider than 64 pixels
- * (conv3x3_f16wide_kernel: power-of-two sides, one activated fp16 source, no fused normalisation, no appended 1x1 slabs, no split-K; reached only
- * where 2566 does not apply).  ABI 5: the answer comes from the same routing function as the launch, so for arguments
+ * (conv3x3_f16wide_kernel: power-of-two sides, one activated fp16 source, no fused normalisation, no split-K; reached only
+ * where 2566 does not apply), 2576 = the same kernel with appended 1x1 slabs (ec0 % 64 == 0 on one raw fp16 source: a U-Net block's fused skip
+ * projection above 64 pixels).  ABI 5: the answer comes from the same routing function as the launch, so for arguments
  * ds_conv2d_nhwc rejects it returns the same negative DS_E_* code (until ABI 4 it answered with a kernel id regardless).  Used by bench.py
  * to attribute time per kernel. */
 DS_API int ds_conv_kernel_id(const ds_conv_args* a);
@@ -501,6 +504,8 @@ DS_API int ds_token_embed(const int* tokens, const float* tok_table, const float
  * [nch/2]; swap=1 gives [sin | cos] (SongUNet), swap=0 [cos | sin] (DhariwalUNet).
  * swap bit 1 (value 2): `sigma` already holds the embedding argument (c_noise) -- the LDM `timestep_embedding`
  * (ldm/modules/diffusionmodules/util.py:151-171) fed by CFGPrecond's c_noise = M * sigma_inv(sigma) - 1.
+ * swap bit 2 (value 4): the argument is multiplied by 1000 -- CMPrecond's rescaled_t = 1000 * (ln(sigma) / 4)
+ * (networks_edm.py:540-541), rounded in that order.
  */
 DS_API int ds_noise_embed(const float* sigma, int bs, const float* freqs, int nch, int swap, float* out, int out_ld, void* stream);
 
